@@ -171,6 +171,69 @@ def instrumented_step(step, pl, frames, labels, idx, schedule="lanes", only=None
     return out
 
 
+DUMP_SAMPLE = 1 << 22            # elements of the seeded state / gradient samples (2 x 16 MB of float32)
+
+
+class StepState:
+    """Everything a training step reads that an earlier step wrote: the fp32 master weights, Adam's moments and step
+    counter, the BatchNorm running statistics and batch counts, and the dropout seed counter.  Captured as the seeded model
+    leaves construction; restore() puts it back with asynchronous device copies on the current stream.
+    The filter-gradient split sums add in arbitrary order (fp32 atomics), so the weights of two runs
+    drift apart by rounding from the first step on and the bf16 forward amplifies it; a step that starts from this state
+    computes the same thing every run, up to the rounding of that one step."""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.P = eng.P.data.clone()
+        self.live = [t for L in eng.layers for t in (L.rm, L.rv, L.nbt)] + [eng.drop_seed]
+        self.saved = [t.clone() for t in self.live]
+
+    def restore(self):
+        eng = self.eng
+        eng.P.data.copy_(self.P)
+        if eng.adam_m is not None:               # (created, zero, by the first step)
+            eng.adam_m.zero_()
+            eng.adam_v.zero_()
+            eng.adam_step.zero_()
+        torch._foreach_copy_(self.live, self.saved)       # (multi-tensor launches: ~190 small tensors)
+
+
+def _flat_sample(sd, keys, seed: int) -> torch.Tensor:
+    """A fixed, seeded sample of the tensors `keys` of `sd`, flattened in sorted key order, as float32 on the host."""
+    flat = torch.cat([sd[k].detach().reshape(-1).float().cpu() for k in sorted(keys)])
+    if flat.numel() <= DUMP_SAMPLE:
+        return flat
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(seed))[:DUMP_SAMPLE].sort().values
+    return flat[idx]
+
+
+def dump_outputs(out_dir: str, eng, pl, loss: torch.Tensor) -> None:
+    """What the last timed step handed its caller, as float32 .npy files under out_dir (about 32 MB in all; main() starts
+    that step from the seeded model's state, StepState):
+      loss          the step's mean cross-entropy, shape (1,)
+      logits        the forward's logits, (batch, classes)
+      state_sample  model.state_dict() (updated weights, BatchNorm running statistics) in checkpoint layout, flattened in
+                    sorted key order, DUMP_SAMPLE elements at fixed seeded positions
+      grad_sample   the step's parameter gradients in the same layout and order, sampled the same way
+    The checkpoint layout does not depend on the engine's arena layout, so two builds compare element for element."""
+    import numpy as np
+    if eng.device.type == "cuda":
+        torch.cuda.synchronize()
+    sd = eng.state_dict()
+    keep = eng.P.data.clone()                  # the gradient arena read through the same layout conversion
+    eng.P.data.copy_(eng.G)
+    gsd = eng.state_dict()
+    eng.P.data.copy_(keep)
+    grad_keys = [k for k in sd if k not in eng.dead and not k.endswith(("running_mean", "running_var", "num_batches_tracked"))]
+    arrays = {"loss": loss.detach().float().cpu().reshape(1),
+              "logits": pl.logits.detach().float().cpu(),
+              "state_sample": _flat_sample(sd, sd.keys(), seed=0),
+              "grad_sample": _flat_sample(gsd, grad_keys, seed=1)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy().astype(np.float32))
+
+
 def cpu_model_string() -> str:
     try:
         with open("/proc/cpuinfo") as f:
@@ -223,7 +286,12 @@ def main():
     ap.add_argument("--serial-stages", action="store_true", help="also report every kernel class timed alone on one stream")
     ap.add_argument("--ablate", default="", help="TIMING DIAGNOSTIC: comma-separated kernel classes (stage names, or laneN) the lane "
                     "scheduler skips -- the step's results are garbage and the line says so (tools/gpu_ablate.sh)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="start the last timed step from the seeded model's state and write what it computed (loss, logits, "
+                         "seeded samples of the updated state and of the gradients) as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from video_classification_amd import dist as sdist
     from video_classification_amd.engine import EngineOptions
@@ -242,6 +310,9 @@ def main():
     model = slowfast_r50_8x8(args.classes, dtype=torch.bfloat16, device=dev, seed=0, options=options)
     model.train()
     eng = model.engine
+    # --dump-outputs: the last timed step starts from the seeded model's state, so what it computes is a function of the
+    # arguments alone (StepState); the other steps train on as usual
+    start = StepState(eng) if args.dump_outputs else None
     gen = torch.Generator().manual_seed(1234 + rank)
     B = args.batch
     frames = torch.randn(B, 3, 32, 224, 224, generator=gen).to(torch.bfloat16).to(dev)   # N,C,T,H,W resident in HBM
@@ -261,16 +332,27 @@ def main():
     for _ in range(max(args.warmup, 2 if step.use_graph else 0)):
         step(frames, frames, labels, slow_t_index=idx)
     barrier()
+    dt = 0.0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if start is not None and i == args.steps - 1:
+            # the restore stays out of the clock: issued between two queued steps it added ~10 ms to the timed region (1.9 ms
+            # alone), while one step issued to an idle GPU takes as long as a pipelined one (27.2 against 27.3 ms)
+            barrier()
+            dt += time.perf_counter() - t0
+            start.restore()
+            barrier()
+            t0 = time.perf_counter()
         step(frames, frames, labels, slow_t_index=idx)
     barrier()
-    dt = time.perf_counter() - t0
+    dt += time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t[0])
     final_loss = float(step.loss[0])
+    if rank == 0 and args.dump_outputs:     # before the instrumented steps below, which train on
+        dump_outputs(args.dump_outputs, eng, eng._plan_for(frames, frames, idx, True), step.loss)
 
     line = {
         "metric": "clips/sec SlowFast-R50 8x8, 32x224^2 bf16 training step", "value": round(args.steps * B * world / dt, 2),
