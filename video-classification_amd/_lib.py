@@ -190,6 +190,13 @@ class _StemSrc(C.Structure):
                 ("kt", C.c_int32)]
 
 
+class _Stem2dSrc(C.Structure):
+    """include/sfk_stem2d.h sfk_stem2d_src: element (n, t, c, h, w) at src[n*sn + t*st + c*sc + h*sh + w*sw]"""
+    _fields_ = [("struct_size", C.c_uint32), ("src_dtype", C.c_int32), ("src", C.c_void_p), ("sn", C.c_int64),
+                ("st", C.c_int64), ("sc", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64), ("n", C.c_int32),
+                ("t", C.c_int32), ("c", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class _Tuning(C.Structure):
     """sfk_tuning: the write-once kernel-selection table of sfk_init (defaults = the measured best)."""
     _fields_ = [("struct_size", C.c_uint32), ("igemm_short_k", C.c_int32), ("igemm_small_k", C.c_int32), ("igemm_wide_store", C.c_int32),
@@ -272,6 +279,14 @@ SIGNATURES = {
     "sfk_abi_version": [],
     "sfk_status_string": [C.c_int],
 }
+# include/sfk_stem2d.h: the frames-as-channels stem of the res2d model, same library, its own header and version
+STEM2D_ABI_VERSION = 1     # include/sfk_stem2d.h SFK_STEM2D_ABI_VERSION
+SIGNATURES_STEM2D = {
+    "sfk_stem2d_abi_version": [],
+    "sfk_stem2d_tiles": [C.POINTER(_Stem2dSrc), _P_FMAP],
+    "sfk_stem2d_fwd": [C.POINTER(_Stem2dSrc), _PV, _P_FMAP, _PF, _PV],
+    "sfk_stem2d_wgrad": [C.POINTER(_Stem2dSrc), _P_FMAP, _PF, _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64}
 
 
@@ -285,6 +300,12 @@ def new_conv_desc() -> "_ConvDesc":
 def new_wgrad_desc() -> "_WgradDesc":
     d = _WgradDesc()
     d.struct_size = C.sizeof(_WgradDesc)
+    return d
+
+
+def new_stem2d_src() -> "_Stem2dSrc":
+    d = _Stem2dSrc()
+    d.struct_size = C.sizeof(_Stem2dSrc)
     return d
 
 
@@ -305,12 +326,15 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"{path} not found: build it with `python video-classification_amd/build.py` "
                        "(there is no CPU or PyTorch fallback for the SlowFast path)")
     lib = C.CDLL(path)
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPE[name] if name in _RESTYPE else C.c_int
+    for table in (SIGNATURES, SIGNATURES_STEM2D):
+        for name, argtypes in table.items():
+            fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+            fn.argtypes = argtypes
+            fn.restype = _RESTYPE[name] if name in _RESTYPE else C.c_int
     if lib.sfk_abi_version() != ABI_VERSION:
         raise SfkError(f"libsfk ABI version mismatch: library {lib.sfk_abi_version()}, binding {ABI_VERSION}")
+    if lib.sfk_stem2d_abi_version() != STEM2D_ABI_VERSION:
+        raise SfkError(f"libsfk stem2d ABI version mismatch: library {lib.sfk_stem2d_abi_version()}, binding {STEM2D_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -503,6 +527,32 @@ class HipBackend:
     def stem_conv_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
         d, fy = self._c_stem(p), _c_fmap(dy)
         return self._plain("sfk_stem_conv_wgrad", C.byref(d), C.byref(fy), _ptr(dw), keep=(d, fy, p, dy, dw))
+
+    # -- the frames-as-channels stem of res2d (include/sfk_stem2d.h); `src` of the StemSrc is indexed (n, c, t, h, w), kt = T
+    @staticmethod
+    def _c_stem2d(p: StemSrc) -> _Stem2dSrc:
+        s = p.src
+        assert s.dim() == 5 and p.t_index is None
+        d = new_stem2d_src()
+        d.src, d.src_dtype = s.data_ptr(), _DT[s.dtype]
+        d.sn, d.sc, d.st, d.sh, d.sw = s.stride()
+        d.n, d.c, d.t, d.h_in, d.w_in = s.shape
+        return d
+
+    def stem2d_tiles(self, p: StemSrc, y: FMap) -> int:
+        d, fy = self._c_stem2d(p), _c_fmap(y)
+        r = self.lib.sfk_stem2d_tiles(C.byref(d), C.byref(fy))
+        if r < 0:
+            _check(r, "sfk_stem2d_tiles")
+        return r
+
+    def stem2d_fwd(self, p: StemSrc, w: torch.Tensor, y: FMap, stats: Optional[torch.Tensor]):
+        d, fy = self._c_stem2d(p), _c_fmap(y)
+        return self._plain("sfk_stem2d_fwd", C.byref(d), _ptr(w), C.byref(fy), _ptr(stats), keep=(d, fy, p, w, y, stats))
+
+    def stem2d_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
+        d, fy = self._c_stem2d(p), _c_fmap(dy)
+        return self._plain("sfk_stem2d_wgrad", C.byref(d), C.byref(fy), _ptr(dw), keep=(d, fy, p, dy, dw))
 
     # -- generic plain-argument entry points
     def _plain(self, name, *args, keep=()):

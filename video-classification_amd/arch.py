@@ -6,6 +6,10 @@ Two parametrisations of the same wiring:
                   ModuleLists (+ dead residual/res_unit parameters), head pools (4,2,2) stride 1.
   canonical_spec  SlowFast-R50 8x8 of BASELINE.json's metric: T_fast = 4 T_slow, fast stem (5,7,7), fusion
                   (7,1,1)/(4,1,1), head pools (8,7,7)/(32,7,7)  ((deprecated)/(torchvideo)train.py:44-71,249).
+  resnet2d_spec   the reference's `res2d` model: torchvision ResNet-50 (v1.5) whose conv1 reads the clip's T frames of
+                  5 channels stacked on the channel axis (train.py:64-76) -- ONE pathway with T = 1 after a
+                  frames-as-channels stem (kt = T, no temporal padding, one output frame), torchvision keys
+                  `conv1`, `bn1`, `layer<s>.<i>.conv<1..3>` / `bn<1..3>` / `downsample.{0,1}`, `fc`, 4-D conv weights.
   slow_r50_spec   the reference's `res3d` model: pytorchvideo slow_r50 with a 5-channel (1,7,7) stem
                   ((deprecated)/train_3dresnet.py:47-51, train.py:79-89) -- ONE pathway: the slow pathway's wiring
                   without lateral fusion, keys `blocks.0.conv`, `blocks.<s>.res_blocks.<i>...`, `blocks.5.proj`.
@@ -41,6 +45,9 @@ class SlowFastSpec:
     dropout: float = 0.5
     bn_eps: float = 1e-5
     bn_momentum: float = 0.1
+    frames_as_channels: bool = False   # res2d: the stem stacks the clip's frames on its input channels (stem_kernels kt = T)
+    key_style: str = "pytorchvideo"    # 'torchvision': conv1 / layer<s>.<i>... / fc keys, 4-D conv weights
+    zero_init_gamma: bool = True       # block-final BatchNorm weight 0 at init (pytorchvideo); torchvision: 1
 
     @property
     def pathways(self) -> int:
@@ -76,6 +83,26 @@ def slow_r50_spec(num_class: int = 400, input_channels: int = 5, depth: int = 50
     return SlowFastSpec(num_class=num_class, input_channels=(input_channels,), stem_dim_outs=(64,),
                         stem_kernels=((1, 7, 7),), conv_a_kernels=(((1, 1, 1), (1, 1, 1), (3, 1, 1), (3, 1, 1)),),
                         depth=depth, fuse=False, fusion_ratio=0, head_pool_kernels=(tuple(head_pool_kernel),))
+
+
+def resnet2d_head_size(crop: int) -> int:
+    """spatial extent of res5 for a crop: stem /2, max pool /2, three stride-2 stages (= crop / 32 for multiples of 32)"""
+    h = (crop - 1) // 2 + 1
+    for _ in range(4):
+        h = (h - 1) // 2 + 1
+    return h
+
+
+def resnet2d_spec(num_class: int = 1000, clip_len: int = 10, channels_per_frame: int = 5, depth: int = 50,
+                  crop: int = 128) -> SlowFastSpec:
+    """torchvision resnet50 with the reference's Conv2d(T*C, 64, 7, 2, 3) conv1 (train.py:64-68): bottleneck stride on the
+    3x3, 1x1 strided projection on the first block of each stage, BN eps 1e-5 / momentum 0.1, no dropout before `fc`.
+    The head's global average pool covers res5 of a `crop` x `crop` input (fixed at construction)."""
+    s = resnet2d_head_size(crop)
+    return SlowFastSpec(num_class=num_class, input_channels=(channels_per_frame,), stem_dim_outs=(64,),
+                        stem_kernels=((clip_len, 7, 7),), conv_a_kernels=(((1, 1, 1),) * 4,), depth=depth, fuse=False,
+                        fusion_ratio=0, head_pool_kernels=((1, s, s),), dropout=0.0, frames_as_channels=True,
+                        key_style="torchvision", zero_init_gamma=False)
 
 
 # ----------------------------------------------------------------------------- layer records
@@ -143,12 +170,14 @@ def build_wiring(spec: SlowFastSpec) -> Wiring:
 
     def path(p: int) -> str:          # create_slowfast wraps every stage in MultiPathWayWithFuse, create_resnet does not
         return f".multipathway_blocks.{p}" if np_ == 2 else ""
+    tv = spec.key_style == "torchvision"
+    assert spec.key_style in ("pytorchvideo", "torchvision") and (not tv or np_ == 1)
     stems = []
     for p in range(np_):
         k = spec.stem_kernels[p]
-        stems.append(ConvBN(f"blocks.0{path(p)}.conv", f"blocks.0{path(p)}.norm",
-                            ConvGeom(spec.input_channels[p], spec.stem_dim_outs[p], k, (1, 2, 2), _half(k)),
-                            is_stem=True))
+        pad = (0, 3, 3) if spec.frames_as_channels else _half(k)      # frames as channels: one output frame
+        stems.append(ConvBN("conv1" if tv else f"blocks.0{path(p)}.conv", "bn1" if tv else f"blocks.0{path(p)}.norm",
+                            ConvGeom(spec.input_channels[p], spec.stem_dim_outs[p], k, (1, 2, 2), pad), is_stem=True))
     dead: List[DeadParam] = []
 
     def fusion(block_idx: int, dim_in: int) -> Optional[ConvBN]:
@@ -198,6 +227,17 @@ def build_wiring(spec: SlowFastSpec) -> Wiring:
                 s_b = (1, ss, ss) if i == 0 else (1, 1, 1)
                 base = f"blocks.{si + 1}{path(p)}.res_blocks.{i}"
                 proj = d_in != dims_out[p] or s_b != (1, 1, 1)
+                if tv:
+                    tb = f"layer{si + 1}.{i}"
+                    blocks.append(Block(
+                        conv_a=ConvBN(f"{tb}.conv1", f"{tb}.bn1", ConvGeom(d_in, dims_inner[p], ka, (1, 1, 1), _half(ka))),
+                        conv_b=ConvBN(f"{tb}.conv2", f"{tb}.bn2",
+                                      ConvGeom(dims_inner[p], dims_inner[p], (1, 3, 3), s_b, (0, 1, 1))),
+                        conv_c=ConvBN(f"{tb}.conv3", f"{tb}.bn3", ConvGeom(dims_inner[p], dims_out[p], (1, 1, 1)),
+                                      zero_init_gamma=spec.zero_init_gamma),
+                        branch1=ConvBN(f"{tb}.downsample.0", f"{tb}.downsample.1",
+                                       ConvGeom(d_in, dims_out[p], (1, 1, 1), s_b)) if proj else None))
+                    continue
                 blocks.append(Block(
                     conv_a=ConvBN(f"{base}.branch2.conv_a", f"{base}.branch2.norm_a",
                                   ConvGeom(d_in, dims_inner[p], ka, (1, 1, 1), _half(ka))),
@@ -215,5 +255,5 @@ def build_wiring(spec: SlowFastSpec) -> Wiring:
         dim_in_s = dim_out_s
         dim_out_s *= 2
     if np_ == 1:
-        return Wiring(spec, stems, stages, fusions, dead, head_in=dim_in_s, head_key="blocks.5.proj")
+        return Wiring(spec, stems, stages, fusions, dead, head_in=dim_in_s, head_key="fc" if tv else "blocks.5.proj")
     return Wiring(spec, stems, stages, fusions, dead, head_in=dim_in_s + dim_in_s // red)

@@ -287,7 +287,9 @@ class Engine:
             g = cb.geom
             if cb.is_stem:
                 # stem filters live in the stem layout [co][((f*cin+ci)*7+kh)*8+kw] (sfk_stem_conv_fwd)
-                assert g.k[1:] == (7, 7) and g.s == (1, 2, 2) and g.p == (g.k[0] // 2, 3, 3), g
+                # (frames-as-channels stem of res2d: the frame is the filter's "kt" axis, no temporal padding, one output frame)
+                pt = 0 if self.spec.frames_as_channels else g.k[0] // 2
+                assert g.k[1:] == (7, 7) and g.s == (1, 2, 2) and g.p == (pt, 3, 3), g
                 kp = stem_kp(g.cin, g.k[0])
                 eg = ConvGeom(kp, g.cout, (1, 1, 1))          # one row of kp "channels" per output channel
                 L = _Layer(cb, eg, g.k[0] * g.cin * 7 * 8, needs_dgrad=False)
@@ -335,7 +337,8 @@ class Engine:
         P.zero_()
         for L in self.layers:
             g = L.cb.geom
-            std = math.sqrt(2.0 / (g.cout * g.wtaps))
+            fan_taps = g.k[1] * g.k[2] if (L.cb.is_stem and self.spec.frames_as_channels) else g.wtaps   # Conv2d's fan_out
+            std = math.sqrt(2.0 / (g.cout * fan_taps))
             w = torch.randn(g.cout, g.cin, *g.k, generator=gen) * std
             P[L.w_off:L.w_off + L.w_numel] = self._to_engine_layout(L, w).to(self.device)
             P[L.g_off:L.g_off + L.c] = 0.0 if L.cb.zero_init_gamma else 1.0
@@ -357,8 +360,12 @@ class Engine:
             self.dead[d.key] = t.to(self.device)
 
     def _to_engine_layout(self, L: _Layer, w: torch.Tensor) -> torch.Tensor:
-        """(cout, cin, kt, kh, kw) -> flat [cout][tap][cin]  (stems: [cout][kt][(kh,kw,cin) zero-padded])."""
+        """(cout, cin, kt, kh, kw) -> flat [cout][tap][cin]  (stems: [cout][kt][(kh,kw,cin) zero-padded]).
+        4-D (torchvision) weights: (cout, cin, kh, kw), and the frames-as-channels stem's (cout, T*C, 7, 7) with input channel
+        t*C + c = frame t, channel c."""
         g = L.cb.geom
+        if w.dim() == 4 and L.cb.is_stem and self.spec.frames_as_channels:
+            w = w.reshape(g.cout, g.k[0], g.cin, 7, 7).permute(0, 2, 1, 3, 4)
         w = w.reshape(g.cout, g.cin, *g.k)
         if L.cb.is_stem:
             w = torch.nn.functional.pad(w.permute(0, 2, 1, 3, 4), (0, 1))           # co, kt, ci, kh, kw(7 -> 8)
@@ -374,12 +381,22 @@ class Engine:
         w = flat.reshape(g.cout, g.k[0], g.k[1], g.k[2], g.cin)
         return w.permute(0, 4, 1, 2, 3).contiguous()
 
-    # checkpoint surface: flat dict with pytorchvideo key names, fp32, reference tensor shapes
+    def _checkpoint_weight(self, L: _Layer, w5: torch.Tensor) -> torch.Tensor:
+        """(cout, cin, kt, kh, kw) -> the checkpoint's shape: 5-D, or 4-D for torchvision keys (stem: (cout, T*C, 7, 7))"""
+        if self.spec.key_style != "torchvision":
+            return w5
+        if L.cb.is_stem and self.spec.frames_as_channels:
+            g = L.cb.geom
+            return w5.permute(0, 2, 1, 3, 4).reshape(g.cout, g.k[0] * g.cin, 7, 7)
+        return w5[:, :, 0]
+
+    # checkpoint surface: flat dict with pytorchvideo (or torchvision) key names, fp32, reference tensor shapes
     def state_dict(self) -> Dict[str, torch.Tensor]:
         sd: Dict[str, torch.Tensor] = {}
         P = self.P.data
         for L in self.layers:
-            sd[L.cb.conv_key + ".weight"] = self._from_engine_layout(L, P[L.w_off:L.w_off + L.w_numel]).clone()
+            sd[L.cb.conv_key + ".weight"] = self._checkpoint_weight(
+                L, self._from_engine_layout(L, P[L.w_off:L.w_off + L.w_numel])).clone()
             nk = L.cb.norm_key
             sd[nk + ".weight"] = P[L.g_off:L.g_off + L.c].clone()
             sd[nk + ".bias"] = P[L.b_off:L.b_off + L.c].clone()
@@ -673,7 +690,9 @@ class Engine:
         st = pl.stem_state[p]
         esz = 2 if self.dtype == torch.bfloat16 else 4
         flops = 2.0 * st["y"].pixels * L.c * L.cb.geom.cin * L.cb.geom.wtaps
-        fwd = self.be.stem_conv_fwd(src, self.S[L.w_off:L.w_off + L.w_numel], st["y"], st["stats"])
+        f2d = self.spec.frames_as_channels               # res2d: Conv2d over the T*C stacked planes (include/sfk_stem2d.h)
+        fwd = (self.be.stem2d_fwd if f2d else self.be.stem_conv_fwd)(src, self.S[L.w_off:L.w_off + L.w_numel], st["y"],
+                                                                     st["stats"])
         meta = dict(kind="stem_fwd", layer=L.cb.conv_key, cout=L.c, flops=flops,
                     bytes=float(x5.numel() * x5.element_size() + st["y"].pixels * L.c * esz))
         if st["fwd_slot"] is None:
@@ -682,7 +701,7 @@ class Engine:
         else:
             pl.fwd[st["fwd_slot"]] = fwd
         if st.get("da") is not None:
-            bwd = self.be.stem_conv_wgrad(src, st["da"], self._gslice(L.w_off, L.w_numel))
+            bwd = (self.be.stem2d_wgrad if f2d else self.be.stem_conv_wgrad)(src, st["da"], self._gslice(L.w_off, L.w_numel))
             if st["bwd_slot"] is None:
                 st["bwd_slot"] = len(pl.bwd)
                 if p == 1:
@@ -701,6 +720,8 @@ class Engine:
         g = L.cb.geom
         n, _, t_in, h_in, w_in = x5.shape
         t_out = t_in if t_index is None else int(t_index.numel())
+        if self.spec.frames_as_channels:
+            t_out = 1
         ho = (h_in + 2 * g.p[1] - g.k[1]) // g.s[1] + 1
         wo = (w_in + 2 * g.p[2] - g.k[2]) // g.s[2] + 1
         tag = f"stem{p}"
@@ -712,7 +733,8 @@ class Engine:
         pl.stem_state[p] = st
         rec = None
         if train:
-            mt = self.be.stem_conv_tiles(StemSrc(x5, t_index, g.k[0]), y)
+            tiles = self.be.stem2d_tiles if self.spec.frames_as_channels else self.be.stem_conv_tiles
+            mt = tiles(StemSrc(x5, t_index, g.k[0]), y)
             st["stats"] = self._buf(f"stats.{tag}", mt * L.c * 2, torch.float32)
             self._stem_ops(pl, p, x5, t_index)
             mean = self._buf(f"mean.{tag}", L.c, torch.float32)
@@ -1329,6 +1351,22 @@ class Engine:
                 streams[op.lane].wait_event(ev)
             else:
                 op(handles[lane])
+
+    def input_view(self, x: torch.Tensor) -> torch.Tensor:
+        """The frames-as-channels stem (res2d) reads its clip as an (N, C, T, H, W) view; this makes that view, without a
+        copy, from the reference's (N, T*C, H, W) tensor (channel t*C + c, any strides) or the loader's (N, T, >=C, H, W)
+        memory.  Every other network: x as it is."""
+        if not self.spec.frames_as_channels:
+            return x
+        c, t = self.spec.input_channels[0], self.spec.stem_kernels[0][0]
+        if x.dim() == 4:
+            n, tc, h, w = x.shape
+            assert tc == t * c, f"res2d input has {tc} channels, the stem reads T*C = {t}*{c}"
+            sn, sk, sh, sw = x.stride()
+            return x.as_strided((n, c, t, h, w), (sn, sk, c * sk, sh, sw), x.storage_offset())
+        assert x.dim() == 5 and x.shape[1] == t and x.shape[2] >= c, \
+            f"res2d input: (N, {t}*{c}, H, W) or (N, {t}, >={c}, H, W), got {tuple(x.shape)}"
+        return x[:, :, :c].permute(0, 2, 1, 3, 4)
 
     def forward(self, x_slow: torch.Tensor, x_fast: torch.Tensor, train: bool, slow_t_index=None) -> Plan:
         """x_*: (N, C, T, H, W) views with ANY strides (the dataset's N,T,C,H,W memory is read in place).

@@ -46,9 +46,10 @@ class SlowFast(torch.nn.Module):
         self.slow_t_index: Optional[torch.Tensor] = None
 
     def forward(self, x, slow_t_index: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x: [x_slow, x_fast] (SlowFast) or one (N,C,T,H,W) tensor (the single-pathway res3d network)."""
+        """x: [x_slow, x_fast] (SlowFast) or one (N,C,T,H,W) tensor (the single-pathway res3d network); res2d: the
+        reference's (N, T*5, H, W) tensor or the loader's (N, T, >=5, H, W) memory (read in place, Engine.input_view)."""
         if self.spec.pathways == 1:
-            x_slow, x_fast = (x if torch.is_tensor(x) else x[0]), None
+            x_slow, x_fast = self.engine.input_view(x if torch.is_tensor(x) else x[0]), None
         else:
             x_slow, x_fast = x[0], x[1]
         if slow_t_index is None:
@@ -108,6 +109,15 @@ def slow_r50(num_class: int = 400, input_channels: int = 5, dtype=torch.float32,
     """The reference's `res3d` model (hub slow_r50 + 5-channel (1,7,7) stem, (deprecated)/train_3dresnet.py:47-51):
     the same engine with one pathway; ``model(x)`` takes the (N,C,T,H,W) tensor itself."""
     spec = arch.slow_r50_spec(num_class, input_channels, depth, tuple(head_pool_kernel))
+    return SlowFast(spec, dtype=dtype, device=device, backend=backend, seed=seed)
+
+
+def resnet50_2d_engine(num_class: int = 1000, clip_len: int = 10, crop: int = 128, dtype=torch.bfloat16, device="cuda",
+                       backend=None, seed: int = 0, depth: int = 50) -> SlowFast:
+    """The reference's `res2d` model (torchvision resnet50 with Conv2d(clip_len*5, 64, 7, 2, 3) as conv1, train.py:64-68) on
+    the engine: torchvision checkpoint keys and shapes (res2d.py's ResNet2d loads the same state dict), the frames-as-channels
+    stem (include/sfk_stem2d.h), a global average pool over the res5 map of a `crop` x `crop` input."""
+    spec = arch.resnet2d_spec(num_class, clip_len, 5, depth, crop)
     return SlowFast(spec, dtype=dtype, device=device, backend=backend, seed=seed)
 
 

@@ -122,6 +122,7 @@ class TrainStep:
 
     def __call__(self, x_slow, x_fast, labels, slow_t_index=None) -> torch.Tensor:
         eng = self.eng
+        x_slow = eng.input_view(x_slow)      # res2d: the (N, C, T, H, W) view of its stacked-frames input; else x as it is
         pl = eng._plan_for(x_slow, x_fast, slow_t_index, True)
         key = (pl.serial, labels.data_ptr(), pl.graph_epoch)
         ent = self._cache.get(key)
@@ -158,8 +159,9 @@ class TrainStep:
 class ModelManager:
     """Name -> (init_model, prepare_data), as reference train.py:39-60.  'slowfast*' and 'res3d' (SURVEY.md section
     8f-4: hub slow_r50 with a 5-channel stem, train.py:79-89 / (deprecated)/train_3dresnet.py:47-51) run on this
-    engine; 'res2d' (torchvision's 2-D ResNet-50 over T*C stacked frames, train.py:64-76) is host plumbing only
-    (res2d.py: BASELINE config 1, "CPU reference path, no GPU").  MODEL.ARCH = 'canonical8x8' swaps the SlowFast
+    engine; 'res2d' (torchvision's 2-D ResNet-50 over T*C stacked frames, train.py:64-76) is host plumbing
+    (res2d.py: BASELINE config 1, "CPU reference path, no GPU") unless MODEL.RES2D_BACKEND = 'engine', which builds the
+    same network on the engine (slowfast.resnet50_2d_engine, MODEL.DTYPE).  MODEL.ARCH = 'canonical8x8' swaps the SlowFast
     geometry for the hub model's ((deprecated)/(torchvideo)train.py:44-71,249)."""
 
     def __init__(self, cfg, device="cuda", backend=None):
@@ -193,14 +195,29 @@ class ModelManager:
             t = t.pin_memory()
         return t.to(self.device, non_blocking=True)
 
-    # ---- res2d (train.py:64-76): host plumbing, see res2d.py
+    # ---- res2d (train.py:64-76): host plumbing (res2d.py), or the engine with MODEL.RES2D_BACKEND = 'engine'
+    def _res2d_backend(self) -> str:
+        b = str(self.cfg.MODEL.get("RES2D_BACKEND", "torch")).lower()
+        if b not in ("torch", "engine"):
+            raise ValueError(f"MODEL.RES2D_BACKEND={b!r}: 'torch' or 'engine'")
+        return b
+
     def _init_res2d_model(self):
+        if self._res2d_backend() == "engine":
+            from .slowfast import _DTYPES, resnet50_2d_engine
+            dtype = _DTYPES[str(self.cfg.MODEL.get("DTYPE", "fp32")).lower()]
+            return resnet50_2d_engine(1000, int(self.cfg.CHALEARN.CLIP_LEN), crop_resize_dict[self.cfg.MODEL.R3D_INPUT],
+                                      dtype=dtype, device=self.device, backend=self.backend)
         from .res2d import resnet50_2d
         return resnet50_2d(in_channels=5 * int(self.cfg.CHALEARN.CLIP_LEN), num_classes=1000).to(
             "cpu" if torch.device(self.device).type != "cuda" else self.device)
 
     def _prepare_res2d_data(self, batch):
-        """(N,T,21,S,S)[:, :, :5] -> (N, T*5, S, S): frames stacked on the channel axis (train.py:70-76)."""
+        """(N,T,21,S,S)[:, :, :5] -> (N, T*5, S, S): frames stacked on the channel axis (train.py:70-76).  Engine backend:
+        the pinned (N,T,21,S,S) batch on the device, handed over as the strided (N,T,5,S,S) view -- no reshape copy; the
+        stem reads frame t, channel c as input channel t*5 + c (Engine.input_view)."""
+        if self._res2d_backend() == "engine":
+            return self._h2d(batch[self.cfg.MODEL.R3D_INPUT])[:, :, :5], self._h2d(batch['label'])
         dev = "cpu" if torch.device(self.device).type != "cuda" else self.device
         x = batch[self.cfg.MODEL.R3D_INPUT][:, :, :5].to(dev)
         n, t, c, h, w = x.size()
