@@ -197,6 +197,14 @@ class _Stem2dSrc(C.Structure):
                 ("t", C.c_int32), ("c", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class _U8Clip(C.Structure):
+    """include/sfk_u8stem.h sfk_u8_clip: byte (n, t, y, x, ch) at src[n*sn + t*st + y*sh + x*sw + ch]; the stem reads
+    channels c0 .. c0 + c - 1 through lut, shifted by the per-clip crop (or not)"""
+    _fields_ = [("struct_size", C.c_uint32), ("pad", C.c_int32), ("src", C.c_void_p), ("sn", C.c_int64), ("st", C.c_int64),
+                ("sh", C.c_int64), ("sw", C.c_int64), ("c0", C.c_int32), ("c", C.c_int32), ("n", C.c_int32),
+                ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("lut", C.c_void_p), ("crop", C.c_void_p)]
+
+
 class _Tuning(C.Structure):
     """sfk_tuning: the write-once kernel-selection table of sfk_init (defaults = the measured best)."""
     _fields_ = [("struct_size", C.c_uint32), ("igemm_short_k", C.c_int32), ("igemm_small_k", C.c_int32), ("igemm_wide_store", C.c_int32),
@@ -287,6 +295,15 @@ SIGNATURES_STEM2D = {
     "sfk_stem2d_fwd": [C.POINTER(_Stem2dSrc), _PV, _P_FMAP, _PF, _PV],
     "sfk_stem2d_wgrad": [C.POINTER(_Stem2dSrc), _P_FMAP, _PF, _PV],
 }
+# include/sfk_u8stem.h: the stems reading uint8 frames through a table (MODEL.U8_STEM), same library, its own header and version
+U8STEM_ABI_VERSION = 1     # include/sfk_u8stem.h SFK_U8STEM_ABI_VERSION
+SIGNATURES_U8STEM = {
+    "sfk_u8stem_abi_version": [],
+    "sfk_u8stem_conv_fwd": [C.POINTER(_U8Clip), _PV, _I32, _I32, _PV, _P_FMAP, _PF, _PV],
+    "sfk_u8stem_conv_wgrad": [C.POINTER(_U8Clip), _PV, _I32, _I32, _P_FMAP, _PF, _PV],
+    "sfk_u8stem2d_fwd": [C.POINTER(_U8Clip), _PV, _P_FMAP, _PF, _PV],
+    "sfk_u8stem2d_wgrad": [C.POINTER(_U8Clip), _P_FMAP, _PF, _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64}
 
 
@@ -309,6 +326,12 @@ def new_stem2d_src() -> "_Stem2dSrc":
     return d
 
 
+def new_u8_clip() -> "_U8Clip":
+    d = _U8Clip()
+    d.struct_size = C.sizeof(_U8Clip)
+    return d
+
+
 def new_tuning() -> "_Tuning":
     t = _Tuning()
     t.struct_size = C.sizeof(_Tuning)
@@ -326,7 +349,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"{path} not found: build it with `python video-classification_amd/build.py` "
                        "(there is no CPU or PyTorch fallback for the SlowFast path)")
     lib = C.CDLL(path)
-    for table in (SIGNATURES, SIGNATURES_STEM2D):
+    for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -335,6 +358,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk ABI version mismatch: library {lib.sfk_abi_version()}, binding {ABI_VERSION}")
     if lib.sfk_stem2d_abi_version() != STEM2D_ABI_VERSION:
         raise SfkError(f"libsfk stem2d ABI version mismatch: library {lib.sfk_stem2d_abi_version()}, binding {STEM2D_ABI_VERSION}")
+    if lib.sfk_u8stem_abi_version() != U8STEM_ABI_VERSION:
+        raise SfkError(f"libsfk u8stem ABI version mismatch: library {lib.sfk_u8stem_abi_version()}, binding {U8STEM_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -553,6 +578,48 @@ class HipBackend:
     def stem2d_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
         d, fy = self._c_stem2d(p), _c_fmap(dy)
         return self._plain("sfk_stem2d_wgrad", C.byref(d), C.byref(fy), _ptr(dw), keep=(d, fy, p, dy, dw))
+
+    # -- the stems reading uint8 frames (include/sfk_u8stem.h); `src` of the StemSrc is an input_pipeline.U8Clip
+    @staticmethod
+    def _c_u8clip(p: StemSrc) -> _U8Clip:
+        x = p.src
+        f = x.frames
+        assert f.dtype == torch.uint8 and f.dim() == 5 and f.stride(4) == 1
+        d = new_u8_clip()
+        d.src, d.lut, d.crop, d.pad = f.data_ptr(), x.lut.data_ptr(), _ptr(x.crop), x.pad
+        d.sn, d.st, d.sh, d.sw = f.stride()[:4]
+        d.c0, d.c = x.c0, x.c
+        d.n, d.t, d.h, d.w = f.shape[:4]
+        return d
+
+    def u8stem_tiles(self, p: StemSrc, y: FMap) -> int:
+        """the BatchNorm partial-sum rows of either u8 stem: sfk_stem_conv_tiles' count, which depends on the output map only
+        (for the one-frame output of the 2-D stem it equals sfk_stem2d_tiles')"""
+        d, fy = _StemSrc(), _c_fmap(y)
+        r = self.lib.sfk_stem_conv_tiles(C.byref(d), C.byref(fy))
+        if r < 0:
+            _check(r, "sfk_stem_conv_tiles")
+        return r
+
+    def u8stem_conv_fwd(self, p: StemSrc, w: torch.Tensor, y: FMap, stats: Optional[torch.Tensor]):
+        d, fy = self._c_u8clip(p), _c_fmap(y)
+        return self._plain("sfk_u8stem_conv_fwd", C.byref(d), _ptr(p.t_index), p.t_len, p.kt, _ptr(w), C.byref(fy),
+                           _ptr(stats), keep=(d, fy, p, w, y, stats))
+
+    def u8stem_conv_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
+        d, fy = self._c_u8clip(p), _c_fmap(dy)
+        return self._plain("sfk_u8stem_conv_wgrad", C.byref(d), _ptr(p.t_index), p.t_len, p.kt, C.byref(fy), _ptr(dw),
+                           keep=(d, fy, p, dy, dw))
+
+    def u8stem2d_fwd(self, p: StemSrc, w: torch.Tensor, y: FMap, stats: Optional[torch.Tensor]):
+        assert p.t_index is None
+        d, fy = self._c_u8clip(p), _c_fmap(y)
+        return self._plain("sfk_u8stem2d_fwd", C.byref(d), _ptr(w), C.byref(fy), _ptr(stats), keep=(d, fy, p, w, y, stats))
+
+    def u8stem2d_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
+        assert p.t_index is None
+        d, fy = self._c_u8clip(p), _c_fmap(dy)
+        return self._plain("sfk_u8stem2d_wgrad", C.byref(d), C.byref(fy), _ptr(dw), keep=(d, fy, p, dy, dw))
 
     # -- generic plain-argument entry points
     def _plain(self, name, *args, keep=()):

@@ -22,7 +22,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     deps = [os.path.join(CSRC, "sfk_common.h"), os.path.join(CSRC, "conv_igemm_epi.h"), os.path.join(CSRC, "conv_wgrad_common.h"), os.path.join(CSRC, "conv_wgrad_band_acc.inc"), os.path.join(ROOT, "include", "sfk.h"),
-            os.path.join(ROOT, "include", "sfk_stem2d.h")]
+            os.path.join(ROOT, "include", "sfk_stem2d.h"), os.path.join(ROOT, "include", "sfk_u8stem.h")]
     flags = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
     flags += os.environ.get("SFK_EXTRA_FLAGS", "").split()          # experiment builds (tools/), with SFK_LIB_OUT
 

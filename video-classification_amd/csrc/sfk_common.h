@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "sfk.h"
+#include "sfk_u8stem.h"
 
 // the process-wide tuning table of sfk_init (optim_misc.hip); read-only after the first launch
 __attribute__((visibility("hidden"))) const sfk_tuning& sfk_tune();
@@ -104,4 +105,21 @@ static inline int64_t sfk_fmap_pixels(const sfk_fmap* f) { return (int64_t)f->n 
 // bytes from f->ptr to the end of the map's pixel records (the extent a buffer resource must cover)
 static inline int64_t sfk_fmap_bytes(const sfk_fmap* f) {
   return sfk_fmap_pixels(f) * f->ld * (f->dtype == SFK_BF16 ? 2 : 4);
+}
+
+// Source tag of the stem kernels' S template parameter for a uint8 clip read through a 256-entry f32 table
+// (include/sfk_u8stem.h), beside float and bf16_t.
+struct U8Lut {};
+// U8Pix<CIN>: the same source with a compile-time channel count, staged a pixel at a time (stem_conv.hip's forward)
+template <int CIN> struct U8Pix {};
+template <typename S> inline constexpr bool sfk_is_u8 = false;
+template <> inline constexpr bool sfk_is_u8<U8Lut> = true;
+template <int CIN> inline constexpr bool sfk_is_u8<U8Pix<CIN>> = true;
+template <typename S> inline constexpr int sfk_u8_pix = 0;
+template <int CIN> inline constexpr int sfk_u8_pix<U8Pix<CIN>> = CIN;
+// the host checks shared by the 3-D and 2-D uint8 stem entry points (SFK_ERR_INVALID when false)
+static inline bool sfk_u8_clip_ok(const sfk_u8_clip* x) {
+  return x && x->struct_size == sizeof(sfk_u8_clip) && x->src && x->lut && x->pad >= 0 && x->c0 >= 0 && x->c > 0 &&
+         x->n > 0 && x->t > 0 && x->h > 0 && x->w > 0 && x->sn >= 0 && x->st >= 0 && x->sh >= 0 &&
+         (int64_t)x->c0 + x->c <= x->sw;
 }

@@ -13,6 +13,8 @@
 //             ([co][pixel]), the plane's patch beside it; A = 8 consecutive pixels of one co, B = the patch values of the
 //             same 8 pixels for one (kh, kw).  dW[cout][plane][7][8] stays in registers over the tile range and is added
 //             to dw with fp32 atomics (dw zeroed on the stream first).
+// Both kernels also read the loader's HWC uint8 frames through a 256-entry f32 table with a per-clip crop shift
+// (S = U8Lut, include/sfk_u8stem.h): the normalised, cropped float clip is then never written.
 #include "sfk_common.h"
 #include "sfk_stem2d.h"
 
@@ -42,6 +44,9 @@ struct S2K {
   float* stats;
   float* dw;
   int tiles_per_block;
+  const float* lut;               // S = U8Lut: value of each source byte (sc = 1: channel c at byte c)
+  const int32_t* crop;            // S = U8Lut: [n][2] (top, left) or null; the frame pixel of (hi, wi) is (hi + top - pad, wi + left - pad)
+  int pad;
 };
 
 template <typename S> __device__ __forceinline__ float ldsrc(const void* p, int64_t off);
@@ -51,15 +56,32 @@ template <> __device__ __forceinline__ float ldsrc<bf16_t>(const void* p, int64_
 struct PatchSlots {
   int64_t off[NSLOT];
   bool ok[NSLOT];
-  __device__ __forceinline__ void set_tile(const S2K& k, int ho0, int wo0) {
+  template <typename S>
+  __device__ __forceinline__ void set_tile(const S2K& k, int n, int ho0, int wo0) {
+    // uint8 source: the crop shifts clip n's frame under the virtual clip; slots whose shifted pixel is outside the frame
+    // are masked like the conv's own padding (any crop value is safe: their loads read the plane's first byte)
+    int64_t dy = 0, dx = 0;
+    if constexpr (sfk_is_u8<S>) {
+      if (k.crop) {
+        dy = (int64_t)k.crop[2 * n] - k.pad;
+        dx = (int64_t)k.crop[2 * n + 1] - k.pad;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < NSLOT; ++i) {
       const int e = threadIdx.x + 256 * i;
       uint32_t r, c;
       k.dpc.divmod((uint32_t)e, r, c);
       const int hi = 2 * ho0 - 3 + (int)r, wi = 2 * wo0 - 3 + (int)c;
-      ok[i] = e < PLANE && (unsigned)hi < (unsigned)k.h_in && (unsigned)wi < (unsigned)k.w_in;
-      off[i] = ok[i] ? (int64_t)hi * k.sh + (int64_t)wi * k.sw : 0;
+      if constexpr (sfk_is_u8<S>) {
+        const int64_t y = hi + dy, x = wi + dx;
+        ok[i] = e < PLANE && (unsigned)hi < (unsigned)k.h_in && (unsigned)wi < (unsigned)k.w_in &&
+                (uint64_t)y < (uint64_t)k.h_in && (uint64_t)x < (uint64_t)k.w_in;
+        off[i] = ok[i] ? y * k.sh + x * k.sw : 0;
+      } else {
+        ok[i] = e < PLANE && (unsigned)hi < (unsigned)k.h_in && (unsigned)wi < (unsigned)k.w_in;
+        off[i] = ok[i] ? (int64_t)hi * k.sh + (int64_t)wi * k.sw : 0;
+      }
     }
   }
 };
@@ -72,13 +94,17 @@ __device__ __forceinline__ int64_t plane_base(const S2K& k, int pl, int n) {
   return (int64_t)n * k.sn + (int64_t)t * k.st + (int64_t)c * k.sc;
 }
 
+// lut: S = U8Lut, the block's LDS copy of the table (one gather per element from LDS instead of a second global round trip)
 template <typename S>
-__device__ __forceinline__ void plane_fetch(const S2K& k, const PatchSlots& ps, int64_t base, float (&v)[NSLOT]) {
+__device__ __forceinline__ void plane_fetch(const S2K& k, const PatchSlots& ps, int64_t base, float (&v)[NSLOT],
+                                            const float* lut = nullptr) {
   const bool bok = base >= 0;              // branch-free: padding slots read the plane's first element, zeroed by a select
   const int64_t b = bok ? base : 0;
 #pragma unroll
   for (int i = 0; i < NSLOT; ++i) {
-    const float x = ldsrc<S>(k.src, b + ps.off[i]);
+    float x;
+    if constexpr (sfk_is_u8<S>) x = lut[static_cast<const uint8_t*>(k.src)[b + ps.off[i]]];   // the table's f32, as the float clip holds it
+    else x = ldsrc<S>(k.src, b + ps.off[i]);
     v[i] = (bok && ps.ok[i]) ? x : 0.f;
   }
 }
@@ -156,12 +182,17 @@ __global__ __launch_bounds__(256) void stem2d_fwd_kernel(const S2K k) {
   T* wl = reinterpret_cast<T*>(smem);                         // [NB][64][WROW]
   T* patch = wl + NB * 64 * WROW;                             // [NB][CP][PLANE]
   float* red = reinterpret_cast<float*>(patch + NB * CP * PLANE);   // [4 waves][64][2]
+  float* lut = red + 4 * 64 * 2;                              // S = U8Lut: [256]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
+  if constexpr (sfk_is_u8<S>) {
+    lut[tid] = k.lut[tid];
+    __syncthreads();
+  }
   const int tile = blockIdx.x;
   int n, ho0, wo0;
   tile_coords(k, tile, n, ho0, wo0);
   PatchSlots ps;
-  ps.set_tile(k, ho0, wo0);
+  ps.set_tile<S>(k, n, ho0, wo0);
   const T* wp = static_cast<const T*>(k.w);
   const int krows8 = k.kp / 8;                                // 8-element rows of the global filter row
 
@@ -172,7 +203,7 @@ __global__ __launch_bounds__(256) void stem2d_fwd_kernel(const S2K k) {
 #pragma unroll
     for (int q = 0; q < CP; ++q) base[q] = plane_base(k, c * CP + q, n);
 #pragma unroll
-    for (int q = 0; q < CP; ++q) plane_fetch<S>(k, ps, base[q], pv[q]);
+    for (int q = 0; q < CP; ++q) plane_fetch<S>(k, ps, base[q], pv[q], lut);
 #pragma unroll
     for (int e = 0; e < WSEG; ++e) {
       const int idx = tid + 256 * e, row = idx / CR, seg = idx - row * CR, r8 = c * CR + seg;
@@ -287,7 +318,12 @@ __global__ __launch_bounds__(256) void stem2d_wgrad_kernel(const S2K k) {
   constexpr int VEC = DT<T>::VEC;
   __shared__ __attribute__((aligned(16))) T dyt[64 * DTW];   // [co][pixel of the tile]
   __shared__ __attribute__((aligned(16))) T patch[PLANE];
+  __shared__ float lut[sfk_is_u8<S> ? 256 : 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
+  if constexpr (sfk_is_u8<S>) {
+    lut[tid] = k.lut[tid];
+    __syncthreads();
+  }
   const int pl = blockIdx.x;
   const int tile0 = blockIdx.y * k.tiles_per_block;
   const int tile1 = min(k.ntiles, tile0 + k.tiles_per_block);
@@ -300,9 +336,9 @@ __global__ __launch_bounds__(256) void stem2d_wgrad_kernel(const S2K k) {
   for (int tile = tile0; tile < tile1; ++tile) {
     int n, ho0, wo0;
     tile_coords(k, tile, n, ho0, wo0);
-    ps.set_tile(k, ho0, wo0);
+    ps.set_tile<S>(k, n, ho0, wo0);
     float v[NSLOT];
-    plane_fetch<S>(k, ps, plane_base(k, pl, n), v);
+    plane_fetch<S>(k, ps, plane_base(k, pl, n), v, lut);
     // dY of pixel tid of the tile (zero outside the map and for co >= cout)
     const int ho = ho0 + (tid >> 4), wo = wo0 + (tid & 15);
     const bool pok = ho < k.ho && wo < k.wo;
@@ -351,6 +387,7 @@ __global__ __launch_bounds__(256) void stem2d_wgrad_kernel(const S2K k) {
 }
 
 constexpr int LDS_FWD = 64 * WROW * 2 * 2 + CP * PLANE * 2 * 2 + 4 * 64 * 2 * 4;   // 85120 B either way (bf16 x 2 buffers, f32 x 1)
+constexpr int LDS_LUT = 256 * 4;                                                   // + the table of the uint8 source
 
 int fill(const sfk_stem2d_src* s, const sfk_fmap* y, S2K& k) {
   if (!s || !y || s->struct_size != sizeof(sfk_stem2d_src)) return SFK_ERR_INVALID;
@@ -377,6 +414,54 @@ int fill(const sfk_stem2d_src* s, const sfk_fmap* y, S2K& k) {
   k.ntiles = (int)ntiles;
   k.dtw.set(k.tiles_w); k.dth.set(k.tiles_h); k.dc.set(s->c); k.dpc.set(PC);
   k.y = y->ptr; k.yld = y->ld; k.yoff = y->c_off;
+  k.lut = nullptr; k.crop = nullptr; k.pad = 0;
+  return SFK_OK;
+}
+
+// the logical (n, t, c, h, w) clip of an sfk_u8_clip as the kernels index it: channel c at byte c0 + c
+int fill_u8(const sfk_u8_clip* x, const sfk_fmap* y, S2K& k) {
+  if (!sfk_u8_clip_ok(x)) return SFK_ERR_INVALID;
+  sfk_stem2d_src s{};
+  s.struct_size = sizeof(sfk_stem2d_src);
+  s.src_dtype = SFK_F32;          // (fill's element-type check only: S = U8Lut reads bytes through the table)
+  s.src = x->src + x->c0;
+  s.sn = x->sn; s.st = x->st; s.sc = 1; s.sh = x->sh; s.sw = x->sw;
+  s.n = x->n; s.t = x->t; s.c = x->c; s.h_in = x->h; s.w_in = x->w;
+  const int st = fill(&s, y, k);
+  if (st != SFK_OK) return st;
+  k.lut = x->lut; k.crop = x->crop; k.pad = x->pad;
+  return SFK_OK;
+}
+
+template <typename S>
+int launch_fwd(const S2K& k, const sfk_fmap* y, hipStream_t hs) {
+  const dim3 grid((unsigned)k.ntiles), block(256);
+  const int lds = LDS_FWD + (sfk_is_u8<S> ? LDS_LUT : 0);
+#define SFK_S2_FWD(T, NB)                                                                                               \
+  do {                                                                                                                  \
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem2d_fwd_kernel<T, S, NB>),                             \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);                                         \
+    hipLaunchKernelGGL((stem2d_fwd_kernel<T, S, NB>), grid, block, lds, hs, k);                                         \
+  } while (0)
+  if (y->dtype == SFK_BF16) SFK_S2_FWD(bf16_t, 2);
+  else SFK_S2_FWD(float, 1);
+#undef SFK_S2_FWD
+  SFK_CHECK_LAUNCH();
+  return SFK_OK;
+}
+
+template <typename S>
+int launch_wgrad(S2K& k, const sfk_fmap* dy, hipStream_t hs) {
+  if (hipMemsetAsync(k.dw, 0, (size_t)k.cout * k.kp * sizeof(float), hs) != hipSuccess) return SFK_ERR_LAUNCH;
+  // about 2048 blocks: planes x tile ranges
+  int split = (2048 + k.planes - 1) / k.planes;
+  if (split > k.ntiles) split = k.ntiles;
+  k.tiles_per_block = (k.ntiles + split - 1) / split;
+  split = (k.ntiles + k.tiles_per_block - 1) / k.tiles_per_block;
+  const dim3 grid((unsigned)k.planes, (unsigned)split), block(256);
+  if (dy->dtype == SFK_BF16) hipLaunchKernelGGL((stem2d_wgrad_kernel<bf16_t, S>), grid, block, 0, hs, k);
+  else hipLaunchKernelGGL((stem2d_wgrad_kernel<float, S>), grid, block, 0, hs, k);
+  SFK_CHECK_LAUNCH();
   return SFK_OK;
 }
 
@@ -399,23 +484,7 @@ extern "C" int sfk_stem2d_fwd(const sfk_stem2d_src* s, const void* w, const sfk_
   k.w = w;
   k.stats = stats;
   hipStream_t hs = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)k.ntiles), block(256);
-#define SFK_S2_FWD(T, S, NB)                                                                                            \
-  do {                                                                                                                  \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem2d_fwd_kernel<T, S, NB>),                             \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_FWD);                                     \
-    hipLaunchKernelGGL((stem2d_fwd_kernel<T, S, NB>), grid, block, LDS_FWD, hs, k);                                     \
-  } while (0)
-  if (y->dtype == SFK_BF16) {
-    if (s->src_dtype == SFK_BF16) SFK_S2_FWD(bf16_t, bf16_t, 2);
-    else SFK_S2_FWD(bf16_t, float, 2);
-  } else {
-    if (s->src_dtype == SFK_BF16) SFK_S2_FWD(float, bf16_t, 1);
-    else SFK_S2_FWD(float, float, 1);
-  }
-#undef SFK_S2_FWD
-  SFK_CHECK_LAUNCH();
-  return SFK_OK;
+  return s->src_dtype == SFK_BF16 ? launch_fwd<bf16_t>(k, y, hs) : launch_fwd<float>(k, y, hs);
 }
 
 extern "C" int sfk_stem2d_wgrad(const sfk_stem2d_src* s, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
@@ -425,20 +494,26 @@ extern "C" int sfk_stem2d_wgrad(const sfk_stem2d_src* s, const sfk_fmap* dy, flo
   if (!dw) return SFK_ERR_INVALID;
   k.dw = dw;
   hipStream_t hs = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(dw, 0, (size_t)k.cout * k.kp * sizeof(float), hs) != hipSuccess) return SFK_ERR_LAUNCH;
-  // about 2048 blocks: planes x tile ranges
-  int split = (2048 + k.planes - 1) / k.planes;
-  if (split > k.ntiles) split = k.ntiles;
-  k.tiles_per_block = (k.ntiles + split - 1) / split;
-  split = (k.ntiles + k.tiles_per_block - 1) / k.tiles_per_block;
-  const dim3 grid((unsigned)k.planes, (unsigned)split), block(256);
-  if (dy->dtype == SFK_BF16) {
-    if (s->src_dtype == SFK_BF16) hipLaunchKernelGGL((stem2d_wgrad_kernel<bf16_t, bf16_t>), grid, block, 0, hs, k);
-    else hipLaunchKernelGGL((stem2d_wgrad_kernel<bf16_t, float>), grid, block, 0, hs, k);
-  } else {
-    if (s->src_dtype == SFK_BF16) hipLaunchKernelGGL((stem2d_wgrad_kernel<float, bf16_t>), grid, block, 0, hs, k);
-    else hipLaunchKernelGGL((stem2d_wgrad_kernel<float, float>), grid, block, 0, hs, k);
-  }
-  SFK_CHECK_LAUNCH();
-  return SFK_OK;
+  return s->src_dtype == SFK_BF16 ? launch_wgrad<bf16_t>(k, dy, hs) : launch_wgrad<float>(k, dy, hs);
+}
+
+// ------------------------------------------------------------------------------------------ uint8 frames (sfk_u8stem.h)
+extern "C" int sfk_u8stem2d_fwd(const sfk_u8_clip* x, const void* w, const sfk_fmap* y, float* stats, sfk_stream_t stream) {
+  S2K k;
+  const int st = fill_u8(x, y, k);
+  if (st != SFK_OK) return st;
+  if (!w) return SFK_ERR_INVALID;
+  if ((((uintptr_t)w) & 15) != 0) return SFK_ERR_UNSUPPORTED;
+  k.w = w;
+  k.stats = stats;
+  return launch_fwd<U8Lut>(k, y, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sfk_u8stem2d_wgrad(const sfk_u8_clip* x, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
+  S2K k;
+  const int st = fill_u8(x, dy, k);
+  if (st != SFK_OK) return st;
+  if (!dw) return SFK_ERR_INVALID;
+  k.dw = dw;
+  return launch_wgrad<U8Lut>(k, dy, static_cast<hipStream_t>(stream));
 }

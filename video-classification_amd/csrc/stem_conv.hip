@@ -8,7 +8,8 @@
 //   forward : A = filter rows (co), B = patch runs (pixel on the lane)        -> D[co][pixel], epilogue = conv_igemm's
 //   wgrad   : pixels are the K dim: A = dY^T via ds_read_b64_tr_b16, B = 8 pixels (stride-2 columns) of one (kh,kw)
 // The clip is read in place through element strides (N,T,C,H,W dataset memory or N,C,T,H,W) with an optional frame
-// index (PackPathway), as f32 or bf16.
+// index (PackPathway), as f32 or bf16 -- or, for the generic kernels, as the loader's HWC uint8 frames through a 256-entry
+// f32 table with a per-clip crop shift (S = U8Lut, include/sfk_u8stem.h).
 #include "sfk_common.h"
 
 namespace {
@@ -39,6 +40,9 @@ struct StemK {
   float* dw;
   int tiles_per_block, ntiles;
   uint32_t src_bytes, y_bytes;   // extents for the buffer resources of the v2 kernels (fit 32 bits, checked at launch)
+  const float* lut;               // S = U8Lut: value of each source byte (sc = 1: channel c at byte c)
+  const int32_t* crop;            // S = U8Lut: [n][2] (top, left) or null; the frame pixel of (hi, wi) is (hi + top - pad, wi + left - pad)
+  int pad;
 };
 
 template <typename S> __device__ __forceinline__ float ldsrc(const void* p, int64_t off);
@@ -53,15 +57,32 @@ constexpr int NSLOT = (PR * PC + 255) / 256;   // 6
 struct PatchSlots {
   int64_t off[NSLOT];   // hi*sh + wi*sw of the current tile
   bool ok[NSLOT];
-  __device__ __forceinline__ void set_tile(const StemK& k, int ho0, int wo0) {
+  template <typename S>
+  __device__ __forceinline__ void set_tile(const StemK& k, int n, int ho0, int wo0) {
+    // uint8 source: the crop shifts clip n's frame under the virtual clip; slots whose shifted pixel is outside the frame
+    // are masked like the conv's own padding (any crop value is safe: their loads read the plane's first byte)
+    int64_t dy = 0, dx = 0;
+    if constexpr (sfk_is_u8<S>) {
+      if (k.crop) {
+        dy = (int64_t)k.crop[2 * n] - k.pad;
+        dx = (int64_t)k.crop[2 * n + 1] - k.pad;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < NSLOT; ++i) {
       const int e = threadIdx.x + 256 * i;
       uint32_t r, c;
       k.dpc.divmod((uint32_t)e, r, c);
       const int hi = 2 * ho0 - 3 + (int)r, wi = 2 * wo0 - 3 + (int)c;
-      ok[i] = e < PR * PC && (unsigned)hi < (unsigned)k.h_in && (unsigned)wi < (unsigned)k.w_in;
-      off[i] = (int64_t)hi * k.sh + (int64_t)wi * k.sw;
+      if constexpr (sfk_is_u8<S>) {
+        const int64_t y = hi + dy, x = wi + dx;
+        ok[i] = e < PR * PC && (unsigned)hi < (unsigned)k.h_in && (unsigned)wi < (unsigned)k.w_in &&
+                (uint64_t)y < (uint64_t)k.h_in && (uint64_t)x < (uint64_t)k.w_in;
+        off[i] = y * k.sh + x * k.sw;
+      } else {
+        ok[i] = e < PR * PC && (unsigned)hi < (unsigned)k.h_in && (unsigned)wi < (unsigned)k.w_in;
+        off[i] = (int64_t)hi * k.sh + (int64_t)wi * k.sw;
+      }
     }
   }
 };
@@ -77,15 +98,20 @@ __device__ __forceinline__ int64_t plane_base(const StemK& k, int pl, int n, int
   return (int64_t)n * k.sn + (int64_t)ci * k.sc + (int64_t)frame * k.st;
 }
 
+// lut: S = U8Lut, the block's LDS copy of the table (one gather per element from LDS instead of a second global round trip)
 template <typename S>
-__device__ __forceinline__ void plane_fetch(const StemK& k, const PatchSlots& ps, int64_t base, float (&v)[NSLOT]) {
+__device__ __forceinline__ void plane_fetch(const StemK& k, const PatchSlots& ps, int64_t base, float (&v)[NSLOT],
+                                            const float* lut = nullptr) {
   // branch-free: padding slots read element 0 of the plane and are zeroed by a select (a load under a branch makes
   // hipcc drain vmcnt behind it -- NSLOT serial round trips per plane instead of one)
   const bool bok = base >= 0;
   const int64_t b = bok ? base : 0;
 #pragma unroll
   for (int i = 0; i < NSLOT; ++i) {
-    const float x = ldsrc<S>(k.src, b + (ps.ok[i] ? ps.off[i] : 0));
+    const int64_t o = b + (ps.ok[i] ? ps.off[i] : 0);
+    float x;
+    if constexpr (sfk_is_u8<S>) x = lut[static_cast<const uint8_t*>(k.src)[o]];   // the table's f32, as the float clip holds it
+    else x = ldsrc<S>(k.src, o);
     v[i] = (bok && ps.ok[i]) ? x : 0.f;
   }
 }
@@ -96,6 +122,46 @@ __device__ __forceinline__ void plane_store(T* patch, const float (&v)[NSLOT]) {
   for (int i = 0; i < NSLOT; ++i) {
     const int e = threadIdx.x + 256 * i;
     if (e < PR * PC) patch[e] = (T)v[i];
+  }
+}
+
+// S = U8Pix<CIN>: the CIN channel bytes of a pixel are contiguous in the HWC frames.  Byte loads of one channel plane put
+// neighbouring lanes sw bytes apart (a wave-wide load spans ~11 cache lines for 21-channel pixels) and every plane touches
+// the same lines again; instead each lane loads the aligned dwords that hold its pixel's CIN bytes once per frame tap and
+// spreads them over the CIN planes (v_alignbyte per 4 channels, the table lookup in LDS).  Masked slots read the pixel at the
+// plane's origin; an aligned dword that holds a byte of the frames never leaves their allocation's pages.
+template <typename T, int CIN>
+__device__ __forceinline__ void stage_u8_pixels(const StemK& k, const PatchSlots& ps, int n, int to, T* patch,
+                                                const float* lut) {
+  constexpr int NQ = (CIN + 3) / 4, NW = NQ + 1;
+  const uint8_t* src = static_cast<const uint8_t*>(k.src);
+  for (int f = 0; f < k.kt; ++f) {
+    const int64_t base = plane_base(k, f * CIN, n, to);        // channel 0 of frame tap f; < 0: temporal padding
+    const bool bok = base >= 0;
+    uint32_t w[NSLOT][NW], sh[NSLOT];
+#pragma unroll
+    for (int i = 0; i < NSLOT; ++i) {                            // all loads first (branch-free, see plane_fetch)
+      const uintptr_t a = (uintptr_t)(src + (bok ? base : 0) + (ps.ok[i] ? ps.off[i] : 0));
+      sh[i] = (uint32_t)(a & 3);
+      const uint32_t* wp = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
+      const uint32_t jmax = (sh[i] + CIN - 1) >> 2;              // the last dword holding one of the CIN bytes
+#pragma unroll
+      for (int j = 0; j < NW; ++j) w[i][j] = wp[(uint32_t)j < jmax ? (uint32_t)j : jmax];
+    }
+#pragma unroll
+    for (int i = 0; i < NSLOT; ++i) {
+      const int e = threadIdx.x + 256 * i;
+      if (e >= PR * PC) continue;
+      const bool ok = bok && ps.ok[i];
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const uint32_t v = __builtin_amdgcn_alignbyte(w[i][q + 1], w[i][q], sh[i]);   // bytes 4q .. 4q+3 of the pixel
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          if (4 * q + b < CIN) patch[(f * CIN + 4 * q + b) * PR * PC + e] = (T)(ok ? lut[(v >> (8 * b)) & 255u] : 0.f);
+        }
+      }
+    }
   }
 }
 
@@ -156,7 +222,9 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemK k) {
   const int wrow = k.kp + 8;                                  // +16 B: spreads ds_read_b128 rows over banks
   T* patch = wl + 16 * FN * wrow;                             // [planes][PR][PC]
   float* red = reinterpret_cast<float*>(patch + k.planes * PR * PC);   // [4 waves][16*FN][2]
+  float* lut = red + 4 * 16 * FN * 2;                         // S = U8Lut: [256] (the tile loop's first barrier publishes it)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
+  if constexpr (sfk_is_u8<S>) lut[tid] = k.lut[tid];
 
   // filters -> LDS (rows >= cout are zero)
   const T* wp = static_cast<const T*>(k.w);
@@ -178,23 +246,27 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemK k) {
   for (int tile = blockIdx.x; tile < k.ntiles; tile += gridDim.x) {
     int n, to, ho0, wo0;
     tile_coords(k, tile, n, to, ho0, wo0);
-    ps.set_tile(k, ho0, wo0);
+    ps.set_tile<S>(k, n, ho0, wo0);
     __syncthreads();                                          // previous tile's patch / red reads are done
     int pl = 0;
+    if constexpr (sfk_u8_pix<S> > 0) {
+      stage_u8_pixels<T, sfk_u8_pix<S>>(k, ps, n, to, patch, lut);
+      pl = k.planes;
+    }
     for (; pl + 3 <= k.planes; pl += 3) {                     // 18 loads in flight per thread
       float v0[NSLOT], v1[NSLOT], v2[NSLOT];
       // the three frame lookups first (one wait), then all 18 element loads back to back
       const int64_t b0 = plane_base(k, pl, n, to), b1 = plane_base(k, pl + 1, n, to), b2 = plane_base(k, pl + 2, n, to);
-      plane_fetch<S>(k, ps, b0, v0);
-      plane_fetch<S>(k, ps, b1, v1);
-      plane_fetch<S>(k, ps, b2, v2);
+      plane_fetch<S>(k, ps, b0, v0, lut);
+      plane_fetch<S>(k, ps, b1, v1, lut);
+      plane_fetch<S>(k, ps, b2, v2, lut);
       plane_store<T>(patch + pl * PR * PC, v0);
       plane_store<T>(patch + (pl + 1) * PR * PC, v1);
       plane_store<T>(patch + (pl + 2) * PR * PC, v2);
     }
     for (; pl < k.planes; ++pl) {
       float v0[NSLOT];
-      plane_fetch<S>(k, ps, plane_base(k, pl, n, to), v0);
+      plane_fetch<S>(k, ps, plane_base(k, pl, n, to), v0, lut);
       plane_store<T>(patch + pl * PR * PC, v0);
     }
     __syncthreads();
@@ -295,11 +367,16 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemK k) {
   constexpr int NDL = DSEG;                    // 256 rows * DSEG segments / 256 threads
   __shared__ __attribute__((aligned(16))) T dyt[256 * DROW];
   __shared__ __attribute__((aligned(16))) T patch[PR * PC];
+  __shared__ float lut[sfk_is_u8<S> ? 256 : 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, g = lane >> 4;
   const int pl = blockIdx.x;
   const int tile0 = blockIdx.y * k.tiles_per_block;
   const int tile1 = min(tile0 + k.tiles_per_block, k.ntiles);
   if (tile0 >= tile1) return;
+  if constexpr (sfk_is_u8<S>) {
+    lut[tid] = k.lut[tid];
+    __syncthreads();
+  }
   const T* dyp = static_cast<const T*>(k.y);
 
   f32x4 acc[FN];
@@ -315,8 +392,8 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemK k) {
   auto fetch = [&](int tile) {
     int n, to, ho0, wo0;
     tile_coords(k, tile, n, to, ho0, wo0);
-    ps.set_tile(k, ho0, wo0);
-    plane_fetch<S>(k, ps, plane_base(k, pl, n, to), pv);
+    ps.set_tile<S>(k, n, ho0, wo0);
+    plane_fetch<S>(k, ps, plane_base(k, pl, n, to), pv, lut);
 #pragma unroll
     for (int i = 0; i < NDL; ++i) {
       const int e = tid + 256 * i;
@@ -1223,6 +1300,80 @@ int fill(const sfk_stem_src* s, int cout, int t_out, int ho, int wo, StemK& k) {
   k.cout = cout; k.ho = ho; k.wo = wo; k.t_out = t_out;
   k.tiles_h = (ho + TS - 1) / TS; k.tiles_w = (wo + TS - 1) / TS;
   k.dtw.set(k.tiles_w); k.dth.set(k.tiles_h); k.dt.set(t_out); k.d7.set(KH); k.dcin.set(s->cin); k.dpc.set(PC);
+  k.lut = nullptr; k.crop = nullptr; k.pad = 0;
+  return SFK_OK;
+}
+
+// the logical (n, ci, t, h, w) clip of an sfk_u8_clip as the generic kernels index it: channel ci at byte c0 + ci
+int fill_u8(const sfk_u8_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt, int n, int cout, int t_out, int ho,
+            int wo, StemK& k) {
+  if (!sfk_u8_clip_ok(x) || x->n != n) return SFK_ERR_INVALID;   // (the tiles index clips and crop rows by the map's n)
+  sfk_stem_src s{};
+  s.src = x->src + x->c0;
+  s.src_dtype = SFK_F32;          // (fill's element-type check only: S = U8Lut reads bytes through the table)
+  s.sn = x->sn; s.sc = 1; s.st = x->st; s.sh = x->sh; s.sw = x->sw;
+  s.cin = x->c; s.t_in = x->t; s.h_in = x->h; s.w_in = x->w;
+  s.t_index = t_index; s.t_len = t_len; s.kt = kt;
+  const int st = fill(&s, cout, t_out, ho, wo, k);
+  if (st != SFK_OK) return st;
+  k.lut = x->lut; k.crop = x->crop; k.pad = x->pad;
+  return SFK_OK;
+}
+
+// the generic forward (any cin / kt / source type): one 16x16 tile per block iteration, filters and patches in LDS
+template <typename S>
+int stem_fwd_generic(StemK& k, const sfk_fmap* y, hipStream_t hs) {
+  const int fn = (y->c + 15) / 16;
+  const size_t esz = y->dtype == SFK_BF16 ? 2 : 4;
+  const size_t lds = esz * ((size_t)16 * fn * (k.kp + 8) + (size_t)k.planes * PR * PC) + 4 * 16 * fn * 2 * sizeof(float) +
+                     (sfk_is_u8<S> ? 256 * sizeof(float) : 0);
+  if (lds > 160 * 1024) return SFK_ERR_UNSUPPORTED;
+  k.ntiles = y->n * y->t * k.tiles_h * k.tiles_w;
+  const int resident = 256 * (int)((160 * 1024) / lds < 1 ? 1 : ((160 * 1024) / lds > 4 ? 4 : (160 * 1024) / lds));
+  const dim3 grid((unsigned)(k.ntiles < 4 * resident ? k.ntiles : 4 * resident)), blk(256);
+#define SFK_STEM_FWD(T, FN)                                                                                 \
+  do {                                                                                                      \
+    if (lds > 64 * 1024)                                                                                    \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_kernel<T, S, FN>),                      \
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
+    hipLaunchKernelGGL((stem_fwd_kernel<T, S, FN>), grid, blk, lds, hs, k);                                 \
+  } while (0)
+#define SFK_STEM_FWD_FN(T)                                          \
+  do {                                                              \
+    if (fn == 1) SFK_STEM_FWD(T, 1);                                \
+    else if (fn == 2) SFK_STEM_FWD(T, 2);                           \
+    else SFK_STEM_FWD(T, 4);                                        \
+  } while (0)
+  if (fn == 3) return SFK_ERR_UNSUPPORTED;
+  if (y->dtype == SFK_BF16) SFK_STEM_FWD_FN(bf16_t);
+  else SFK_STEM_FWD_FN(float);
+#undef SFK_STEM_FWD_FN
+#undef SFK_STEM_FWD
+  SFK_CHECK_LAUNCH();
+  return SFK_OK;
+}
+
+// the generic filter gradient: grid = (plane, tile split), split sums added to dw with fp32 atomics
+template <typename S>
+int stem_wgrad_generic(StemK& k, const sfk_fmap* dy, hipStream_t hs) {
+  int splits = (2048 + k.planes - 1) / k.planes;
+  if (splits > k.ntiles) splits = k.ntiles;
+  if (splits > 65535) splits = 65535;
+  k.tiles_per_block = (k.ntiles + splits - 1) / splits;
+  splits = (k.ntiles + k.tiles_per_block - 1) / k.tiles_per_block;
+  const int fn = (dy->c + 15) / 16;
+  if (fn == 3) return SFK_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)k.planes, (unsigned)splits), blk(256);
+#define SFK_STEM_WG(T)                                                                      \
+  do {                                                                                      \
+    if (fn == 1) hipLaunchKernelGGL((stem_wgrad_kernel<T, S, 1>), grid, blk, 0, hs, k);     \
+    else if (fn == 2) hipLaunchKernelGGL((stem_wgrad_kernel<T, S, 2>), grid, blk, 0, hs, k); \
+    else hipLaunchKernelGGL((stem_wgrad_kernel<T, S, 4>), grid, blk, 0, hs, k);             \
+  } while (0)
+  if (dy->dtype == SFK_BF16) SFK_STEM_WG(bf16_t);
+  else SFK_STEM_WG(float);
+#undef SFK_STEM_WG
+  SFK_CHECK_LAUNCH();
   return SFK_OK;
 }
 
@@ -1297,35 +1448,8 @@ extern "C" int sfk_stem_conv_fwd(const sfk_stem_src* s, const void* w, const sfk
     SFK_CHECK_LAUNCH();
     return SFK_OK;
   }
-  const int fn = (y->c + 15) / 16;
-  const size_t esz = y->dtype == SFK_BF16 ? 2 : 4;
-  const size_t lds = esz * ((size_t)16 * fn * (k.kp + 8) + (size_t)k.planes * PR * PC) + 4 * 16 * fn * 2 * sizeof(float);
-  if (lds > 160 * 1024) return SFK_ERR_UNSUPPORTED;
-  k.ntiles = y->n * y->t * k.tiles_h * k.tiles_w;
-  const int resident = 256 * (int)((160 * 1024) / lds < 1 ? 1 : ((160 * 1024) / lds > 4 ? 4 : (160 * 1024) / lds));
-  const dim3 grid((unsigned)(k.ntiles < 4 * resident ? k.ntiles : 4 * resident)), blk(256);
   hipStream_t hs = static_cast<hipStream_t>(stream);
-#define SFK_STEM_FWD(T, S, FN)                                                                              \
-  do {                                                                                                      \
-    if (lds > 64 * 1024)                                                                                    \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_kernel<T, S, FN>),                      \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
-    hipLaunchKernelGGL((stem_fwd_kernel<T, S, FN>), grid, blk, lds, hs, k);                                 \
-  } while (0)
-#define SFK_STEM_FWD_FN(T, S)                                       \
-  do {                                                              \
-    if (fn == 1) SFK_STEM_FWD(T, S, 1);                             \
-    else if (fn == 2) SFK_STEM_FWD(T, S, 2);                        \
-    else SFK_STEM_FWD(T, S, 4);                                     \
-  } while (0)
-  if (fn == 3) return SFK_ERR_UNSUPPORTED;
-  if (y->dtype == SFK_BF16) {
-    if (s->src_dtype == SFK_BF16) SFK_STEM_FWD_FN(bf16_t, bf16_t); else SFK_STEM_FWD_FN(bf16_t, float);
-  } else {
-    if (s->src_dtype == SFK_BF16) SFK_STEM_FWD_FN(float, bf16_t); else SFK_STEM_FWD_FN(float, float);
-  }
-  SFK_CHECK_LAUNCH();
-  return SFK_OK;
+  return s->src_dtype == SFK_BF16 ? stem_fwd_generic<bf16_t>(k, y, hs) : stem_fwd_generic<float>(k, y, hs);
 }
 
 extern "C" int sfk_stem_conv_wgrad(const sfk_stem_src* s, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
@@ -1359,25 +1483,35 @@ extern "C" int sfk_stem_conv_wgrad(const sfk_stem_src* s, const sfk_fmap* dy, fl
     SFK_CHECK_LAUNCH();
     return SFK_OK;
   }
-  int splits = (2048 + k.planes - 1) / k.planes;
-  if (splits > k.ntiles) splits = k.ntiles;
-  if (splits > 65535) splits = 65535;
-  k.tiles_per_block = (k.ntiles + splits - 1) / splits;
-  splits = (k.ntiles + k.tiles_per_block - 1) / k.tiles_per_block;
-  const int fn = (dy->c + 15) / 16;
-  if (fn == 3) return SFK_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)k.planes, (unsigned)splits), blk(256);
-#define SFK_STEM_WG(T, S)                                                                   \
-  do {                                                                                      \
-    if (fn == 1) hipLaunchKernelGGL((stem_wgrad_kernel<T, S, 1>), grid, blk, 0, hs, k);     \
-    else if (fn == 2) hipLaunchKernelGGL((stem_wgrad_kernel<T, S, 2>), grid, blk, 0, hs, k); \
-    else hipLaunchKernelGGL((stem_wgrad_kernel<T, S, 4>), grid, blk, 0, hs, k);             \
-  } while (0)
-  if (dy->dtype == SFK_BF16) {
-    if (s->src_dtype == SFK_BF16) SFK_STEM_WG(bf16_t, bf16_t); else SFK_STEM_WG(bf16_t, float);
-  } else {
-    if (s->src_dtype == SFK_BF16) SFK_STEM_WG(float, bf16_t); else SFK_STEM_WG(float, float);
-  }
-  SFK_CHECK_LAUNCH();
-  return SFK_OK;
+  return s->src_dtype == SFK_BF16 ? stem_wgrad_generic<bf16_t>(k, dy, hs) : stem_wgrad_generic<float>(k, dy, hs);
+}
+
+// ------------------------------------------------------------------------------------------ uint8 frames (sfk_u8stem.h)
+extern "C" int sfk_u8stem_abi_version(void) { return SFK_U8STEM_ABI_VERSION; }
+
+extern "C" int sfk_u8stem_conv_fwd(const sfk_u8_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt, const void* w,
+                                   const sfk_fmap* y, float* stats, sfk_stream_t stream) {
+  if (!w || !sfk_fmap_ok(y)) return SFK_ERR_INVALID;
+  StemK k;
+  const int st = fill_u8(x, t_index, t_len, kt, y->n, y->c, y->t, y->h, y->w, k);
+  if (st != SFK_OK) return st;
+  if ((y->ld % 4) || (y->c_off % 4) || (((uintptr_t)y->ptr) & 15) || (((uintptr_t)w) & 15)) return SFK_ERR_UNSUPPORTED;
+  k.w = w; k.y = y->ptr; k.yld = y->ld; k.yoff = y->c_off; k.stats = stats; k.dw = nullptr;
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  // the reference geometries' channel counts stage whole pixels (stage_u8_pixels); any other count a plane at a time
+  if (x->c == 5) return stem_fwd_generic<U8Pix<5>>(k, y, hs);
+  if (x->c == 15) return stem_fwd_generic<U8Pix<15>>(k, y, hs);
+  return stem_fwd_generic<U8Lut>(k, y, hs);
+}
+
+extern "C" int sfk_u8stem_conv_wgrad(const sfk_u8_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt,
+                                     const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
+  if (!dw || !sfk_fmap_ok(dy)) return SFK_ERR_INVALID;
+  StemK k;
+  const int st = fill_u8(x, t_index, t_len, kt, dy->n, dy->c, dy->t, dy->h, dy->w, k);
+  if (st != SFK_OK) return st;
+  if (!sfk_fmap_vec_ok(dy)) return SFK_ERR_UNSUPPORTED;
+  k.w = nullptr; k.y = dy->ptr; k.yld = dy->ld; k.yoff = dy->c_off; k.stats = nullptr; k.dw = dw;
+  k.ntiles = dy->n * dy->t * k.tiles_h * k.tiles_w;
+  return stem_wgrad_generic<U8Lut>(k, dy, static_cast<hipStream_t>(stream));
 }

@@ -16,6 +16,7 @@ numerically this step is "parity unpinned" against torchvision itself (tests/tes
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -69,3 +70,68 @@ class DevicePreprocess:
         stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
         self.be.u8_normalize_crop(x, self.lut, crop, int(padding or 0), out)(stream)
         return out
+
+
+@dataclass(eq=False)
+class U8Clip:
+    """One pathway's view of a device uint8 batch, read by the stem kernels themselves (include/sfk_u8stem.h, MODEL.U8_STEM):
+    the normalised, cropped float clip DevicePreprocess would write is never materialised.  Logical element (n, ci, t, h, w)
+    is ``lut[frames[n, t, h + top - pad, w + left - pad, c0 + ci]]`` (zero outside the frame; no shift without a crop), the
+    clip DevicePreprocess produces, sliced to channels c0 .. c0 + c - 1 and permuted to (N, c, T, H, W).
+
+    frames: (N, T, H, W, P) uint8 with channel stride 1 and any pixel pitch P >= c0 + c (a loader may send only the
+    channels the stems read); crop: (N, 2) int32 (top, left) on the same device, or None (test / valid clips).  The crop
+    CONTENTS are read when the stems run, so a captured graph follows new offsets written into the same tensor."""
+    frames: torch.Tensor
+    c0: int
+    c: int
+    crop: Optional[torch.Tensor]
+    pad: int
+    lut: torch.Tensor
+
+    def __post_init__(self):
+        f = self.frames
+        assert f.dtype == torch.uint8 and f.dim() == 5 and f.stride(4) == 1, "frames: (N, T, H, W, P) uint8, channels contiguous"
+        assert 0 <= self.c0 and 0 < self.c and self.c0 + self.c <= f.shape[4] <= f.stride(3), (self.c0, self.c, f.shape)
+        assert self.lut.dtype == torch.float32 and self.lut.numel() == 256 and self.lut.device == f.device
+        if self.crop is not None:
+            assert self.crop.dtype == torch.int32 and tuple(self.crop.shape) == (f.shape[0], 2) and self.crop.is_contiguous()
+            assert self.crop.device == f.device
+
+    # the logical (N, c, T, H, W) geometry, as the engine's plan code reads a float clip's
+    @property
+    def shape(self) -> torch.Size:
+        n, t, h, w, _ = self.frames.shape
+        return torch.Size((n, self.c, t, h, w))
+
+    @property
+    def device(self) -> torch.device:
+        return self.frames.device
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return torch.uint8
+
+    def dim(self) -> int:
+        return 5
+
+    def numel(self) -> int:
+        return self.shape.numel()
+
+    def element_size(self) -> int:
+        return 1
+
+    def geometry_key(self) -> tuple:
+        """what a plan built for this clip depends on (never equal to a float tensor's key)"""
+        f = self.frames
+        return ("u8", tuple(f.shape), tuple(f.stride()), self.c0, self.c, self.crop is not None, self.pad)
+
+    def bound_ptrs(self) -> tuple:
+        """the device addresses the stem ops hold"""
+        return (self.frames.data_ptr(), None if self.crop is None else self.crop.data_ptr(), self.lut.data_ptr())
+
+
+def u8_pathways(frames: torch.Tensor, crop: Optional[torch.Tensor], lut: torch.Tensor, channels) -> list:
+    """U8Clips over the same device frames and crop, one per (c0, c) range; pad = S // 10 (RandomCrop's padding)."""
+    pad = frames.shape[2] // 10
+    return [U8Clip(frames, c0, c, crop, pad, lut) for c0, c in channels]

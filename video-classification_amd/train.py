@@ -29,6 +29,7 @@ from torch.utils.data.dataloader import default_collate
 from . import dist as sdist
 from .config import crop_resize_dict
 from .engine import Engine
+from .input_pipeline import U8Clip
 from .slowfast import init_my_slowfast
 
 
@@ -167,6 +168,7 @@ class ModelManager:
     def __init__(self, cfg, device="cuda", backend=None):
         self.cfg, self.device, self.backend = cfg, device, backend
         self._pre = None
+        self._lut = None
         name = cfg.MODEL.NAME
         self.arch = str(cfg.MODEL.get("ARCH", "ref")).lower()
         if self.arch not in ("ref", "canonical8x8"):
@@ -195,6 +197,37 @@ class ModelManager:
             t = t.pin_memory()
         return t.to(self.device, non_blocking=True)
 
+    # ---- the uint8 transport: a batch carrying <R3D_INPUT>_u8 (N,T,S,S,P uint8 HWC frames, P >= the channels read, optional
+    #      `crop` (N,2)) instead of the float32 tensor.  MODEL.U8_STEM False: DevicePreprocess writes the normalised, cropped
+    #      float clip on the device and the stems read its views; True: the stems read the frames themselves (U8Clip).
+    def _u8_key(self, batch) -> Optional[str]:
+        key = self.cfg.MODEL.R3D_INPUT + "_u8"
+        return key if key in batch else None
+
+    def _u8_stem(self) -> bool:
+        return bool(self.cfg.MODEL.get("U8_STEM", False))
+
+    def _u8_float(self, batch) -> torch.Tensor:
+        """DevicePreprocess: (N,T,S,S,P) uint8 -> (N,T,P,S,S) float32 on the device"""
+        if self._pre is None:
+            from .input_pipeline import DevicePreprocess
+            self._pre = DevicePreprocess(self.device, self.backend)
+        return self._pre(batch[self._u8_key(batch)], batch.get("crop"))
+
+    def _u8_clips(self, batch, channels) -> list:
+        """U8Clips over the pinned-H2D frames and crop, one per (c0, c) channel range"""
+        from .input_pipeline import normalize_lut, u8_pathways
+        if self._lut is None:
+            self._lut = normalize_lut().to(self.device)
+        frames = self._h2d(batch[self._u8_key(batch)])
+        assert frames.dtype == torch.uint8 and frames.dim() == 5
+        if frames.stride(4) != 1:
+            frames = frames.contiguous()
+        crop = batch.get("crop")
+        if crop is not None:
+            crop = self._h2d(crop.to(torch.int32)).contiguous()
+        return u8_pathways(frames, crop, self._lut, channels)
+
     # ---- res2d (train.py:64-76): host plumbing (res2d.py), or the engine with MODEL.RES2D_BACKEND = 'engine'
     def _res2d_backend(self) -> str:
         b = str(self.cfg.MODEL.get("RES2D_BACKEND", "torch")).lower()
@@ -217,6 +250,10 @@ class ModelManager:
         the pinned (N,T,21,S,S) batch on the device, handed over as the strided (N,T,5,S,S) view -- no reshape copy; the
         stem reads frame t, channel c as input channel t*5 + c (Engine.input_view)."""
         if self._res2d_backend() == "engine":
+            if self._u8_key(batch):                      # the uint8 transport
+                if self._u8_stem():
+                    return self._u8_clips(batch, [(0, 5)])[0], self._h2d(batch['label'])
+                return self._u8_float(batch)[:, :, :5], self._h2d(batch['label'])
             return self._h2d(batch[self.cfg.MODEL.R3D_INPUT])[:, :, :5], self._h2d(batch['label'])
         dev = "cpu" if torch.device(self.device).type != "cuda" else self.device
         x = batch[self.cfg.MODEL.R3D_INPUT][:, :, :5].to(dev)
@@ -276,8 +313,13 @@ class ModelManager:
 
     def _prepare_res3d_data(self, batch):
         """(N,T,21,S,S) -> BGR+UV (N,5,T,S,S) strided view (train.py:85-89; 5 channels as train.py:72 / the 5-channel
-        stem of :81)."""
-        x = self._h2d(batch[self.cfg.MODEL.R3D_INPUT])
+        stem of :81).  A uint8 batch: DevicePreprocess's float clip, or (MODEL.U8_STEM) a U8Clip over channels 0:5."""
+        if self._u8_key(batch):
+            if self._u8_stem():
+                return self._u8_clips(batch, [(0, 5)])[0], self._h2d(batch['label'])
+            x = self._u8_float(batch)
+        else:
+            x = self._h2d(batch[self.cfg.MODEL.R3D_INPUT])
         x = torch.permute(x, [0, 2, 1, 3, 4])
         return x[:, 0:5], self._h2d(batch['label'])
 
@@ -285,13 +327,13 @@ class ModelManager:
         """(N,T,21,S,S) -> [BGR+UV (N,5,T,S,S), flow (N,15,T,S,S)] strided views of the SAME memory; the depth channel
         (20) is dropped (train.py:125-145).  The stem kernels read these views in place.
         A batch that carries ``<R3D_INPUT>_u8`` (N,T,S,S,21 uint8 frames, optional ``crop`` (N,2)) instead of the float32
-        tensor takes the uint8 transport: normalise + RandomCrop run on the device (input_pipeline.py)."""
+        tensor takes the uint8 transport: normalise + RandomCrop run on the device (input_pipeline.py), or, with
+        MODEL.U8_STEM, inside the two stems, which read the frames as U8Clips over channels 0:5 and 5:20."""
         key = self.cfg.MODEL.R3D_INPUT
-        if key + "_u8" in batch:
-            if self._pre is None:
-                from .input_pipeline import DevicePreprocess
-                self._pre = DevicePreprocess(self.device, self.backend)
-            x = self._pre(batch[key + "_u8"], batch.get("crop"))
+        if self._u8_key(batch):
+            if self._u8_stem():
+                return self._u8_clips(batch, [(0, 5), (5, 15)]), self._h2d(batch['label'])
+            x = self._u8_float(batch)
         else:
             x = self._h2d(batch[key])
         x = torch.permute(x, [0, 2, 1, 3, 4])
@@ -432,7 +474,7 @@ class Trainer:
             self.train_sampler.set_epoch(self.epoch)     # a new permutation of the epoch, the same on every rank
         for batch in self.train_loader:
             x, y_true = self.mm.prepare_data(batch)
-            if torch.is_tensor(x):                       # res3d / res2d: one input tensor
+            if isinstance(x, (torch.Tensor, U8Clip)):    # res3d / res2d: one input tensor (or uint8 clip)
                 self.step(x, None, y_true)
             else:
                 self.step(x[0], x[1], y_true, slow_t_index=self.model.slow_t_index)
