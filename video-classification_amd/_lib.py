@@ -205,6 +205,17 @@ class _U8Clip(C.Structure):
                 ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("lut", C.c_void_p), ("crop", C.c_void_p)]
 
 
+class _RoiDesc(C.Structure):
+    """include/sfk_v2.h sfk_roi_desc: byte (n, t, y, x, c) at src[n*sn + t*st + y*sh + x*sw + c*sc]; the resized crop of
+    box[n] lands at dst[n*dn + t*dt + (c_off + c)*dc + y*dh + x]"""
+    _fields_ = [("struct_size", C.c_uint32), ("antialias", C.c_int32), ("src", C.c_void_p), ("sn", C.c_int64),
+                ("st", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64), ("sc", C.c_int64), ("n", C.c_int32),
+                ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("out_h", C.c_int32),
+                ("out_w", C.c_int32), ("lut", C.c_void_p), ("box", C.c_void_p), ("crop", C.c_void_p), ("pad", C.c_int32),
+                ("dst_dtype", C.c_int32), ("dst", C.c_void_p), ("dn", C.c_int64), ("dt", C.c_int64), ("dc", C.c_int64),
+                ("dh", C.c_int64), ("c_off", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class _Tuning(C.Structure):
     """sfk_tuning: the write-once kernel-selection table of sfk_init (defaults = the measured best)."""
     _fields_ = [("struct_size", C.c_uint32), ("igemm_short_k", C.c_int32), ("igemm_small_k", C.c_int32), ("igemm_wide_store", C.c_int32),
@@ -304,6 +315,15 @@ SIGNATURES_U8STEM = {
     "sfk_u8stem2d_fwd": [C.POINTER(_U8Clip), _PV, _P_FMAP, _PF, _PV],
     "sfk_u8stem2d_wgrad": [C.POINTER(_U8Clip), _P_FMAP, _PF, _PV],
 }
+# include/sfk_v2.h: the v2 part-box trainer's ROI crop-resize and SGD, same library, its own header and version
+V2_ABI_VERSION = 1         # include/sfk_v2.h SFK_V2_ABI_VERSION
+ROI_MAX_RATIO = 8          # include/sfk_v2.h SFK_ROI_MAX_RATIO
+ROI_MAX_C = 16             # include/sfk_v2.h SFK_ROI_MAX_C
+SIGNATURES_V2 = {
+    "sfk_v2_abi_version": [],
+    "sfk_roi_resize": [C.POINTER(_RoiDesc), _PV],
+    "sfk_sgd": [_PF, _PF, _PF, _I64, C.c_float, C.c_float, C.c_float, _I32, C.c_float, _PV, _PV, _I32, _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64}
 
 
@@ -332,6 +352,12 @@ def new_u8_clip() -> "_U8Clip":
     return d
 
 
+def new_roi_desc() -> "_RoiDesc":
+    d = _RoiDesc()
+    d.struct_size = C.sizeof(_RoiDesc)
+    return d
+
+
 def new_tuning() -> "_Tuning":
     t = _Tuning()
     t.struct_size = C.sizeof(_Tuning)
@@ -349,7 +375,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"{path} not found: build it with `python video-classification_amd/build.py` "
                        "(there is no CPU or PyTorch fallback for the SlowFast path)")
     lib = C.CDLL(path)
-    for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM):
+    for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -360,6 +386,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk stem2d ABI version mismatch: library {lib.sfk_stem2d_abi_version()}, binding {STEM2D_ABI_VERSION}")
     if lib.sfk_u8stem_abi_version() != U8STEM_ABI_VERSION:
         raise SfkError(f"libsfk u8stem ABI version mismatch: library {lib.sfk_u8stem_abi_version()}, binding {U8STEM_ABI_VERSION}")
+    if lib.sfk_v2_abi_version() != V2_ABI_VERSION:
+        raise SfkError(f"libsfk v2 ABI version mismatch: library {lib.sfk_v2_abi_version()}, binding {V2_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -835,6 +863,29 @@ class HipBackend:
         sd = _DT[shadow.dtype] if shadow is not None else SFK_F32
         return self._plain("sfk_adam", _ptr(p), _ptr(g), _ptr(m), _ptr(v), count, lr, b1, b2, eps, gscale, _ptr(step),
                            _ptr(shadow), sd, keep=(p, g, m, v, step, shadow))
+
+    def sgd(self, p, g, buf, count, lr, momentum, dampening, nesterov, gscale, step, shadow=None):
+        """sfk_sgd (include/sfk_v2.h): torch.optim.SGD without weight decay; step[0] is incremented by the launch"""
+        sd = _DT[shadow.dtype] if shadow is not None else SFK_F32
+        return self._plain("sfk_sgd", _ptr(p), _ptr(g), _ptr(buf), count, lr, momentum, dampening, 1 if nesterov else 0,
+                           gscale, _ptr(step), _ptr(shadow), sd, keep=(p, g, buf, step, shadow))
+
+    def roi_resize(self, src, lut, box, out, antialias: bool, crop=None, pad: int = 0, c_off: int = 0):
+        """sfk_roi_resize (include/sfk_v2.h): src (N,T,H,W,C) uint8, any byte strides (HWC or a permuted planar view);
+        box (N,4) int32 (x1, y1, x2, y2); out (N,T,C',S,S') f32|bf16 with unit W stride, channels c_off .. c_off+C-1 written;
+        crop (N,2) int32 (top, left) or None."""
+        n, t, h, w, c = src.shape
+        assert src.dtype == torch.uint8 and box.dtype == torch.int32 and box.is_contiguous() and tuple(box.shape) == (n, 4)
+        assert out.dim() == 5 and out.stride(4) == 1 and out.shape[0] == n and out.shape[1] == t and c_off + c <= out.shape[2]
+        assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (n, 2))
+        d = new_roi_desc()
+        d.antialias, d.src, d.lut, d.box, d.crop, d.pad = 1 if antialias else 0, src.data_ptr(), lut.data_ptr(), box.data_ptr(), _ptr(crop), pad
+        d.sn, d.st, d.sh, d.sw, d.sc = src.stride()
+        d.n, d.t, d.h, d.w, d.c = n, t, h, w, c
+        d.out_h, d.out_w = out.shape[3], out.shape[4]
+        d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
+        d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
+        return self._plain("sfk_roi_resize", C.byref(d), keep=(d, src, lut, box, out, crop))
 
     def filter_transpose(self, src, dst, cout, wtaps, cin):
         return self._plain("sfk_filter_transpose", _ptr(src), _DT[src.dtype], _ptr(dst), _DT[dst.dtype], cout, wtaps,

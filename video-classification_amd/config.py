@@ -98,6 +98,8 @@ _C.MODEL.DTYPE = 'fp32'        # 'fp32' (reference precision) | 'bf16' (benchmar
 _C.MODEL.ARCH = 'ref'          # 'ref' = init_my_slowfast geometry | 'canonical8x8' = SlowFast-R50 8x8 (BGR frames, PackPathway alpha 4)
 _C.MODEL.DEPTH = 50            # the reference hard-codes 50 (model/my_slowfast.py:98); 18 / 26 = the small test networks
 _C.MODEL.RES2D_BACKEND = 'torch'  # MODEL.NAME res2d: 'torch' (res2d.py, PyTorch kernels, fp32) | 'engine' (libsfk, MODEL.DTYPE)
+_C.MODEL.PARTS = 'lHandArmTorso'  # gesture_v2 (new_feature_test.py:812): the PartCompose composition whose box each clip crops
+_C.MODEL.RESIZE_ANTIALIAS = True  # gesture_v2: antialiased resize of the crop (torchvision >= 0.17 tensor Resize) or not (older)
 _C.MODEL.U8_STEM = False       # uint8 batches (<R3D_INPUT>_u8): the engine's stems read the frames (True) or DevicePreprocess writes the float clip first (False)
 _C.DIST = CfgNode()
 _C.DIST.BUCKET_MB = 32         # gradient all-reduce bucket size

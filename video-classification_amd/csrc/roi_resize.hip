@@ -1,0 +1,275 @@
+// sfk_roi_resize (include/sfk_v2.h): part-box crop + uint8 table lookup + separable bilinear resize (F.interpolate,
+// align_corners=False, with or without antialiasing) + optional RandomCrop shift, one launch per batch.
+//
+// One workgroup owns a tile of B destination rows x TW destination columns of one (clip, frame), all channels:
+//   1. it reads the clip's box (and crop), builds the tap index / weight tables of its TW columns and B rows in LDS with
+//      torch's CPU arithmetic (upsample_bilinear2d's fused source index; _upsample_bilinear2d_aa's mixed float/double
+//      weights), and the byte table;
+//   2. it stages the source bytes its taps touch -- R rows x SP columns x c channels -- in LDS, as aligned dwords when the
+//      channels of a pixel are adjacent (HWC), as bytes otherwise (planar);
+//   3. horizontal pass: R x c x TW fp32 band in LDS (taps in torch's order, no contraction);
+//   4. vertical pass: one coalesced row store per (channel, row), zeros where the crop shift leaves the resized image.
+// The host sizes B, TW, R and SP from the worst-case ratio frame / output, so every box fits its LDS; the kernel still
+// clamps every LDS index to what it staged, so a box the host did not foresee can neither write out of bounds nor read
+// unstaged memory.
+#include <math.h>
+
+#include "sfk_common.h"
+#include "sfk_v2.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxTaps = 2 * SFK_ROI_MAX_RATIO + 1;
+constexpr int kLdsBudget = 64 * 1024;
+
+struct RoiGeo {
+  int B, TW, R, SP, KH, KW;
+  int row_tiles, col_tiles;
+  int off_lut, off_xw, off_xi, off_yw, off_yi, off_sb, off_tmp, lds;
+};
+
+inline int align16(int v) { return (v + 15) & ~15; }
+
+RoiGeo roi_layout(int B, int TW, int c, int KH, int KW, double sh, double sw, int out_h, int out_w) {
+  RoiGeo g;
+  g.B = B;
+  g.TW = TW;
+  g.KH = KH;
+  g.KW = KW;
+  g.R = (int)floor((B - 1) * sh) + KH + 2;
+  g.SP = (int)floor((TW - 1) * sw) + KW + 2;
+  g.row_tiles = (out_h + B - 1) / B;
+  g.col_tiles = (out_w + TW - 1) / TW;
+  int o = 0;
+  g.off_lut = o; o += 256 * 4;
+  g.off_xw = o;  o += align16(TW * KW * 4);
+  g.off_xi = o;  o += align16(TW * KW * 4);
+  g.off_yw = o;  o += align16(B * KH * 4);
+  g.off_yi = o;  o += align16(B * KH * 4);
+  g.off_tmp = o; o += align16(g.R * c * TW * 4);
+  g.off_sb = o;  o += align16(g.R * g.SP * c);
+  g.lds = o;
+  return g;
+}
+
+// Taps of resized index i (0 <= i < out) over a source extent of `in` pixels: up to K (index, weight) pairs, unused ones
+// (index = first index, weight 0).  Exactly torch's CPU arithmetic (aten/src/ATen/native/cpu/UpSampleKernel.cpp).
+__device__ void roi_taps(int i, int in, int out, int aa, int K, int* idx, float* wt) {
+  const float scale = (float)in / (float)out;
+  if (!aa) {
+    int i0, i1;
+    float l0, l1;
+    if (in == out) {
+      i0 = i1 = i;
+      l0 = 1.f;
+      l1 = 0.f;
+    } else {
+      float src = __fmaf_rn(scale, (float)i + 0.5f, -0.5f);
+      if (src < 0.f) src = 0.f;
+      i0 = min((int)floorf(src), in - 1);
+      l1 = fminf(fmaxf(__fsub_rn(src, (float)i0), 0.f), 1.f);
+      i1 = i0 + (i0 < in - 1 ? 1 : 0);
+      l0 = __fsub_rn(1.f, l1);
+    }
+    idx[0] = i0;
+    wt[0] = l0;
+    idx[1] = i1;
+    wt[1] = l1;
+    for (int k = 2; k < K; ++k) { idx[k] = i0; wt[k] = 0.f; }
+    return;
+  }
+  if (in == out) {                 // torch skips the axis: identity
+    idx[0] = i;
+    wt[0] = 1.f;
+    for (int k = 1; k < K; ++k) { idx[k] = i; wt[k] = 0.f; }
+    return;
+  }
+  const float support = scale >= 1.f ? scale : 1.f;
+  const int max_k = min((int)ceilf(support) * 2 + 1, K);
+  const float invscale = scale >= 1.f ? (float)(1.0 / (double)scale) : 1.f;
+  const float center = (float)((double)scale * ((double)i + 0.5));
+  const int xmin = max((int)((double)__fsub_rn(center, support) + 0.5), 0);
+  int xsize = min((int)((double)__fadd_rn(center, support) + 0.5), in) - xmin;
+  xsize = min(max(xsize, 0), max_k);
+  float total = 0.f;
+  for (int k = 0; k < K; ++k) {
+    float w = 0.f;
+    if (k < xsize) {
+      const float x = fabsf((float)(((double)__fsub_rn((float)(k + xmin), center) + 0.5) * (double)invscale));
+      w = x < 1.f ? (float)(1.0 - (double)x) : 0.f;
+      total = __fadd_rn(total, w);
+    }
+    wt[k] = w;
+    idx[k] = k < xsize ? xmin + k : xmin;
+  }
+  if (total != 0.f)
+    for (int k = 0; k < xsize; ++k) wt[k] = __fdiv_rn(wt[k], total);
+  if (xsize == 0) idx[0] = min(max(xmin, 0), in - 1);
+  for (int k = 0; k < K; ++k) idx[k] = min(max(idx[k], 0), in - 1);
+}
+
+template <typename D>
+__global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, RoiGeo g) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  float* lut = reinterpret_cast<float*>(smem + g.off_lut);
+  float* xw = reinterpret_cast<float*>(smem + g.off_xw);
+  int* xi = reinterpret_cast<int*>(smem + g.off_xi);
+  float* yw = reinterpret_cast<float*>(smem + g.off_yw);
+  int* yi = reinterpret_cast<int*>(smem + g.off_yi);
+  float* tmp = reinterpret_cast<float*>(smem + g.off_tmp);
+  unsigned char* sb = smem + g.off_sb;
+
+  const int tid = threadIdx.x;
+  const int n = blockIdx.z, t = blockIdx.y;
+  const int tr = blockIdx.x / g.col_tiles, tc = blockIdx.x - tr * g.col_tiles;
+  const int Y0 = tr * g.B, X0 = tc * g.TW;
+  const int Bv = min(g.B, d.out_h - Y0), TWv = min(g.TW, d.out_w - X0);
+  const int C = d.c, KH = g.KH, KW = g.KW;
+
+  // the box, clamped the way a Python slice clamps it
+  const int32_t* bx = d.box + 4 * (int64_t)n;
+  const int x1 = min(max(bx[0], 0), d.w - 1), y1 = min(max(bx[1], 0), d.h - 1);
+  const int x2 = min(max(bx[2], x1 + 1), d.w), y2 = min(max(bx[3], y1 + 1), d.h);
+  const int bw = x2 - x1, bh = y2 - y1;
+  int dy = 0, dx = 0;
+  if (d.crop) {
+    dy = d.crop[2 * (int64_t)n] - d.pad;
+    dx = d.crop[2 * (int64_t)n + 1] - d.pad;
+  }
+
+  // 1. tables (source indices relative to the box) and the byte table
+  for (int e = tid; e < 256; e += kThreads) lut[e] = d.lut[e];
+  if (tid < g.TW) {
+    const int r = min(max(X0 + min(tid, TWv - 1) + dx, 0), d.out_w - 1);
+    int id[kMaxTaps];
+    float w[kMaxTaps];
+    roi_taps(r, bw, d.out_w, d.antialias, KW, id, w);
+    for (int k = 0; k < KW; ++k) { xi[tid * KW + k] = id[k]; xw[tid * KW + k] = w[k]; }
+  } else if (tid >= 64 && tid < 64 + g.B) {
+    const int j = tid - 64;
+    const int r = min(max(Y0 + min(j, Bv - 1) + dy, 0), d.out_h - 1);
+    int id[kMaxTaps];
+    float w[kMaxTaps];
+    roi_taps(r, bh, d.out_h, d.antialias, KH, id, w);
+    for (int k = 0; k < KH; ++k) { yi[j * KH + k] = id[k]; yw[j * KH + k] = w[k]; }
+  }
+  __syncthreads();
+  // the source window the taps touch (indices are monotonic in the output index; the first tap is the smallest)
+  int xlo = xi[0], xhi = xi[0], ylo = yi[0], yhi = yi[0];
+  for (int k = 0; k < KW; ++k) xhi = max(xhi, xi[(TWv - 1) * KW + k]);
+  for (int k = 0; k < KH; ++k) yhi = max(yhi, yi[(Bv - 1) * KH + k]);
+  const int ncol = min(xhi - xlo + 1, g.SP), nrow = min(yhi - ylo + 1, g.R);
+
+  // 2. stage the window's bytes: sb[(row * SP + col) * C + ch]
+  const uint8_t* base = d.src + n * d.sn + t * d.st + (int64_t)(y1 + ylo) * d.sh + (int64_t)(x1 + xlo) * d.sw;
+  if (d.sc == 1 && d.sw >= C) {
+    // one aligned dword per lane over each row's bytes [first pixel, last pixel's channel C-1]: every dword holds at
+    // least one byte of an in-frame pixel of the window
+    const int pitch = (int)d.sw;
+    const int rbytes = (ncol - 1) * pitch + C;
+    for (int r = 0; r < nrow; ++r) {
+      const uint8_t* rp = base + (int64_t)r * d.sh;
+      const uintptr_t a0 = (uintptr_t)rp & ~(uintptr_t)3;
+      const int nd = (int)(((uintptr_t)rp + rbytes + 3 - a0) >> 2);
+      for (int q = tid; q < nd; q += kThreads) {
+        const uint32_t v = *reinterpret_cast<const uint32_t*>(a0 + 4 * (uintptr_t)q);
+        // byte offsets within the row window are < SP * pitch: 32-bit, one division per dword, then a walk
+        const int off0 = (int)((int64_t)(a0 + 4 * (uintptr_t)q) - (int64_t)(uintptr_t)rp);
+        const int o = max(off0, 0);
+        int px = o / pitch, ch = o - px * pitch;
+#pragma unroll
+        for (int b = max(-off0, 0); b < 4; ++b) {
+          if (off0 + b >= rbytes) break;
+          if (ch < C) sb[(r * g.SP + px) * C + ch] = (unsigned char)(v >> (8 * b));
+          if (++ch == pitch) { ch = 0; ++px; }
+        }
+      }
+    }
+  } else {
+    const int total = nrow * ncol * C;
+    for (int e = tid; e < total; e += kThreads) {
+      const int ch = e % C, px = (e / C) % ncol, r = e / (C * ncol);
+      sb[(r * g.SP + px) * C + ch] = base[(int64_t)r * d.sh + (int64_t)px * d.sw + (int64_t)ch * d.sc];
+    }
+  }
+  __syncthreads();
+
+  // 3. horizontal pass: tmp[(row * C + ch) * TW + j]
+  {
+    const int total = nrow * C * TWv;
+    for (int e = tid; e < total; e += kThreads) {
+      const int j = e % TWv, rc = e / TWv;
+      const int ch = rc % C, r = rc / C;
+      const unsigned char* row = sb + r * g.SP * C + ch;
+      float acc = 0.f;
+      for (int k = 0; k < KW; ++k) {
+        const int col = min(max(xi[j * KW + k] - xlo, 0), ncol - 1);
+        const float p = __fmul_rn(lut[row[col * C]], xw[j * KW + k]);
+        acc = k == 0 ? p : __fadd_rn(acc, p);
+      }
+      tmp[(r * C + ch) * g.TW + j] = acc;
+    }
+  }
+  __syncthreads();
+
+  // 4. vertical pass and the stores, one destination row of one channel plane per TW lanes
+  {
+    const int total = C * Bv * TWv;
+    for (int e = tid; e < total; e += kThreads) {
+      const int j = e % TWv, rc = e / TWv;
+      const int yy = rc % Bv, ch = rc / Bv;
+      float acc = 0.f;
+      for (int k = 0; k < KH; ++k) {
+        const int r = min(max(yi[yy * KH + k] - ylo, 0), nrow - 1);
+        const float p = __fmul_rn(tmp[(r * C + ch) * g.TW + j], yw[yy * KH + k]);
+        acc = k == 0 ? p : __fadd_rn(acc, p);
+      }
+      const int ry = Y0 + yy + dy, rx = X0 + j + dx;
+      if (ry < 0 || ry >= d.out_h || rx < 0 || rx >= d.out_w) acc = 0.f;
+      D* o = static_cast<D*>(d.dst) + n * d.dn + t * d.dt + (int64_t)(d.c_off + ch) * d.dc + (int64_t)(Y0 + yy) * d.dh + X0 + j;
+      *o = (D)acc;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int sfk_roi_resize(const sfk_roi_desc* d, sfk_stream_t stream) {
+  if (!d || d->struct_size != sizeof(sfk_roi_desc)) return SFK_ERR_INVALID;
+  if (!d->src || !d->lut || !d->box || !d->dst) return SFK_ERR_INVALID;
+  if (d->n <= 0 || d->t <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->out_h <= 0 || d->out_w <= 0) return SFK_ERR_INVALID;
+  if (d->sn < 0 || d->st < 0 || d->sh < 0 || d->sw < 0 || d->sc < 0 || d->dn < 0 || d->dt < 0 || d->dc < 0 || d->dh < 0)
+    return SFK_ERR_INVALID;
+  if ((d->antialias != 0 && d->antialias != 1) || d->pad < 0 || d->c_off < 0) return SFK_ERR_INVALID;
+  if (d->dst_dtype != SFK_F32 && d->dst_dtype != SFK_BF16) return SFK_ERR_INVALID;
+  if (d->c > SFK_ROI_MAX_C || (d->sc == 1 && d->sw > 4096)) return SFK_ERR_UNSUPPORTED;
+  const double sh = (double)d->h / d->out_h, sw = (double)d->w / d->out_w;
+  if (sh > SFK_ROI_MAX_RATIO || sw > SFK_ROI_MAX_RATIO) return SFK_ERR_UNSUPPORTED;
+  // worst-case taps: the box never exceeds its frame, so its ratio never exceeds sh / sw
+  const int KH = d->antialias ? (int)ceil(sh > 1.0 ? sh : 1.0) * 2 + 1 : 2;
+  const int KW = d->antialias ? (int)ceil(sw > 1.0 ? sw : 1.0) * 2 + 1 : 2;
+  const double spans_h = sh > 1.0 ? sh : 1.0, spans_w = sw > 1.0 ? sw : 1.0;
+  RoiGeo g{};
+  bool ok = false;
+  for (int TW : {64, 32, 16}) {
+    for (int B : {16, 8, 4, 2, 1}) {
+      g = roi_layout(B, TW, d->c, KH, KW, spans_h, spans_w, d->out_h, d->out_w);
+      if (g.lds <= kLdsBudget) { ok = true; break; }
+    }
+    if (ok) break;
+  }
+  if (!ok) return SFK_ERR_UNSUPPORTED;
+  const int64_t tiles = (int64_t)g.row_tiles * g.col_tiles;
+  if (tiles > 0x7fffffff || d->t > 65535 || d->n > 65535) return SFK_ERR_UNSUPPORTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)tiles, (unsigned)d->t, (unsigned)d->n);
+  if (d->dst_dtype == SFK_BF16)
+    hipLaunchKernelGGL(roi_resize_kernel<bf16_t>, grid, dim3(kThreads), g.lds, s, *d, g);
+  else
+    hipLaunchKernelGGL(roi_resize_kernel<float>, grid, dim3(kThreads), g.lds, s, *d, g);
+  SFK_CHECK_LAUNCH();
+  return SFK_OK;
+}
+
+extern "C" int sfk_v2_abi_version(void) { return SFK_V2_ABI_VERSION; }

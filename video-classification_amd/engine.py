@@ -319,6 +319,8 @@ class Engine:
         self.adam_m = None
         self.adam_v = None
         self.adam_step = None
+        self.sgd_buf = None
+        self.sgd_step = None
         # compute-precision copies of the filters: S = [cout][tap][cin] (forward, filter-gradient layout),
         # St = [cin][tap][cout] (data-gradient pass)
         self.S = self.P.data if self.dtype == torch.float32 else self._new(self.conv_total, dtype=self.dtype)
@@ -1424,6 +1426,17 @@ class Engine:
         self._adam_state()
         return self.be.adam(self.P.data, self.G, self.adam_m, self.adam_v, self.arena_numel, lr, betas[0], betas[1],
                             eps, grad_scale, self.adam_step, None)
+
+    def sgd_ops(self, lr: float, momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False,
+                grad_scale: float = 1.0) -> Run:
+        """torch.optim.SGD (no weight decay) over the whole arena in one sfk_sgd launch (include/sfk_v2.h), with a momentum
+        buffer the size of G and a step counter of its own, both allocated on first use.  Arena entries without a live
+        parameter (dead fusion weights, padding) keep G == 0 and therefore stay as they are, as in torch."""
+        if self.sgd_step is None:
+            self.sgd_buf = self._new(self.arena_numel)
+            self.sgd_step = self._new(1, dtype=torch.int64)
+        return self.be.sgd(self.P.data, self.G, self.sgd_buf, self.arena_numel, lr, momentum, dampening, nesterov,
+                           grad_scale, self.sgd_step, None)
 
     def adam_split_ops(self, cut: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, grad_scale: float = 1.0):
         """(main, tail): the same update as adam_ops in two launches -- arena [cut:] (increments the step counter) and [:cut]

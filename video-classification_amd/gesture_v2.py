@@ -1,0 +1,274 @@
+"""The v2 part-box recipe of the reference (new_feature_test.py:470-979) on the engine.
+
+What it is: SlowFast with a 5-channel slow pathway (RGB + DensePose UV) and a 2-channel fast pathway (gray optical flow),
+``init_my_slowfast(cfg, (5, 2), (64, 8))``, trained with SGD (momentum 0.9) on clips cropped to the union of chosen
+DensePose part boxes over the clip's frames and resized to MODEL.INPUT_SIZE.
+
+What differs from the reference, and why:
+  * the dataset (``ChalearnGestureFrames``) samples frames and boxes exactly as ``ChalearnGestureDataset`` but hands over
+    the uncropped uint8 frames (T, H, W, 7) = [R, G, B, U, V, F0, F1] and the box; the crop, ``/255`` and the bilinear
+    ``Resize`` run on the device in one ``sfk_roi_resize`` launch (``input_pipeline.RoiResize``).  The resize is pinned
+    to ``torch.nn.functional.interpolate``, which torchvision's tensor ``Resize`` calls; torchvision itself is unpinned
+    (not installed here).  MODEL.RESIZE_ANTIALIAS picks its antialias flag: True is torchvision >= 0.17, False older;
+  * ``ModelManager.prepare_data`` still takes the reference loader's float batch {'rgb', 'uv', 'flow', 'label'};
+  * the Trainer is ``train.Trainer`` (checkpoints, device-side eval aggregation, one process per GPU) with the v2
+    optimiser, parts and a train loader that keeps the last, smaller batch (drop_last=False, :815).
+"""
+from __future__ import annotations
+
+import pickle
+import random
+from pathlib import Path
+from typing import Callable, List, Optional, Sequence
+
+import numpy as np
+import torch
+import torch.utils.data
+
+from . import train as _train
+from .slowfast import init_my_slowfast
+
+CHANNELS = ("R", "G", "B", "U", "V", "F0", "F1")     # frames_u8's last axis; slow = [0:5], fast = [5:7]
+
+
+class PartCompose:
+    """DensePose part ids and their compositions (new_feature_test.py:470-547), restated."""
+    lHand = [4]
+    rHand = [3]
+    lUpArm = [15, 17]
+    rUpArm = [16, 18]
+    lLoArm = [19, 21]
+    rLoArm = [20, 22]
+    torso = [1, 2]
+    head = [23, 24]
+    lArm = lUpArm + lLoArm
+    rArm = rUpArm + rLoArm
+    TorsoArmHand = torso + lArm + rArm + lHand + rHand
+    lHandLoArm = lHand + lLoArm
+    lHandArm = lHand + lArm
+    lHandArmTorso = lHand + lArm + torso
+    rHandLoArm = rHand + rLoArm
+    rHandArm = rHand + rArm
+    rHandArmTorso = rHand + rArm + torso
+
+    @staticmethod
+    def combine_box_xyxy(box_arr) -> tuple:
+        """(N, 4) boxes -> their union (min x1, min y1, max x2, max y2)"""
+        assert len(box_arr) > 0
+        a = np.array(box_arr)
+        return (min(a[:, 0]), min(a[:, 1]), max(a[:, 2]), max(a[:, 3]))
+
+    def combine_spatial_box_xyxy(self, part_boxes, part_list):
+        """one frame's [P][4] part boxes -> the union over part_list (None parts skipped); None when no part is there"""
+        if part_boxes is None:
+            return None
+        boxes = [part_boxes[p] for p in part_list]
+        boxes = [b for b in boxes if b is not None]
+        return self.combine_box_xyxy(np.array(boxes)) if boxes else None
+
+    def combine_temporal_box_xyxy(self, temporal_part_boxes, part_list):
+        """[T][P][4] -> the union over the frames (None frames and frames without any of the parts skipped)"""
+        per_frame = [self.combine_spatial_box_xyxy(pb, part_list) for pb in temporal_part_boxes]
+        per_frame = [b for b in per_frame if b is not None]
+        if not per_frame:
+            raise ValueError(f"no box of parts {list(part_list)} in any frame of the clip")
+        return self.combine_box_xyxy(per_frame)
+
+
+def parts_of(name: str) -> List[int]:
+    """MODEL.PARTS -> the part ids (a PartCompose attribute name, e.g. 'lHandArmTorso')"""
+    parts = getattr(PartCompose, str(name), None)
+    if not isinstance(parts, list):
+        raise ValueError(f"MODEL.PARTS={name!r} is not a PartCompose composition")
+    return list(parts)
+
+
+def random_sampling(seq_len: int, clip_len: int, rng=random) -> List[int]:
+    """new_feature_test.py:663-669: a random start (randint, both ends included), indices wrapped mod seq_len"""
+    start = rng.randint(0, max(0, seq_len - clip_len))
+    return [i % seq_len for i in range(start, start + clip_len)]
+
+
+def uniform_sampling(seq_len: int, clip_len: int, rng=random) -> List[List[int]]:
+    """new_feature_test.py:671-680: non-overlapping windows range(0, seq_len - clip_len, clip_len); one random clip when
+    the video is not longer than a clip"""
+    if seq_len <= clip_len:
+        return [random_sampling(seq_len, clip_len, rng)]
+    return [list(range(t, t + clip_len)) for t in range(0, seq_len - clip_len, clip_len)]
+
+
+def change_base(path: Path, base: str) -> Path:
+    """ChaPath.change_base (new_feature_test.py:40-46): the 4th path component from the end -> base"""
+    parts = list(Path(path).parts)
+    parts[-4] = base
+    return Path(*parts)
+
+
+def decord_read_video(filename: Path, channels: int, frames: Sequence[int], format: str = "gray") -> torch.Tensor:
+    """VideoIO.read_video_TCHW (new_feature_test.py:95-132): (T, C, H, W) uint8; 'rgb24' reads one colour video, 'gray'
+    reads the channel videos '<c>_<name>' and keeps their first plane."""
+    try:
+        import decord
+    except ImportError as e:
+        raise RuntimeError("ChalearnGestureFrames needs decord to read videos (not installed); pass read_video=") from e
+    decord.bridge.set_bridge("torch")
+    if format == "rgb24":
+        return decord.VideoReader(str(filename)).get_batch(list(frames)).permute(0, 3, 1, 2)
+    planes = [decord.VideoReader(str(Path(filename.parent, f"{c}_{filename.name}"))).get_batch(list(frames))[..., 0]
+              for c in range(channels)]
+    return torch.stack(planes, dim=1)
+
+
+class ChalearnGestureFrames(torch.utils.data.Dataset):
+    """The reference's ChalearnGestureDataset (new_feature_test.py:556-710) with the crop and resize left to the device.
+
+    labels: the reference's ``Labels(cfg).from_set(name_of_set)`` list of (rgb path, depth path, 1-based label).  Items:
+    {'frames_u8': (T, H, W, 7) uint8 [R, G, B, U, V, F0, F1], 'box': int32 (x1, y1, x2, y2) clamped to the frame,
+    'label': label - 1}; a list of them for sampling='uniform'.  read_video(path, channels, indices, format) -> (T, C, H, W)
+    uint8 is injectable (default: decord, as the reference)."""
+
+    def __init__(self, cfg, name_of_set: str, parts, sampling: str, labels, read_video: Optional[Callable] = None):
+        assert name_of_set in ("train", "test", "valid")
+        assert sampling in ("random", "uniform")
+        self.label_list = list(labels)
+        self.parts = list(parts)
+        self.clip_len = cfg.CHALEARN.CLIP_LEN
+        self.root, self.sample_base = cfg.CHALEARN.ROOT, cfg.CHALEARN.SAMPLE
+        self.box_base, self.flow_base, self.uv_base = cfg.CHALEARN.BOX, cfg.CHALEARN.FLOW_VIDEO, cfg.CHALEARN.UV_VIDEO
+        self.sampling = sampling
+        self.compose = PartCompose()
+        self.read_video = read_video or decord_read_video
+        self.rng = random
+
+    def __len__(self):
+        return len(self.label_list)
+
+    def clip_box(self, boxes, clip_indices, h: int, w: int) -> torch.Tensor:
+        """the union box of the clip's frames, x1, y1 = max(0, .) as the reference, x2, y2 clamped to the frame as its
+        slice clamps them; an empty box is a ValueError"""
+        x1, y1, x2, y2 = (int(v) for v in self.compose.combine_temporal_box_xyxy([boxes[i] for i in clip_indices], self.parts))
+        x1, y1 = max(0, x1), max(0, y1)
+        x2, y2 = min(x2, w), min(y2, h)
+        if x2 <= x1 or y2 <= y1:
+            raise ValueError(f"empty part box {(x1, y1, x2, y2)} in a {w}x{h} frame")
+        return torch.tensor([x1, y1, x2, y2], dtype=torch.int32)
+
+    def _features_from_indices(self, clip_indices, boxes, rgb_path, label):
+        flow = self.read_video(change_base(rgb_path, self.flow_base), 2, clip_indices, "gray")
+        uv = self.read_video(change_base(rgb_path, self.uv_base), 2, clip_indices, "gray")
+        rgb = self.read_video(rgb_path, 0, clip_indices, "rgb24")
+        x = torch.cat([rgb, uv, flow], dim=1)                          # T, 7, H, W
+        _, _, h, w = x.shape
+        box = self.clip_box(boxes, clip_indices, h, w)
+        return {"frames_u8": x.permute(0, 2, 3, 1).contiguous(), "box": box, "label": label - 1}
+
+    def __getitem__(self, index):
+        rgb_path, _depth_path, label = self.label_list[index]
+        rgb_path = Path(self.root, self.sample_base, rgb_path)
+        with change_base(rgb_path, self.box_base).with_suffix(".pkl").open("rb") as f:
+            boxes = pickle.load(f)
+        seq_len = len(boxes) - 1                    # as the reference: the reader's frame count is one short
+        if self.sampling == "random":
+            return self._features_from_indices(random_sampling(seq_len, self.clip_len, self.rng), boxes, rgb_path, label)
+        return [self._features_from_indices(ci, boxes, rgb_path, label)
+                for ci in uniform_sampling(seq_len, self.clip_len, self.rng)]
+
+
+class SyntheticGesture(torch.utils.data.Dataset):
+    """Seeded stand-in with ChalearnGestureFrames' item contract: random uint8 frames of h x w with a random box per clip
+    (train -> dict, test -> list of dicts), for tests and tools/bench_v2.py."""
+
+    def __init__(self, cfg, name_of_set: str, num_videos: int = 8, clips_per_video=(1, 3), seed: int = 0,
+                 h: int = 240, w: int = 320, min_box: int = 15):
+        self.cfg, self.name = cfg, name_of_set
+        self.t, self.h, self.w, self.min_box = int(cfg.CHALEARN.CLIP_LEN), h, w, min_box
+        g = torch.Generator().manual_seed(seed)
+        self.labels = torch.randint(0, cfg.CHALEARN.NUM_CLASS, (num_videos,), generator=g).tolist()
+        self.nclips = torch.randint(clips_per_video[0], clips_per_video[1] + 1, (num_videos,), generator=g).tolist()
+        self.seed = seed
+
+    def __len__(self):
+        return len(self.labels)
+
+    def _clip(self, i, j):
+        g = torch.Generator().manual_seed(self.seed * 7919 + i * 31 + j)
+        frames = torch.randint(0, 256, (self.t, self.h, self.w, 7), generator=g, dtype=torch.uint8)
+        x1 = int(torch.randint(0, self.w - self.min_box, (1,), generator=g))
+        y1 = int(torch.randint(0, self.h - self.min_box, (1,), generator=g))
+        x2 = int(torch.randint(x1 + self.min_box, self.w + 1, (1,), generator=g))
+        y2 = int(torch.randint(y1 + self.min_box, self.h + 1, (1,), generator=g))
+        return {"frames_u8": frames, "box": torch.tensor([x1, y1, x2, y2], dtype=torch.int32), "label": self.labels[i]}
+
+    def __getitem__(self, i):
+        if self.name == "train":
+            return self._clip(i, 0)
+        return [self._clip(i, j) for j in range(self.nclips[i])]
+
+
+class ModelManager(_train.ModelManager):
+    """new_feature_test.py:712-775: init_my_slowfast(cfg, (5, 2), (64, 8)) with the v1 pretrained surgery, and
+    prepare_data for the reference's float batch or the uint8 batch of ChalearnGestureFrames."""
+
+    def __init__(self, cfg, device="cuda", backend=None):
+        self.cfg, self.device, self.backend = cfg, device, backend
+        self._pre = None
+        self._lut = None
+        self._roi = None
+        self.arch = "ref"
+        self.init_model = self._init_v2_model
+        self.prepare_data = self._prepare_v2_data
+
+    def _init_v2_model(self):
+        model = init_my_slowfast(self.cfg, (5, 2), (64, 8), device=self.device, backend=self.backend)
+        ckpt = Path("pretrained", "SLOWFAST_8x8_R50.pyth")          # :741-759 (absent offline: random init)
+        if ckpt.is_file():
+            state = torch.load(ckpt, map_location="cpu", weights_only=True)["model_state"]
+            model.load_state_dict(self.delete_mismatch(state), strict=False)
+        else:
+            print(f"warning: {ckpt} not found, training from the reference init scheme")
+        return model
+
+    def roi_resize(self) -> "RoiResize":
+        if self._roi is None:
+            from .input_pipeline import RoiResize
+            from .slowfast import _DTYPES
+            dtype = _DTYPES[str(self.cfg.MODEL.get("DTYPE", "fp32")).lower()]
+            self._roi = RoiResize(int(self.cfg.MODEL.INPUT_SIZE), self.device, self.backend, out_dtype=dtype,
+                                  antialias=bool(self.cfg.MODEL.get("RESIZE_ANTIALIAS", True)))
+        return self._roi
+
+    def _prepare_v2_data(self, batch):
+        """-> [slow (N, 5, T, S, S), fast (N, 2, T, S, S)], labels.  The uint8 batch {'frames_u8', 'box'[, 'crop']} is
+        resized on the device into one (N, T, 7, S, S) tensor whose channel slices are the two pathways (no copy); the
+        float batch {'rgb', 'uv', 'flow'} is the reference's permute + cat (:761-769)."""
+        y = self._h2d(batch["label"])
+        if "frames_u8" in batch:
+            x = self.roi_resize()(batch["frames_u8"], batch["box"], batch.get("crop"))
+            x = torch.permute(x, [0, 2, 1, 3, 4])
+            return [x[:, 0:5], x[:, 5:7]], y
+        rgb, uv, flow = (torch.permute(self._h2d(batch[k]), [0, 2, 1, 3, 4]) for k in ("rgb", "uv", "flow"))
+        return [torch.cat([rgb, uv], dim=1), flow], y
+
+
+class Trainer(_train.Trainer):
+    """new_feature_test.py:796-979 on train.Trainer: SGD(lr, momentum 0.9), MODEL.PARTS, a train loader that keeps the
+    last smaller batch, uniform non-overlapping test windows; checkpoints, eval and the multi-process path as train.Trainer."""
+    train_drop_last = False                              # :815
+    momentum = 0.9                                       # :832
+
+    def _model_manager(self, cfg, device, backend):
+        return ModelManager(cfg, device=device, backend=backend)
+
+    def _make_step(self, eng, use_graph, reducer):
+        return _train.TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer, optimizer="sgd",
+                                momentum=self.momentum)
+
+    def _reference_datasets(self):
+        try:
+            from utils.chalearn import Labels                       # the reference's label lists, unchanged
+        except Exception as e:
+            raise RuntimeError("no datasets / loaders were given and the reference's utils.chalearn is not importable here "
+                               f"({e}); pass train_set/test_set (e.g. SyntheticGesture)") from e
+        parts = parts_of(self.cfg.MODEL.get("PARTS", "lHandArmTorso"))
+        return (ChalearnGestureFrames(self.cfg, "train", parts, "random", Labels(self.cfg).from_set("train")),
+                ChalearnGestureFrames(self.cfg, "test", parts, "uniform", Labels(self.cfg).from_set("test")))

@@ -135,3 +135,48 @@ def u8_pathways(frames: torch.Tensor, crop: Optional[torch.Tensor], lut: torch.T
     """U8Clips over the same device frames and crop, one per (c0, c) range; pad = S // 10 (RandomCrop's padding)."""
     pad = frames.shape[2] // 10
     return [U8Clip(frames, c0, c, crop, pad, lut) for c0, c in channels]
+
+
+def byte_lut() -> torch.Tensor:
+    """float32[256]: u / 255, the v2 loader's ``X.to(float32).div(255)`` (new_feature_test.py:600), bit for bit"""
+    return torch.arange(256).float().div(255)
+
+
+class RoiResize:
+    """The v2 part-box loader's crop + /255 + Resize((S, S)) (new_feature_test.py:590-661) on the device: uint8 frames
+    (N, T, H, W, C) and their boxes (N, 4) = (x1, y1, x2, y2) -> the (N, T, C, S, S) clip, f32 or bf16, in ONE
+    ``sfk_roi_resize`` launch (include/sfk_v2.h).  The resize is ``F.interpolate(bilinear, align_corners=False,
+    antialias=antialias)``, what torchvision's tensor ``Resize`` calls: pinned to torch, torchvision itself unpinned (it
+    is not installed here; it antialiases tensors by default from 0.17 on and did not before).  crop (N, 2) int32
+    (top, left) applies RandomCrop(S, padding) after the resize (``do_augment``), zeros outside."""
+
+    def __init__(self, size: int, device="cuda", backend=None, out_dtype: torch.dtype = torch.float32,
+                 antialias: bool = True):
+        if backend is None:
+            from ._lib import HipBackend
+            backend = HipBackend()              # raises when libsfk.so is missing: no CPU path
+        self.be, self.device, self.out_dtype = backend, torch.device(device), out_dtype
+        self.size, self.antialias = int(size), bool(antialias)
+        self.lut = byte_lut().to(self.device)
+
+    def _h2d(self, t: torch.Tensor) -> torch.Tensor:
+        if t.device.type == "cpu" and self.device.type == "cuda" and not t.is_pinned():
+            t = t.pin_memory()
+        return t.to(self.device, non_blocking=True)
+
+    def __call__(self, frames_u8: torch.Tensor, box: torch.Tensor, crop: Optional[torch.Tensor] = None,
+                 padding: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 5
+        n, t, h, w, c = frames_u8.shape
+        x = self._h2d(frames_u8)
+        box = self._h2d(box.to(torch.int32)).contiguous()
+        assert tuple(box.shape) == (n, 4)
+        pad = 0
+        if crop is not None:
+            pad = self.size // 10 if padding is None else int(padding)
+            crop = self._h2d(crop.to(torch.int32)).contiguous()
+        if out is None:
+            out = torch.empty(n, t, c, self.size, self.size, dtype=self.out_dtype, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+        self.be.roi_resize(x, self.lut, box, out, self.antialias, crop, pad)(stream)
+        return out

@@ -42,8 +42,14 @@ class TrainStep:
     lowest host load.  Every switch comes from ``engine.options`` (engine.EngineOptions); nothing here reads the environment."""
 
     def __init__(self, engine: Engine, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, use_graph: bool = False,
-                 reducer: Optional[sdist.GradReducer] = None, overlap_segments: int = 6):
+                 reducer: Optional[sdist.GradReducer] = None, overlap_segments: int = 6, optimizer: str = "adam",
+                 momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False):
+        """optimizer 'adam' (train.py:182: lr, betas, eps) or 'sgd' (the v2 trainer, new_feature_test.py:832: lr, momentum,
+        dampening, nesterov; one sfk_sgd launch over the arena, never split beside the last kernel)."""
+        if optimizer not in ("adam", "sgd"):
+            raise ValueError(f"optimizer={optimizer!r}: 'adam' or 'sgd'")
         self.eng, self.lr, self.betas, self.eps = engine, lr, betas, eps
+        self.optimizer, self.momentum, self.dampening, self.nesterov = optimizer, momentum, dampening, nesterov
         self.reducer = reducer
         self.world = reducer.world if reducer is not None else 1
         self.segmented = reducer is not None and reducer.active     # cut backward into segments and exchange them as they finish
@@ -74,14 +80,19 @@ class TrainStep:
 
     def _build(self, pl, labels):
         eng = self.eng
+        gscale = self.reducer.grad_scale if self.reducer is not None else 1.0
+        if self.optimizer == "sgd":
+            opt = eng.sgd_ops(self.lr, self.momentum, self.dampening, self.nesterov, gscale)
+        else:
+            opt = eng.adam_ops(self.lr, self.betas, self.eps, gscale)
         ops = dict(
             loss=eng.loss_ops(pl, labels, self.loss, self.loss_sum, self.correct),
-            adam=eng.adam_ops(self.lr, self.betas, self.eps, self.reducer.grad_scale if self.reducer is not None else 1.0),
+            adam=opt,                 # the optimiser launch, Adam or SGD (the key bench.py's profiler reads)
             zero_loss=eng.be.fill_zero(self.loss),
             zero_grad=eng.be.fill_zero(eng.G),
         )
-        # the optimiser beside the last kernel of the step (engine.Plan.tail_cut): eager four-lane single-rank steps only
-        if (pl.tail_cut is not None and not self.segmented and not self.use_graph and eng.two_streams and eng.device.type == "cuda"
+        # the optimiser beside the last kernel of the step (engine.Plan.tail_cut): eager four-lane single-rank Adam steps only
+        if (self.optimizer == "adam" and pl.tail_cut is not None and not self.segmented and not self.use_graph and eng.two_streams and eng.device.type == "cuda"
                 and eng.options.split_adam):
             ops["adam_main"], ops["adam_tail"] = eng.adam_split_ops(pl.tail_cut[1], self.lr, self.betas, self.eps)
         return ops
@@ -399,7 +410,7 @@ class Trainer:
                 train_set, test_set = self._reference_datasets()
             train_loader, test_loader = self._make_loaders(train_set, test_set)
         self.train_loader, self.test_loader = train_loader, test_loader
-        self.mm = ModelManager(cfg, device=device, backend=backend)
+        self.mm = self._model_manager(cfg, device, backend)
         self.model = self.mm.init_model()
         self.num_step = 0
         self.ckpt_dir = Path(cfg.CHALEARN.ROOT, cfg.MODEL.LOGS, cfg.MODEL.CKPT_DIR, cfg.MODEL.NAME)
@@ -413,7 +424,16 @@ class Trainer:
             self.step = TorchStep(self.model, lr=cfg.MODEL.LR)
         else:
             reducer = sdist.GradReducer(eng.G, bucket_mb=cfg.DIST.BUCKET_MB) if self.world > 1 else None
-            self.step = TrainStep(eng, lr=cfg.MODEL.LR, use_graph=use_graph, reducer=reducer)
+            self.step = self._make_step(eng, use_graph, reducer)
+
+    # ---- what a derived trainer (gesture_v2.Trainer) swaps: the model manager, the optimiser, the train loader's drop_last
+    train_drop_last = True                               # train.py:164
+
+    def _model_manager(self, cfg, device, backend):
+        return ModelManager(cfg, device=device, backend=backend)
+
+    def _make_step(self, eng, use_graph, reducer):
+        return TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer)
 
     def _reference_datasets(self):
         try:
@@ -429,15 +449,17 @@ class Trainer:
         pin = torch.device(self.device).type == "cuda"
         kw = dict(num_workers=self.num_workers, pin_memory=pin)
         if self.world > 1:
-            self.train_sampler = sdist.EpochShardSampler(len(tr), self.rank, self.world, seed=0)
+            self.train_sampler = sdist.EpochShardSampler(len(tr), self.rank, self.world, seed=0,
+                                                         drop_last=self.train_drop_last)
             train = torch.utils.data.DataLoader(tr, batch_size=self.batch_size, sampler=self.train_sampler,
-                                                drop_last=True, **kw)
+                                                drop_last=self.train_drop_last, **kw)
             test = torch.utils.data.DataLoader(te, batch_size=self.batch_size, drop_last=False, collate_fn=_identity,
                                                sampler=sdist.VideoShardSampler(len(te), self.rank, self.world), **kw)
             test.sfk_shard = (self.rank, self.world, len(te))
         else:
             self.train_sampler = None
-            train = torch.utils.data.DataLoader(tr, batch_size=self.batch_size, shuffle=True, drop_last=True, **kw)
+            train = torch.utils.data.DataLoader(tr, batch_size=self.batch_size, shuffle=True,
+                                                drop_last=self.train_drop_last, **kw)
             test = torch.utils.data.DataLoader(te, batch_size=self.batch_size, shuffle=False, drop_last=False,
                                                collate_fn=_identity, **kw)
         return train, test
