@@ -40,8 +40,9 @@ extern "C" {
  * sfk_tuning.wgrad_target_256 / wgrad_min_stages_256 (retired in 15); 12 = sfk_bn_apply(out_sums), sfk_bn_tail_fwd / _bwd take the column sums
  * of `a` from it (no constant-1 channel group beside the activation any more); 13 = sfk_conv_pw_dual; 14 = sfk_tuning.igemm_p8 / wgrad_p8,
  * sfk_conv_igemm_family value 4; 15 = sfk_tuning.igemm_halo, family value 5; 16 = sfk_tuning.wgrad_band; 17 = sfk_tuning.stem_v3; 18 = sfk_bn_finalize_apply (19, 20: SFK_BN_SYNC_INTS counters),
- * sfk_bn_bwd_finalize_apply. */
-#define SFK_ABI_VERSION 20
+ * sfk_bn_bwd_finalize_apply; 21 = the two fused finalize launches, SFK_BN_SYNC_INTS and sfk_tuning.wgrad_target_256 /
+ * wgrad_min_stages_256 removed, stem_v3 bit 2 retired. */
+#define SFK_ABI_VERSION 21
 #define SFK_MAX_TAPS 16
 #define SFK_BN_FOLD_ROWS 64 /* rows of the optional BatchNorm fold workspace */
 
@@ -271,19 +272,6 @@ int sfk_bn_apply(const sfk_fmap* y, const float* scale, const float* shift, cons
                  const float* res_scale, const float* res_shift, int32_t relu, const sfk_fmap* out,
                  uint8_t* relu_bits, float* out_sums, int32_t max_parts, int32_t* nparts_out, sfk_stream_t stream);
 
-/* sfk_bn_finalize + sfk_bn_apply in ONE launch: the apply's first workgroups fold the partial rows (the same deterministic block
- * sums: results bit-identical to the two calls), every workgroup waits for their counter before it reads scale / shift.  The
- * step's finalize launches are 8 us kernels on dependent chains behind a dispatch gap each; as a prologue the fold runs under
- * the dispatch ramp of the consumer's own grid.  Arguments as the two calls (c = y->c; out_sums is not available here);
- * sync: SFK_BN_SYNC_INTS int32 of the caller's, ZERO before the first call and left zero by every call (one set per BatchNorm that
- * may be in flight at the same time).  Meant for c <= 512: the channel pairs are claimed through one counter. */
-#define SFK_BN_SYNC_INTS 2144
-int sfk_bn_finalize_apply(const float* partials, int32_t nparts, int64_t count, const float* gamma, const float* beta,
-                          float eps, float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked,
-                          float* mean, float* invstd, float* workspace, int32_t* sync, const sfk_fmap* y, float* scale,
-                          float* shift, const sfk_fmap* res, const float* res_scale, const float* res_shift, int32_t relu,
-                          const sfk_fmap* out, uint8_t* relu_bits, sfk_stream_t stream);
-
 /* Backward of a = act(bn(y) [+ shortcut]) given dA:
  *   dz = dA * mask,   mask = relu_bits (as written by sfk_bn_apply) if given, else (mask_src > 0) if mask_src,
  *                     else (y*scale+shift > 0) if relu, else 1
@@ -302,11 +290,6 @@ int sfk_bn_bwd_finalize(const float* partials, int32_t nparts, int32_t c, int64_
 int sfk_bn_bwd_apply(const sfk_fmap* da, const sfk_fmap* y, const sfk_fmap* mask_src, const float* mean,
                      const float* invstd, const float* scale, const float* shift, int32_t relu,
                      const float* coef, const sfk_fmap* dy, sfk_stream_t stream);
-/* sfk_bn_bwd_finalize + sfk_bn_bwd_apply in one launch (see sfk_bn_finalize_apply; results bit-identical to the two calls). */
-int sfk_bn_bwd_finalize_apply(const float* partials, int32_t nparts, int64_t count, const float* gamma, float* dgamma,
-                              float* dbeta, float* coef, float* workspace, int32_t* sync, const sfk_fmap* da, const sfk_fmap* y,
-                              const sfk_fmap* mask_src, const float* mean, const float* invstd, const float* scale,
-                              const float* shift, int32_t relu, const sfk_fmap* dy, sfk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * The block tail  a -> conv_c (1x1x1, bias=False) -> norm_c (BatchNorm3d) [-> + shortcut -> ReLU]  WITHOUT the conv output
@@ -508,8 +491,6 @@ typedef struct {
                                          bit 1: 224 computed rows per tile where that fills the CUs better (M = 50,176)   */
   int32_t wgrad_target_gen;   /* 512:  ... of the register-staged filter-gradient kernels (0 = 1024); round 3: 768 -> 512,
                                          -0.15 ms per step on two boxes (fewer, longer workgroups on the side lanes)   */
-  int32_t wgrad_target_256;   /* retired (ignored): the round-3 256-column ring tile; conv_wgrad_p8.hip serves those layers (wgrad_p8) */
-  int32_t wgrad_min_stages_256; /* retired (ignored)                                                                          */
   int32_t igemm_p8;           /* 1:    bit 0: the deep-pipelined 256 x 256 conv tile (one workgroup per CU, 64-channel K-tiles, LDS-DMA
                                          in flight across the barriers, wave groups half a phase apart) for the MFMA-bound
                                          layers; bit 1: 224 computed rows per tile where that needs fewer row-generations   */
@@ -523,8 +504,7 @@ typedef struct {
   int32_t stem_v3;            /* 3:    bit 0: the input-frame-stationary forward of the canonical fast stem (filter in registers, one LDS
                                          pixel run per three MFMAs, half tiles with two workgroups per CU: stem_fwd_v4_kernel);
                                          bit 1: the same machinery for the canonical slow stem (kt = 1, 64 channels:
-                                         stem_fwd_s4_kernel); bit 2 (EXPERIMENT): whole frames per workgroup in the fast stem's
-                                         filter gradient                                                                   */
+                                         stem_fwd_s4_kernel)                                                               */
 } sfk_tuning;
 int sfk_default_tuning(sfk_tuning* out); /* out->struct_size must be set; fills every other field */
 int sfk_init(const sfk_tuning* t);       /* NULL = defaults */

@@ -140,7 +140,6 @@ class EngineOptions:
     no environment variable at all: bench.py --ablate sets it and says so in its output line."""
     fuse_bn_bwd: bool = False          # BatchNorm-backward reduce in the dgrad epilogues (sfk_conv_desc.bnb): neutral .. -0.75 %
     tail_dual: bool = True             # sfk_conv_pw_dual for the narrowest block tails
-    shortcut_lane: str = "f"           # projection shortcuts beside branch2 on the filter-gradient lane: f forward, b backward, 1 both, 0 neither
     wgrad_lanes: int = 1               # 0: filter gradients on the pathway lanes; 1: one lane per pathway; 2: ONE lane for both
     relu_bits: bool = True             # block-output ReLU masks kept as bitmaps
     relu_out_mask: bool = True         # ... and applied by the data-gradient pass that finishes an identity block's output gradient
@@ -150,30 +149,20 @@ class EngineOptions:
     tail_max_c: int = 128
     fuse_stem_tail: bool = True        # the stems' BatchNorm -> ReLU -> MaxPool as one forward pass / two-pass backward
     fuse_tail_dg: bool = True          # R and the first dgrad pass of the tail backward in one kernel
-    tail_r_lane: int = 0               # R = dz^T a beside the first dgrad pass: 0 pathway lane, 2 filter-gradient lane, 4 own lanes
     split_refresh: bool = True         # filter refresh: stems on the trunk, the rest on the idle filter-gradient lane
     refresh_behind_stems: bool = True  # ... issued BEHIND the two stem convs (it waits for both) instead of beside them
     split_adam: bool = True            # Adam beside the last kernel of the step (TrainStep)
     trunk_priority: bool = True        # the trunk lane on a high-priority HIP stream (TrainStep)
-    mfma_wgrad_trunk: bool = False     # MFMA-bound filter gradients on the pathway's own lane, directly behind their data gradient
     dist_wgrad_one_lane: bool = True   # world > 1: all filter gradients on ONE lane, the collective's stream is the fourth queue
-    fuse_finalize: bool = False        # BatchNorm finalize as the prologue of its bn_apply / bn_bwd_apply launch (sfk_bn_finalize_apply):
-                                       # bit-identical, 5 us per launch alone -- and 27.7 -> 27.9 .. 28.1 ms in the step (waiting workgroups
-                                       # hold CUs the other lanes would use): off
-    fuse_finalize_max_c: int = 64      # ... for BatchNorms of at most this many channels (the pairs are claimed through one counter)
-    lane_cus: str = ""                 # EXPERIMENT: CUs the side lanes may use, "fast,wgrad_slow,wgrad_fast" (0 / empty = all): the
-                                       # side streams are created with hipExtStreamCreateWithCUMask (eager schedule only)
     ablate_kinds: frozenset = frozenset()
 
-    _ENV = {"SFK_FUSE_BNB": ("fuse_bn_bwd", "1"), "SFK_TAIL_DUAL": ("tail_dual", "!0"), "SFK_SHORTCUT_LANE": ("shortcut_lane", "s"),
+    _ENV = {"SFK_FUSE_BNB": ("fuse_bn_bwd", "1"), "SFK_TAIL_DUAL": ("tail_dual", "!0"),
             "SFK_WGRAD_LANES": ("wgrad_lanes", "i"), "SFK_RELU_BITS": ("relu_bits", "!0"), "SFK_RELU_OUT": ("relu_out_mask", "!0"),
             "SFK_WGWS": ("deterministic_wgrad", "1"), "SFK_TAIL": ("fuse_tail", "!0"), "SFK_TAIL_MINC": ("tail_min_c", "i"),
             "SFK_TAIL_MAXC": ("tail_max_c", "i"), "SFK_STEM_TAIL": ("fuse_stem_tail", "!0"), "SFK_TAIL_DG": ("fuse_tail_dg", "!0"),
-            "SFK_TAIL_RLANE": ("tail_r_lane", "i"), "SFK_SPLIT_REFRESH": ("split_refresh", "!0"), "SFK_REFRESH_BEHIND": ("refresh_behind_stems", "!0"),
+            "SFK_SPLIT_REFRESH": ("split_refresh", "!0"), "SFK_REFRESH_BEHIND": ("refresh_behind_stems", "!0"),
             "SFK_SPLIT_ADAM": ("split_adam", "!0"), "SFK_TRUNK_PRIO": ("trunk_priority", "!0"),
-            "SFK_WGRAD_TRUNK": ("mfma_wgrad_trunk", "1"), "SFK_DIST_ONE_LANE": ("dist_wgrad_one_lane", "!0"),
-            "SFK_LANE_CUS": ("lane_cus", "s"), "SFK_FUSE_FIN": ("fuse_finalize", "!0"),
-            "SFK_FUSE_FIN_MAXC": ("fuse_finalize_max_c", "i")}
+            "SFK_DIST_ONE_LANE": ("dist_wgrad_one_lane", "!0")}
 
     @classmethod
     def from_env(cls, env=None) -> "EngineOptions":
@@ -184,33 +173,13 @@ class EngineOptions:
             if var not in env:
                 continue
             v = env[var]
-            setattr(o, field, v == "1" if kind == "1" else v != "0" if kind == "!0" else int(v) if kind == "i" else v)
+            setattr(o, field, v == "1" if kind == "1" else v != "0" if kind == "!0" else int(v))
         return o
 
     def non_default(self) -> Dict[str, object]:
         d = EngineOptions()
         return {f.name: getattr(self, f.name) for f in dataclasses.fields(self)
                 if not f.name.startswith("_") and getattr(self, f.name) != getattr(d, f.name)}
-
-
-def _masked_stream(device, spec: int):
-    """EXPERIMENT (EngineOptions.lane_cus): a HIP stream whose kernels may only use some CUs.  spec = ncu (the first ncu mask
-    bits) or -ncu (the LAST ncu bits); the runtime deals mask bits round-robin over the 8 XCDs, so any contiguous run of bits
-    is spread evenly.  Wrapped as a torch ExternalStream; lives as long as the process."""
-    import ctypes as C
-    total = torch.cuda.get_device_properties(device).multi_processor_count
-    n = min(abs(spec), total)
-    bits = range(n) if spec > 0 else range(total - n, total)
-    words = (C.c_uint32 * ((total + 31) // 32))()
-    for b in bits:
-        words[b // 32] |= 1 << (b % 32)
-    hip = C.CDLL("libamdhip64.so")            # the runtime torch already loaded (one instance per process)
-    st = C.c_void_p()
-    with torch.cuda.device(device):
-        rc = hip.hipExtStreamCreateWithCUMask(C.byref(st), C.c_uint32(len(words)), words)
-    if rc != 0 or not st.value:
-        raise RuntimeError(f"hipExtStreamCreateWithCUMask({spec}) failed: {rc}")
-    return torch.cuda.ExternalStream(st.value, device)
 
 
 class Engine:
@@ -227,20 +196,16 @@ class Engine:
         self._layers: Dict[str, _Layer] = {}
         self._bufs: Dict[str, torch.Tensor] = {}
         self._plans: Dict[tuple, Plan] = {}
-        self._pending_fin: Dict[int, tuple] = {}     # deferred BatchNorm finalizes by id(scale buffer): consumed by the next _apply
         self._build_params(seed)
         self.max_parts = _max_parts() if getattr(self.be, "name", "") == "hip" else 1024
         self.two_streams = True           # slow / fast pathway on two HIP streams (see OpList)
         # every switch comes from the options object (defaults = the measured best); nothing here reads the environment
         o = self.options = options if options is not None else EngineOptions()
-        assert o.shortcut_lane in ("f", "b", "1", "0") and o.tail_r_lane in (0, 2, 4) and o.wgrad_lanes in (0, 1, 2)
+        assert o.wgrad_lanes in (0, 1, 2)
         # BatchNorm-backward reduce folded into the dgrad epilogues (sfk_conv_desc.bnb): removes 3.3 ms of reduce kernels,
         # adds 3.0 ms to the conv class -- measured neutral on the step (877 vs 879 clips/s), so it is opt-in
         self.fuse_bn_bwd = o.fuse_bn_bwd
         self.tail_dual = o.tail_dual
-        # projection shortcuts beside branch2 on the pathway's filter-gradient lane: f = forward (default: that lane is idle in the
-        # forward, +0.5 %), b = backward too (the lane carries the filter gradients there: -0.7 %), 1 = both, 0 = neither
-        self.shortcut_lane_f, self.shortcut_lane_b = o.shortcut_lane in ("1", "f"), o.shortcut_lane in ("1", "b")
         # diagnostic: kernel classes (OpList meta kinds) that the lane scheduler SKIPS -- what does the step time owe to one
         # class?  (bench.py --ablate; results are garbage with anything skipped)
         self._ablate_kinds = frozenset(o.ablate_kinds)
@@ -266,13 +231,10 @@ class Engine:
         self.tail_max_c = o.tail_max_c
         # the stems' BatchNorm -> ReLU -> MaxPool as one forward pass and a two-pass backward (sfk_bn_maxpool_*)
         self.fuse_stem_tail = (o.fuse_stem_tail and hasattr(self.be, "bn_maxpool_fwd") and self.be.bn_maxpool_supported(3, 2, 1))
-        # R = dz^T a beside the first dgrad pass (_tail_bwd): 0 = on the pathway's lane (default), 2 = on its filter-gradient lane
-        # (neutral), 4 = on lanes of its own (an experiment: 948 clips/s with the default 4 hardware queues, 719 with 8)
         self.fuse_tail_dg = o.fuse_tail_dg                                  # R and the first dgrad pass in one kernel (_tail_bwd)
-        self.tail_r_lane = o.tail_r_lane
         # 0 slow pathway / trunk, 1 fast pathway, 2 / 3 filter gradients of the slow / fast pathway.  Not more: a process gets
         # 4 hardware queues (GPU_MAX_HW_QUEUES), streams beyond that share one and serialise (6 lanes: 948 vs 1033 clips/s)
-        self.NLANES = 6 if o.tail_r_lane == 4 else 4
+        self.NLANES = 4
         self._side = None
         self.drop_seed = torch.full((1,), 0x5EED0000 + seed, dtype=torch.int64, device=self.device)
 
@@ -507,9 +469,8 @@ class Engine:
                       bytes=float(esz * (x.pixels * L.eg.cin + rows * L.eg.cout + L.w_numel)))
         return stats, mt
 
-    def _unit_fwd(self, pl: Plan, L: _Layer, x: FMap, tag: str, train: bool, n: int, defer: bool = False):
-        """conv + BatchNorm coefficients.  returns (y, scale, shift, rec).  defer: the caller's next op is _apply(y, scale, shift,
-        ...) on the same lane -- the finalize then rides that launch as its prologue (EngineOptions.fuse_finalize)"""
+    def _unit_fwd(self, pl: Plan, L: _Layer, x: FMap, tag: str, train: bool, n: int):
+        """conv + BatchNorm coefficients.  returns (y, scale, shift, rec)"""
         od = L.eg.out_dims((x.t, x.h, x.w))
         y = self._fmap(f"y.{tag}", n, od[0], od[1], od[2], L.c)
         scale = self._buf(f"scale.{tag}", L.c, torch.float32)
@@ -520,13 +481,9 @@ class Engine:
             stats, mt = self._conv(pl, L, x, y, f"stats.{tag}")
             mean = self._buf(f"mean.{tag}", L.c, torch.float32)
             invstd = self._buf(f"invstd.{tag}", L.c, torch.float32)
-            if defer and self.options.fuse_finalize and L.c <= min(512, self.options.fuse_finalize_max_c) and hasattr(self.be, "bn_finalize_apply"):
-                self._pending_fin[id(scale)] = (stats, mt, y.pixels, gamma, beta, self.spec.bn_eps, self.spec.bn_momentum, L.rm, L.rv,
-                                                L.nbt, mean, invstd, self._fold_ws(tag, L.c), self._buf(f"finsync.{tag}", 2144, torch.int32))
-            else:
-                pl.fwd.append(self.be.bn_finalize(stats, mt, L.c, y.pixels, gamma, beta, self.spec.bn_eps,
-                                                  self.spec.bn_momentum, L.rm, L.rv, L.nbt, mean, invstd, scale, shift,
-                                                  self._fold_ws(tag, L.c)), kind="bn_finalize")
+            pl.fwd.append(self.be.bn_finalize(stats, mt, L.c, y.pixels, gamma, beta, self.spec.bn_eps,
+                                              self.spec.bn_momentum, L.rm, L.rv, L.nbt, mean, invstd, scale, shift,
+                                              self._fold_ws(tag, L.c)), kind="bn_finalize")
             rec = _UnitRec(L, x, y, mean, invstd, scale, shift)
         else:
             self._conv(pl, L, x, y, None)
@@ -535,12 +492,7 @@ class Engine:
 
     def _apply(self, pl: Plan, y: FMap, scale, shift, res, res_scale, res_shift, relu: bool, out: FMap, bits=None):
         esz = 2 if self.dtype == torch.bfloat16 else 4
-        fin = self._pending_fin.pop(id(scale), None)
-        if fin is not None:     # this BatchNorm's finalize was deferred to here (_unit_fwd(defer=True)): one launch for both
-            run = self.be.bn_finalize_apply(*fin, y, scale, shift, res, res_scale, res_shift, relu, out, relu_bits=bits)
-        else:
-            run = self.be.bn_apply(y, scale, shift, res, res_scale, res_shift, relu, out, relu_bits=bits)
-        pl.fwd.append(run,
+        pl.fwd.append(self.be.bn_apply(y, scale, shift, res, res_scale, res_shift, relu, out, relu_bits=bits),
                       kind="bn_apply",
                       bytes=float(y.pixels * y.c * esz * (2 + (1 if res is not None else 0))
                                   + (y.pixels * y.c // self.kvec if bits is not None else 0)))
@@ -568,18 +520,6 @@ class Engine:
             pl.bwd.append(run, kind="bn_bwd_reduce", layer=L.cb.norm_key,
                           bytes=el * (2 + (1 if mask_src is not None else 0) + (1 if dz_inplace else 0))
                           + (rec.y.pixels * L.c // self.kvec if bits is not None else 0))
-        if self.options.fuse_finalize and L.c <= min(512, self.options.fuse_finalize_max_c) and hasattr(self.be, "bn_bwd_finalize_apply"):
-            # the finalize rides the apply launch as its prologue (sfk_bn_bwd_finalize_apply): dgamma / dbeta are complete behind it
-            fin = (parts, np_, rec.y.pixels, self._pslice(L.g_off, L.c), self._gslice(L.g_off, L.c), self._gslice(L.b_off, L.c), coef,
-                   self._fold_ws(tag, L.c), self._buf(f"bfinsync.{tag}", 2144, torch.int32))
-            if dz_inplace:   # the mask is already applied to da
-                run, nb = self.be.bn_bwd_finalize_apply(*fin, da, rec.y, None, rec.mean, rec.invstd, rec.scale, rec.shift, False, dy), 3
-            else:
-                run = self.be.bn_bwd_finalize_apply(*fin, da, rec.y, mask_src, rec.mean, rec.invstd, rec.scale, rec.shift, relu, dy)
-                nb = 3 + (1 if mask_src is not None else 0)
-            pl.bwd.append(run, kind="bn_bwd_apply", layer=L.cb.norm_key, bytes=el * nb)
-            pl.grad_marks.append((len(pl.bwd), (L.g_off, L.b_off + round_up(L.c, self.vec) - L.g_off)))
-            return
         pl.bwd.append(self.be.bn_bwd_finalize(parts, np_, L.c, rec.y.pixels, self._pslice(L.g_off, L.c), rec.invstd,
                                               self._gslice(L.g_off, L.c), self._gslice(L.b_off, L.c), coef,
                                               self._fold_ws(tag, L.c)), kind="bn_finalize")
@@ -605,11 +545,6 @@ class Engine:
         home = pl.bwd.cur_lane
         wants = hasattr(self.be, "conv_wgrad_wants_workspace") and self.be.conv_wgrad_wants_workspace(wp)
         wl = (2 if self.wgrad_one_lane else home + 2) if self.wgrad_lanes else home
-        # the MFMA-bound layers' 256 x 256 tiles own every CU they run on (one workgroup per CU): options.mfma_wgrad_trunk keeps
-        # them on the pathway's own lane, directly behind the data gradient that read the same dY (still in L2 / MALL), instead of
-        # beside the trunk's kernels
-        if wants and self.options.mfma_wgrad_trunk:
-            wl = home
         if wl != home:
             pl.bwd.sync(wl, home)
             pl.bwd.cur_lane = wl
@@ -800,7 +735,7 @@ class Engine:
     # ---- lateral fusion: conv over the fast pathway -> BN -> ReLU -> channel slice of the slow buffer
     def _fusion_fwd(self, pl, bi: int, xf: FMap, out_slice: FMap, train: bool):
         L = self._layers[self.wiring.fusions[bi].conv_key]
-        y, scale, shift, rec = self._unit_fwd(pl, L, xf, f"fuse{bi}", train, xf.n, defer=True)
+        y, scale, shift, rec = self._unit_fwd(pl, L, xf, f"fuse{bi}", train, xf.n)
         assert (y.t, y.h, y.w, y.c) == (out_slice.t, out_slice.h, out_slice.w, out_slice.c), \
             "lateral fusion: fast pathway does not line up with the slow pathway (T_fast / stride != T_slow?)"
         self._apply(pl, y, scale, shift, None, None, None, True, out_slice)
@@ -904,12 +839,9 @@ class Engine:
         wp = WgradPass(ab, d_out, (1, 1, 1), self.TAP0, r, 1, c4, C)
         meta = dict(kind="conv_wgrad", layer=Lc.cb.conv_key, cout=C, flops=2.0 * d_out.pixels * C * c4,
                     bytes=float(esz * (ab.pixels * c4 + d_out.pixels * C) + 4 * C * c4))
-        # R = dz^T a_b may run BESIDE the first data-gradient pass dz (A W), whose filter the forward left (A = gamma * invstd
-        # needs no gradient statistics): tail_r_lane puts it on the pathway's filter-gradient lane and the pathway waits for
-        # it only before the small algebra that needs it.  Measured: see DESIGN.md section 4b (the lane carries a backlog of
-        # earlier filter gradients; lanes of its own exceed the 4 hardware queues a process gets and serialise).
-        # ... and where the filter-gradient tile has idle waves (slow res2: 256 x 64) those compute that first pass from the dz
-        # rows the tile already holds: dz is read ONCE for R and dz (A W) (sfk_wgrad_desc.dg_w / dg_y)
+        # R = dz^T a_b runs on the pathway's lane (beside it on another lane was neutral or slower: DESIGN.md section 4b).
+        # Where the filter-gradient tile has idle waves (slow res2: 256 x 64) those compute the first data-gradient pass
+        # dz (A W) from the dz rows the tile already holds: dz is read ONCE for both (sfk_wgrad_desc.dg_w / dg_y)
         rows = (d_out.t, d_out.h, d_out.w)
         wp.dg_w, wp.dg_y = tail["wd"], dab
         fused_dg = self.fuse_tail_dg and hasattr(self.be, "conv_wgrad_dg_supported") and self.be.conv_wgrad_dg_supported(wp)
@@ -917,26 +849,18 @@ class Engine:
             meta = dict(meta, flops=2.0 * meta["flops"], bytes=meta["bytes"] + float(esz * d_out.pixels * c4))
         else:
             wp.dg_w = wp.dg_y = None
-        home = pl.bwd.cur_lane
-        rl = home + self.tail_r_lane if (self.wgrad_lanes and self.tail_r_lane and not fused_dg) else home
-        if rl != home:
-            pl.bwd.sync(rl, home)
-            pl.bwd.cur_lane = rl
         if self.deterministic_wgrad:
-            self._ws_wgrad(pl.bwd, wp, f"b{rl}", **meta)
+            self._ws_wgrad(pl.bwd, wp, f"b{pl.bwd.cur_lane}", **meta)
         else:
             pl.bwd.append(self.be.conv_wgrad(wp), **meta)
-        pl.bwd.cur_lane = home
         # the narrowest maps (fast res2 / res3: 8 / 16 channels): both passes in ONE streaming kernel after the small algebra
         # (sfk_conv_pw_dual: da written once; two MFMA tiles that are all epilogue become one pass at HBM speed)
-        dual = (not fused_dg and rl == home and self.tail_dual and hasattr(self.be, "conv_pw_dual_supported")
+        dual = (not fused_dg and self.tail_dual and hasattr(self.be, "conv_pw_dual_supported")
                 and self.be.conv_pw_dual_supported(d_out, ab, dab))
         if not fused_dg and not dual:
             pl.bwd.append(self.be.conv_igemm(ConvPass(d_out, dab, rows, (1, 1, 1), (1, 1, 1), (0, 0, 0), self.TAP0, tail["wd"], 1, C, c4)),
                           kind="conv_dgrad", layer=Lc.cb.conv_key, cout=c4, flops=2.0 * d_out.pixels * C * c4,
                           bytes=float(esz * (d_out.pixels * C + d_out.pixels * c4 + Lc.w_numel)))
-        if rl != home:
-            pl.bwd.sync(home, rl)
         bias = self._buf(f"tailbias.{tag}", c4, torch.float32)
         coef = self._buf(f"tailcoef.{tag}", C * 4, torch.float32)
         m = self._buf(f"tailM.{tag}", c4 * c4)             # W^T diag(B) W, the filter of the second data-gradient pass
@@ -968,16 +892,16 @@ class Engine:
             # four-lane training schedule it runs on the pathway's filter-gradient lane (idle in the forward) instead of in
             # front of conv_a on the pathway's own chain -- the trunk is the step's critical path
             home = pl.fwd.cur_lane
-            if self.shortcut_lane_f and train and self.two_streams and self.wgrad_lanes and self.device.type == "cuda":
+            if train and self.two_streams and self.wgrad_lanes and self.device.type == "cuda":
                 sl = home + 2
                 pl.fwd.sync(sl, home)
                 pl.fwd.cur_lane = sl
             y1, s1, h1, rec1 = self._unit_fwd(pl, L1, x, f"{tag}.b1", train, n)
             pl.fwd.cur_lane = home
-        ya, sa, ha, reca = self._unit_fwd(pl, La, x, f"{tag}.a", train, n, defer=True)
+        ya, sa, ha, reca = self._unit_fwd(pl, La, x, f"{tag}.a", train, n)
         aa = self._fmap(f"a.{tag}.a", n, ya.t, ya.h, ya.w, La.c)
         self._apply(pl, ya, sa, ha, None, None, None, True, aa)
-        yb, sb, hb, recb = self._unit_fwd(pl, Lb, aa, f"{tag}.b", train, n, defer=not self._tail_ok(Lc))
+        yb, sb, hb, recb = self._unit_fwd(pl, Lb, aa, f"{tag}.b", train, n)
         if sl is not None:
             pl.fwd.sync(pl.fwd.cur_lane, sl)          # the shortcut map and its coefficients are ready
         if self._tail_ok(Lc):
@@ -987,7 +911,7 @@ class Engine:
             return (blk, tag, x, out, rec1, reca, recb, tail, bits)
         ab = self._fmap(f"a.{tag}.b", n, yb.t, yb.h, yb.w, Lb.c)
         self._apply(pl, yb, sb, hb, None, None, None, True, ab)
-        yc, sc, hc, recc = self._unit_fwd(pl, Lc, ab, f"{tag}.c", train, n, defer=True)
+        yc, sc, hc, recc = self._unit_fwd(pl, Lc, ab, f"{tag}.c", train, n)
         assert (yc.t, yc.h, yc.w, yc.c) == (out.t, out.h, out.w, out.c)
         # the block output's ReLU mask, 1 bit per element, for the backward pass (which otherwise re-reads `out`)
         bits = self._buf(f"relubits.{tag}", out.pixels * (out.c // self.kvec), torch.uint8) if (train and self.relu_bits) else None
@@ -1030,20 +954,6 @@ class Engine:
                 self._bn_bwd(pl, recc, d_out, f"{tag}.c", True, out, True, dyc, reduced=reduced_c, bits=bits)
             self._wgrad(pl, recc, dyc)
             red_b = self._dgrad(pl, recc, dyc, dab, accumulate=False, fuse=(recb, None, True, f"{tag}.b"))
-        # projection shortcut: its BatchNorm backward only needs dz (final by now: the conv_c part above masked / consumed it)
-        # and only meets branch2 at the last data-gradient pass -- on the four-lane schedule it runs on the pathway's
-        # filter-gradient lane into a buffer of its own instead of in place at the end of the pathway's chain
-        sc_lane, dy1 = None, None
-        if rec1 is not None and self.shortcut_lane_b and self.two_streams and self.wgrad_lanes and not self.wgrad_one_lane \
-                and self.device.type == "cuda":
-            home = pl.bwd.cur_lane
-            sc_lane = home + 2
-            dy1 = self._fmap(f"dy.{tag}.b1", n, d_out.t, d_out.h, d_out.w, d_out.c)
-            pl.bwd.sync(sc_lane, home)
-            pl.bwd.cur_lane = sc_lane
-            self._bn_bwd(pl, rec1, d_out, f"{tag}.b1", False, None, False, dy1)
-            pl.bwd.cur_lane = home
-            self._wgrad(pl, rec1, dy1)
         self._bn_bwd(pl, recb, dab, f"{tag}.b", True, None, False, dab, reduced=red_b)
         self._wgrad(pl, recb, dab)
         daa = self._fmap(f"da.{tag}.a", n, reca.y.t, reca.y.h, reca.y.w, reca.y.c)
@@ -1063,13 +973,10 @@ class Engine:
             return d_out, red_prev
         dx = self._fmap(f"dx.{tag}", n, x.t, x.h, x.w, x.c)
         self._dgrad(pl, reca, daa, dx, accumulate=False)
-        if sc_lane is not None:
-            pl.bwd.sync(pl.bwd.cur_lane, sc_lane)      # the shortcut's BatchNorm backward ran beside branch2 (above)
-        else:
-            self._bn_bwd(pl, rec1, d_out, f"{tag}.b1", False, None, False, d_out)   # d_out already holds dz
-            self._wgrad(pl, rec1, d_out)
-            dy1 = d_out
-        self._dgrad(pl, rec1, dy1, dx, accumulate=True)
+        # projection shortcut: its BatchNorm backward only needs dz (d_out: the conv_c part above masked / consumed it)
+        self._bn_bwd(pl, rec1, d_out, f"{tag}.b1", False, None, False, d_out)
+        self._wgrad(pl, rec1, d_out)
+        self._dgrad(pl, rec1, d_out, dx, accumulate=True)
         return dx, None
 
     def _stage_bwd(self, pl, brecs, d: FMap) -> FMap:
@@ -1305,7 +1212,6 @@ class Engine:
             if len(self._plans) >= 6:
                 self._plans.clear()
             pl = self._build_plan(x_slow, x_fast, slow_t_index, train)
-            assert not self._pending_fin, "a deferred BatchNorm finalize was never consumed by an _apply"
             pl.key = key
             Engine._plan_serial += 1
             pl.serial = Engine._plan_serial          # never reused (id() of a dropped plan can be)
@@ -1342,9 +1248,7 @@ class Engine:
         if not self.two_streams:
             return [main]
         if self._side is None:
-            cus = [int(v) for v in self.options.lane_cus.split(",")] if self.options.lane_cus else []
-            self._side = [_masked_stream(self.device, cus[i]) if i < len(cus) and cus[i] > 0 else torch.cuda.Stream(self.device)
-                          for i in range(self.NLANES - 1)]
+            self._side = [torch.cuda.Stream(self.device) for _ in range(self.NLANES - 1)]
         return [main] + self._side
 
     def _run_lanes(self, ops: "OpList", begin: int = 0, end: Optional[int] = None):
