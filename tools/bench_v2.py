@@ -1,7 +1,10 @@
 """The v2 part-box trainer at its geometry (N 10, T 20, 240x320 frames, S 192, bf16): sfk_roi_resize time, bytes and
 fraction of HBM peak; a host-fed v2 training step from uint8 frames + boxes against the same step from the float
 pre-resized batch (ms, peak memory); and the host time the loader no longer spends (one clip's F.interpolate on one thread).
-Prints one JSON line.  Usage: python tools/bench_v2.py [--steps 10] [--warmup 3]"""
+--jitter adds sfk_color_jitter (include/sfk_aug.h): its two launches at the v2 and the HTAH (N 55, 21 channels) geometry with
+the bytes they must move (three planes read twice and written once) and the effective bandwidth, the same call for clips
+without a contrast op (pass 1 exits at once: what is left is pass 2), and the uint8 step with the batch's 'jitter' entry.
+Prints one JSON line.  Usage: python tools/bench_v2.py [--steps 10] [--warmup 3] [--jitter]"""
 import argparse
 import json
 import os
@@ -37,6 +40,7 @@ def main():
     ap.add_argument("--n", type=int, default=10)
     ap.add_argument("--t", type=int, default=20)
     ap.add_argument("--size", type=int, default=192)
+    ap.add_argument("--jitter", action="store_true")
     args = ap.parse_args()
     from video_classification_amd import gesture_v2 as v2
     from video_classification_amd._lib import HipBackend
@@ -65,6 +69,29 @@ def main():
             res[key + "_MB"] = round(nbytes / 1e6, 1)
             res[key + "_hbm_frac"] = round(nbytes / (ms * 1e-3) / HBM_PEAK, 3)
 
+    # 1b. the colour jitter alone, in place on the three colour planes of a resident float clip
+    if args.jitter:
+        from video_classification_amd.input_pipeline import draw_color_jitter
+        st = torch.cuda.current_stream().cuda_stream
+        for tag, nn, ch, dtype, bgr, mean, std in (("v2_f32", n, 7, torch.float32, False, 0.0, 1.0),
+                                                   ("v2_bf16", n, 7, torch.bfloat16, False, 0.0, 1.0),
+                                                   ("htah_f32", 55, 21, torch.float32, True, 0.45, 0.225)):
+            clip = ((torch.rand(nn, t, ch, s, s, device=dev) - mean) / std).to(dtype)
+            ws = torch.empty(be.color_jitter_workspace_bytes(nn, t, s, s) // 4, device=dev)
+            prm = draw_color_jitter(nn, generator=g)
+            nbytes = 3 * 3 * nn * t * s * s * clip.element_size()
+            for sub, p in (("", prm), ("_nocontrast", torch.where(prm == 1.0, torch.tensor(-1.0), prm))):
+                p = p.clone()
+                p[:, 4:] = prm[:, 4:]
+                run = be.color_jitter(clip, p.to(dev), ws, 0, bgr, mean, std)
+                ms = cuda_ms(lambda: run(st), 50, 5)
+                key = f"jitter_{tag}{sub}"
+                res[key + "_us"] = round(ms * 1e3, 1)
+                if not sub:
+                    res[key + "_MB"] = round(nbytes / 1e6, 1)
+                    res[key + "_GBps"] = round(nbytes / (ms * 1e-3) / 1e9, 1)
+            del clip
+
     # 2. a host-fed v2 step: uint8 frames + boxes against the float batch resized on the host
     cfg = get_cfg()
     cfg.CHALEARN.BATCH_SIZE, cfg.CHALEARN.CLIP_LEN, cfg.MODEL.INPUT_SIZE, cfg.MODEL.DTYPE = n, t, s, "bf16"
@@ -80,7 +107,10 @@ def main():
     fb = {"rgb": X[:, :, 0:3].contiguous().pin_memory(), "uv": X[:, :, 3:5].contiguous().pin_memory(),
           "flow": X[:, :, 5:7].contiguous().pin_memory(), "label": labels}
     model.train()
-    for tag, batch in (("uint8", ub), ("float", fb)):
+    runs = [("uint8", ub), ("float", fb)]
+    if args.jitter:
+        runs.append(("uint8_jitter", dict(ub, jitter=draw_color_jitter(n, generator=g).pin_memory())))
+    for tag, batch in runs:
         def one():
             x, y = mm.prepare_data(batch)
             step(x[0], x[1], y)

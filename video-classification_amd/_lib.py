@@ -215,6 +215,15 @@ class _RoiDesc(C.Structure):
                 ("dh", C.c_int64), ("c_off", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class _JitterDesc(C.Structure):
+    """include/sfk_aug.h sfk_jitter_desc: element (n, t, c, y, x) of the three colour planes at
+    x[n*sn + t*st + (c_off + c)*sc + y*sh + x], jittered in place with the per-clip params[n][8]"""
+    _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_int32), ("x", C.c_void_p), ("sn", C.c_int64), ("st", C.c_int64),
+                ("sc", C.c_int64), ("sh", C.c_int64), ("n", C.c_int32), ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("c_off", C.c_int32), ("bgr", C.c_int32), ("mean", C.c_float), ("std", C.c_float), ("params", C.c_void_p),
+                ("workspace", C.c_void_p)]
+
+
 class _Tuning(C.Structure):
     """sfk_tuning: the write-once kernel-selection table of sfk_init (defaults = the measured best)."""
     _fields_ = [("struct_size", C.c_uint32), ("igemm_short_k", C.c_int32), ("igemm_small_k", C.c_int32), ("igemm_wide_store", C.c_int32),
@@ -319,7 +328,15 @@ SIGNATURES_V2 = {
     "sfk_roi_resize": [C.POINTER(_RoiDesc), _PV],
     "sfk_sgd": [_PF, _PF, _PF, _I64, C.c_float, C.c_float, C.c_float, _I32, C.c_float, _PV, _PV, _I32, _PV],
 }
-_RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64}
+# include/sfk_aug.h: the device-side ColorJitter of the training clips, same library, its own header and version
+AUG_ABI_VERSION = 1        # include/sfk_aug.h SFK_AUG_ABI_VERSION
+SIGNATURES_AUG = {
+    "sfk_aug_abi_version": [],
+    "sfk_color_jitter_workspace_bytes": [_I32, _I32, _I32, _I32],
+    "sfk_color_jitter": [C.POINTER(_JitterDesc), _PV],
+}
+_RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
+            "sfk_color_jitter_workspace_bytes": C.c_int64}
 
 
 def new_conv_desc() -> "_ConvDesc":
@@ -353,6 +370,12 @@ def new_roi_desc() -> "_RoiDesc":
     return d
 
 
+def new_jitter_desc() -> "_JitterDesc":
+    d = _JitterDesc()
+    d.struct_size = C.sizeof(_JitterDesc)
+    return d
+
+
 def new_tuning() -> "_Tuning":
     t = _Tuning()
     t.struct_size = C.sizeof(_Tuning)
@@ -370,7 +393,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"{path} not found: build it with `python video-classification_amd/build.py` "
                        "(there is no CPU or PyTorch fallback for the SlowFast path)")
     lib = C.CDLL(path)
-    for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2):
+    for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -383,6 +406,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk u8stem ABI version mismatch: library {lib.sfk_u8stem_abi_version()}, binding {U8STEM_ABI_VERSION}")
     if lib.sfk_v2_abi_version() != V2_ABI_VERSION:
         raise SfkError(f"libsfk v2 ABI version mismatch: library {lib.sfk_v2_abi_version()}, binding {V2_ABI_VERSION}")
+    if lib.sfk_aug_abi_version() != AUG_ABI_VERSION:
+        raise SfkError(f"libsfk aug ABI version mismatch: library {lib.sfk_aug_abi_version()}, binding {AUG_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -856,6 +881,28 @@ class HipBackend:
         d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
         d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
         return self._plain("sfk_roi_resize", C.byref(d), keep=(d, src, lut, box, out, crop))
+
+    def color_jitter_workspace_bytes(self, n: int, t: int, h: int, w: int) -> int:
+        """bytes of fp32 scratch sfk_color_jitter needs for n clips of t frames of h x w (include/sfk_aug.h)"""
+        r = int(self.lib.sfk_color_jitter_workspace_bytes(n, t, h, w))
+        if r < 0:
+            _check(r, "sfk_color_jitter_workspace_bytes")
+        return r
+
+    def color_jitter(self, clip, params, workspace, c_off: int = 0, bgr: bool = False, mean: float = 0.0, std: float = 1.0):
+        """sfk_color_jitter (include/sfk_aug.h): clip (N,T,C,H,W) f32|bf16 with unit W stride, channels c_off .. c_off+2
+        jittered IN PLACE; params (N,8) float32 = order[4], b, c, s, h on the device, read when the launch runs; workspace:
+        float32, color_jitter_workspace_bytes(N, T, H, W) bytes; stored value s <-> image value s*std + mean."""
+        assert clip.dim() == 5 and clip.stride(4) == 1 and 0 <= c_off and c_off + 3 <= clip.shape[2]
+        n, t, _, h, w = clip.shape
+        assert params.dtype == torch.float32 and params.is_contiguous() and tuple(params.shape) == (n, 8)
+        assert workspace.dtype == torch.float32 and workspace.numel() * 4 >= self.color_jitter_workspace_bytes(n, t, h, w)
+        d = new_jitter_desc()
+        d.dtype, d.x, d.params, d.workspace = _DT[clip.dtype], clip.data_ptr(), params.data_ptr(), workspace.data_ptr()
+        d.sn, d.st, d.sc, d.sh = clip.stride()[:4]
+        d.n, d.t, d.h, d.w = n, t, h, w
+        d.c_off, d.bgr, d.mean, d.std = c_off, 1 if bgr else 0, mean, std
+        return self._plain("sfk_color_jitter", C.byref(d), keep=(d, clip, params, workspace))
 
     def filter_transpose(self, src, dst, cout, wtaps, cin):
         return self._plain("sfk_filter_transpose", _ptr(src), _DT[src.dtype], _ptr(dst), _DT[dst.dtype], cout, wtaps,

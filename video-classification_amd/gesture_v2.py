@@ -139,6 +139,8 @@ class ChalearnGestureFrames(torch.utils.data.Dataset):
         self.compose = PartCompose()
         self.read_video = read_video or decord_read_video
         self.rng = random
+        # MODEL.COLOR_JITTER: the train set's random clips carry their ColorJitter draws (input_pipeline.draw_color_jitter)
+        self.jitter = _train.jitter_ranges(cfg) if name_of_set == "train" else None
 
     def __len__(self):
         return len(self.label_list)
@@ -160,7 +162,11 @@ class ChalearnGestureFrames(torch.utils.data.Dataset):
         x = torch.cat([rgb, uv, flow], dim=1)                          # T, 7, H, W
         _, _, h, w = x.shape
         box = self.clip_box(boxes, clip_indices, h, w)
-        return {"frames_u8": x.permute(0, 2, 3, 1).contiguous(), "box": box, "label": label - 1}
+        item = {"frames_u8": x.permute(0, 2, 3, 1).contiguous(), "box": box, "label": label - 1}
+        if self.jitter is not None and self.sampling == "random":
+            from .input_pipeline import draw_color_jitter
+            item["jitter"] = draw_color_jitter(1, *self.jitter)[0]
+        return item
 
     def __getitem__(self, index):
         rgb_path, _depth_path, label = self.label_list[index]
@@ -197,7 +203,12 @@ class SyntheticGesture(torch.utils.data.Dataset):
         y1 = int(torch.randint(0, self.h - self.min_box, (1,), generator=g))
         x2 = int(torch.randint(x1 + self.min_box, self.w + 1, (1,), generator=g))
         y2 = int(torch.randint(y1 + self.min_box, self.h + 1, (1,), generator=g))
-        return {"frames_u8": frames, "box": torch.tensor([x1, y1, x2, y2], dtype=torch.int32), "label": self.labels[i]}
+        item = {"frames_u8": frames, "box": torch.tensor([x1, y1, x2, y2], dtype=torch.int32), "label": self.labels[i]}
+        ranges = _train.jitter_ranges(self.cfg) if self.name == "train" else None
+        if ranges is not None:
+            from .input_pipeline import draw_color_jitter
+            item["jitter"] = draw_color_jitter(1, *ranges, generator=g)[0]
+        return item
 
     def __getitem__(self, i):
         if self.name == "train":
@@ -214,6 +225,7 @@ class ModelManager(_train.ModelManager):
         self._pre = None
         self._lut = None
         self._roi = None
+        self._jit = None
         self.arch = "ref"
         self.init_model = self._init_v2_model
         self.prepare_data = self._prepare_v2_data
@@ -240,13 +252,21 @@ class ModelManager(_train.ModelManager):
     def _prepare_v2_data(self, batch):
         """-> [slow (N, 5, T, S, S), fast (N, 2, T, S, S)], labels.  The uint8 batch {'frames_u8', 'box'[, 'crop']} is
         resized on the device into one (N, T, 7, S, S) tensor whose channel slices are the two pathways (no copy); the
-        float batch {'rgb', 'uv', 'flow'} is the reference's permute + cat (:761-769)."""
+        float batch {'rgb', 'uv', 'flow'} is the reference's permute + cat (:761-769).  An optional 'jitter' (N, 8) entry
+        (input_pipeline.draw_color_jitter) applies ColorJitter to the R, G, B planes on the device: after the resize and
+        the crop of a uint8 batch ("Optional Augment (crop&pad, color jitter)", :608-611), to the device copy of 'rgb' of
+        a float batch; the values are image values in [0, 1] (mean 0, std 1)."""
         y = self._h2d(batch["label"])
         if "frames_u8" in batch:
             x = self.roi_resize()(batch["frames_u8"], batch["box"], batch.get("crop"))
+            if "jitter" in batch:
+                self.color_jitter()(x, batch["jitter"])
             x = torch.permute(x, [0, 2, 1, 3, 4])
             return [x[:, 0:5], x[:, 5:7]], y
-        rgb, uv, flow = (torch.permute(self._h2d(batch[k]), [0, 2, 1, 3, 4]) for k in ("rgb", "uv", "flow"))
+        rgb, uv, flow = (self._h2d(batch[k]) for k in ("rgb", "uv", "flow"))
+        if "jitter" in batch:
+            rgb = self.color_jitter()(self._own(rgb, batch["rgb"]), batch["jitter"])
+        rgb, uv, flow = (torch.permute(t, [0, 2, 1, 3, 4]) for t in (rgb, uv, flow))
         return [torch.cat([rgb, uv], dim=1), flow], y
 
 

@@ -41,6 +41,67 @@ def draw_crop_offsets(n: int, padding: int, generator: Optional[torch.Generator]
     return out
 
 
+def draw_color_jitter(n: int, brightness: float = 0.5, contrast: float = 0.3, saturation: float = 0.2, hue: float = 0.1,
+                      generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """(n, 8) float32 rows (order[4], b, c, s, h) for ``sfk_color_jitter``: per clip the draws of torchvision's
+    ColorJitter.get_params in its order -- ``torch.randperm(4)``, then one ``torch.empty(1).uniform_(lo, hi)`` each for
+    brightness, contrast and saturation from [max(0, 1 - v), 1 + v] and for hue from [-v, v] (the defaults are
+    dataset/chalearn_dataset.py:48-50's).  An op whose range is 0 takes no draw and its slot of the order becomes -1, as
+    torchvision skips an op whose factor is None; its factor column holds the identity."""
+    vals = (float(brightness), float(contrast), float(saturation), float(hue))
+    assert all(v >= 0 for v in vals) and vals[3] <= 0.5, vals
+    out = torch.empty(n, 8, dtype=torch.float32)
+    for i in range(n):
+        order = torch.randperm(4, generator=generator).to(torch.float32)
+        for op, v in enumerate(vals):
+            lo, hi = (-v, v) if op == 3 else (max(0.0, 1.0 - v), 1.0 + v)
+            if v == 0:
+                order[order == op] = -1.0
+                out[i, 4 + op] = 0.0 if op == 3 else 1.0
+            else:
+                out[i, 4 + op] = float(torch.empty(1).uniform_(lo, hi, generator=generator))
+        out[i, :4] = order
+    return out
+
+
+class ColorJitter:
+    """torchvision's ColorJitter (the reference's train-time colour augmentation, dataset/chalearn_dataset.py:48-50) on the
+    three colour planes of a float clip batch (N, T, C, H, W) that already lives on the device, IN PLACE, by
+    ``sfk_color_jitter`` (include/sfk_aug.h): two launches on the current stream, one parameter row per clip
+    (``draw_color_jitter``).  A stored value s stands for the image value s*std + mean; bgr tells the plane order.
+    torchvision is not installed here: the semantics are pinned to plain torch (tests/ref_jitter.py), torchvision itself
+    unpinned."""
+
+    def __init__(self, device="cuda", backend=None):
+        if backend is None:
+            from ._lib import HipBackend
+            backend = HipBackend()              # raises when libsfk.so is missing: no CPU path
+        self.be, self.device = backend, torch.device(device)
+        self._ws = {}                           # (n, t, h, w) -> the float32 workspace of that geometry
+
+    def _h2d(self, t: torch.Tensor) -> torch.Tensor:
+        if t.device.type == "cpu" and self.device.type == "cuda" and not t.is_pinned():
+            t = t.pin_memory()
+        return t.to(self.device, non_blocking=True)
+
+    def workspace(self, n: int, t: int, h: int, w: int) -> torch.Tensor:
+        key = (n, t, h, w)
+        if key not in self._ws:
+            nbytes = self.be.color_jitter_workspace_bytes(n, t, h, w)
+            self._ws[key] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
+        return self._ws[key]
+
+    def __call__(self, clip: torch.Tensor, params: torch.Tensor, c_off: int = 0, bgr: bool = False, mean: float = 0.0,
+                 std: float = 1.0) -> torch.Tensor:
+        assert clip.dim() == 5 and clip.stride(4) == 1 and clip.device.type == self.device.type
+        n, t, _, h, w = clip.shape
+        params = self._h2d(params.to(torch.float32)).contiguous()
+        assert tuple(params.shape) == (n, 8), tuple(params.shape)
+        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+        self.be.color_jitter(clip, params, self.workspace(n, t, h, w), c_off, bgr, mean, std)(stream)
+        return clip
+
+
 class DevicePreprocess:
     """uint8 frames (N, T, S, S, C) -> normalised clip batch (N, T, C, S, S) on the device."""
 

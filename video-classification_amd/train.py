@@ -168,6 +168,15 @@ class TrainStep:
         return self.loss
 
 
+def jitter_ranges(cfg):
+    """MODEL.COLOR_JITTER on: the (brightness, contrast, saturation, hue) ranges of MODEL.JITTER_*; off: None"""
+    m = cfg.MODEL
+    if not bool(m.get("COLOR_JITTER", False)):
+        return None
+    return (float(m.get("JITTER_BRIGHTNESS", 0.5)), float(m.get("JITTER_CONTRAST", 0.3)),
+            float(m.get("JITTER_SATURATION", 0.2)), float(m.get("JITTER_HUE", 0.1)))
+
+
 class ModelManager:
     """Name -> (init_model, prepare_data), as reference train.py:39-60.  'slowfast*' and 'res3d' (SURVEY.md section
     8f-4: hub slow_r50 with a 5-channel stem, train.py:79-89 / (deprecated)/train_3dresnet.py:47-51) run on this
@@ -180,6 +189,7 @@ class ModelManager:
         self.cfg, self.device, self.backend = cfg, device, backend
         self._pre = None
         self._lut = None
+        self._jit = None
         name = cfg.MODEL.NAME
         self.arch = str(cfg.MODEL.get("ARCH", "ref")).lower()
         if self.arch not in ("ref", "canonical8x8"):
@@ -219,15 +229,48 @@ class ModelManager:
         return bool(self.cfg.MODEL.get("U8_STEM", False))
 
     def _u8_float(self, batch) -> torch.Tensor:
-        """DevicePreprocess: (N,T,S,S,P) uint8 -> (N,T,P,S,S) float32 on the device"""
+        """DevicePreprocess: (N,T,S,S,P) uint8 -> (N,T,P,S,S) float32 on the device (then the batch's 'jitter', if any)"""
         if self._pre is None:
             from .input_pipeline import DevicePreprocess
             self._pre = DevicePreprocess(self.device, self.backend)
-        return self._pre(batch[self._u8_key(batch)], batch.get("crop"))
+        return self._jitter_v1(self._pre(batch[self._u8_key(batch)], batch.get("crop")), batch)
+
+    # ---- the device-side ColorJitter: a batch carrying 'jitter' (N,8), the draws of input_pipeline.draw_color_jitter
+    def color_jitter(self) -> "ColorJitter":
+        if self._jit is None:
+            from .input_pipeline import ColorJitter
+            self._jit = ColorJitter(self.device, self.backend)
+        return self._jit
+
+    @staticmethod
+    def _own(x: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
+        """x as a unit-stride tensor that is not the loader's own memory (the jitter works in place)"""
+        if x.stride(-1) != 1:
+            return x.contiguous()
+        return x.clone() if x.untyped_storage().data_ptr() == src.untyped_storage().data_ptr() else x
+
+    def _float_clip(self, batch) -> torch.Tensor:
+        """the float32 (N,T,21,S,S) loader batch on the device (then the batch's 'jitter', if any)"""
+        src = batch[self.cfg.MODEL.R3D_INPUT]
+        x = self._h2d(src)
+        return self._jitter_v1(self._own(x, src), batch) if "jitter" in batch else x
+
+    def _jitter_v1(self, x: torch.Tensor, batch) -> torch.Tensor:
+        """ColorJitter on channels 0..2 (B, G, R: cv2.imread order) of the normalised (N,T,21,S,S) clip, in place, when the
+        batch carries 'jitter'.  It runs where the reference's commented-out call sits (dataset/chalearn_dataset.py:87, after
+        the RandomCrop), but on IMAGE values: each stored value is de-normalised (s*0.225 + 0.45), jittered and normalised
+        again.  The crop's padding is stored 0, that is image value 0.45, and is jittered like any other pixel."""
+        if "jitter" not in batch:
+            return x
+        from .input_pipeline import MEAN, STD
+        return self.color_jitter()(x, batch["jitter"], 0, True, MEAN, STD)
 
     def _u8_clips(self, batch, channels) -> list:
         """U8Clips over the pinned-H2D frames and crop, one per (c0, c) channel range"""
         from .input_pipeline import normalize_lut, u8_pathways
+        if "jitter" in batch:
+            raise ValueError("MODEL.U8_STEM: true reads the uint8 frames in the stems, so there is no float clip for the "
+                             "batch's 'jitter' entry to work on; turn U8_STEM or MODEL.COLOR_JITTER off")
         if self._lut is None:
             self._lut = normalize_lut().to(self.device)
         frames = self._h2d(batch[self._u8_key(batch)])
@@ -265,7 +308,9 @@ class ModelManager:
                 if self._u8_stem():
                     return self._u8_clips(batch, [(0, 5)])[0], self._h2d(batch['label'])
                 return self._u8_float(batch)[:, :, :5], self._h2d(batch['label'])
-            return self._h2d(batch[self.cfg.MODEL.R3D_INPUT])[:, :, :5], self._h2d(batch['label'])
+            return self._float_clip(batch)[:, :, :5], self._h2d(batch['label'])
+        if "jitter" in batch:
+            raise ValueError("a 'jitter' entry needs MODEL.RES2D_BACKEND = 'engine' (the torch backend has no device kernels)")
         dev = "cpu" if torch.device(self.device).type != "cuda" else self.device
         x = batch[self.cfg.MODEL.R3D_INPUT][:, :, :5].to(dev)
         n, t, c, h, w = x.size()
@@ -286,7 +331,7 @@ class ModelManager:
     def _prepare_canonical_data(self, batch):
         """(N,T,21,S,S) -> the BGR frames as one strided (N,3,T,S,S) view, handed over as BOTH pathways: the slow
         pathway's PackPathway gather (model.slow_t_index) happens inside its stem kernel."""
-        x = torch.permute(self._h2d(batch[self.cfg.MODEL.R3D_INPUT]), [0, 2, 1, 3, 4])[:, 0:3]
+        x = torch.permute(self._float_clip(batch), [0, 2, 1, 3, 4])[:, 0:3]
         return [x, x], self._h2d(batch['label'])
 
     @staticmethod
@@ -330,7 +375,7 @@ class ModelManager:
                 return self._u8_clips(batch, [(0, 5)])[0], self._h2d(batch['label'])
             x = self._u8_float(batch)
         else:
-            x = self._h2d(batch[self.cfg.MODEL.R3D_INPUT])
+            x = self._float_clip(batch)
         x = torch.permute(x, [0, 2, 1, 3, 4])
         return x[:, 0:5], self._h2d(batch['label'])
 
@@ -339,14 +384,14 @@ class ModelManager:
         (20) is dropped (train.py:125-145).  The stem kernels read these views in place.
         A batch that carries ``<R3D_INPUT>_u8`` (N,T,S,S,21 uint8 frames, optional ``crop`` (N,2)) instead of the float32
         tensor takes the uint8 transport: normalise + RandomCrop run on the device (input_pipeline.py), or, with
-        MODEL.U8_STEM, inside the two stems, which read the frames as U8Clips over channels 0:5 and 5:20."""
-        key = self.cfg.MODEL.R3D_INPUT
+        MODEL.U8_STEM, inside the two stems, which read the frames as U8Clips over channels 0:5 and 5:20.
+        An optional ``jitter`` (N,8) entry applies ColorJitter to the B, G, R planes of the float clip (_jitter_v1)."""
         if self._u8_key(batch):
             if self._u8_stem():
                 return self._u8_clips(batch, [(0, 5), (5, 15)]), self._h2d(batch['label'])
             x = self._u8_float(batch)
         else:
-            x = self._h2d(batch[key])
+            x = self._float_clip(batch)
         x = torch.permute(x, [0, 2, 1, 3, 4])
         y_true = self._h2d(batch['label'])
         return [x[:, 0:5], x[:, 5:20]], y_true
@@ -383,8 +428,13 @@ class SyntheticChalearn(torch.utils.data.Dataset):
             if self.name == 'train':
                 from .input_pipeline import draw_crop_offsets
                 item['crop'] = draw_crop_offsets(1, self.size // 10, g)[0]
-            return item
-        return {self.key: (u8.float() / 255.0 - 0.45) / 0.225, 'label': self.labels[i]}
+        else:
+            item = {self.key: (u8.float() / 255.0 - 0.45) / 0.225, 'label': self.labels[i]}
+        ranges = jitter_ranges(self.cfg) if self.name == 'train' else None
+        if ranges is not None:                       # MODEL.COLOR_JITTER: the train clip's ColorJitter draws
+            from .input_pipeline import draw_color_jitter
+            item['jitter'] = draw_color_jitter(1, *ranges, generator=g)[0]
+        return item
 
     def __getitem__(self, i):
         if self.name == 'train':
