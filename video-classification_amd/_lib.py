@@ -224,6 +224,15 @@ class _JitterDesc(C.Structure):
                 ("workspace", C.c_void_p)]
 
 
+class _PoolDesc(C.Structure):
+    """include/sfk_pool.h sfk_pool_desc: byte (f, y, x, ch) of the frame pool at
+    pool[f*frame_stride + y*row_stride + x*pixel_pitch + c0 + ch]; clip n, time t of out is frame index[n][t] through lut"""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_int32), ("pool", C.c_void_p), ("frame_stride", C.c_int64),
+                ("row_stride", C.c_int64), ("pixel_pitch", C.c_int32), ("frames", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("c0", C.c_int32), ("c", C.c_int32), ("n", C.c_int32), ("t", C.c_int32), ("index", C.c_void_p),
+                ("lut", C.c_void_p), ("fill", C.c_int32), ("out", C.c_void_p)]
+
+
 class _Tuning(C.Structure):
     """sfk_tuning: the write-once kernel-selection table of sfk_init (defaults = the measured best)."""
     _fields_ = [("struct_size", C.c_uint32), ("igemm_short_k", C.c_int32), ("igemm_small_k", C.c_int32), ("igemm_wide_store", C.c_int32),
@@ -335,6 +344,14 @@ SIGNATURES_AUG = {
     "sfk_color_jitter_workspace_bytes": [_I32, _I32, _I32, _I32],
     "sfk_color_jitter": [C.POINTER(_JitterDesc), _PV],
 }
+# include/sfk_pool.h: the pooled evaluation input (one upload per test frame, windows gathered on the device), same library,
+# its own header and version
+POOL_ABI_VERSION = 1       # include/sfk_pool.h SFK_POOL_ABI_VERSION
+POOL_MAX_ROW_BYTES = 60 * 1024   # include/sfk_pool.h SFK_POOL_MAX_ROW_BYTES
+SIGNATURES_POOL = {
+    "sfk_pool_abi_version": [],
+    "sfk_u8_pool_gather": [C.POINTER(_PoolDesc), _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
@@ -376,6 +393,12 @@ def new_jitter_desc() -> "_JitterDesc":
     return d
 
 
+def new_pool_desc() -> "_PoolDesc":
+    d = _PoolDesc()
+    d.struct_size = C.sizeof(_PoolDesc)
+    return d
+
+
 def new_tuning() -> "_Tuning":
     t = _Tuning()
     t.struct_size = C.sizeof(_Tuning)
@@ -393,7 +416,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"{path} not found: build it with `python video-classification_amd/build.py` "
                        "(there is no CPU or PyTorch fallback for the SlowFast path)")
     lib = C.CDLL(path)
-    for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG):
+    for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -408,6 +431,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk v2 ABI version mismatch: library {lib.sfk_v2_abi_version()}, binding {V2_ABI_VERSION}")
     if lib.sfk_aug_abi_version() != AUG_ABI_VERSION:
         raise SfkError(f"libsfk aug ABI version mismatch: library {lib.sfk_aug_abi_version()}, binding {AUG_ABI_VERSION}")
+    if lib.sfk_pool_abi_version() != POOL_ABI_VERSION:
+        raise SfkError(f"libsfk pool ABI version mismatch: library {lib.sfk_pool_abi_version()}, binding {POOL_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -903,6 +928,23 @@ class HipBackend:
         d.n, d.t, d.h, d.w = n, t, h, w
         d.c_off, d.bgr, d.mean, d.std = c_off, 1 if bgr else 0, mean, std
         return self._plain("sfk_color_jitter", C.byref(d), keep=(d, clip, params, workspace))
+
+    def u8_pool_gather(self, pool, index, lut, fill: int, out, c0: int = 0, c: Optional[int] = None):
+        """sfk_u8_pool_gather (include/sfk_pool.h): pool (F,H,W,P) uint8 with unit channel stride (the byte strides are the
+        tensor's), index (N,T) int32 on the device, read when the launch runs; out (N,T,c,H,W) f32|bf16 contiguous =
+        lut[pool[index[n,t], y, x, c0 + ch]], or lut[fill] everywhere in a slab whose index is outside [0, F)."""
+        f, h, w, p = pool.shape
+        c = p - c0 if c is None else c
+        assert pool.dtype == torch.uint8 and pool.stride(3) == 1 and 0 <= c0 and 0 < c and c0 + c <= p
+        assert index.dtype == torch.int32 and index.dim() == 2 and index.is_contiguous()
+        n, t = index.shape
+        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
+        assert out.is_contiguous() and tuple(out.shape) == (n, t, c, h, w), (tuple(out.shape), (n, t, c, h, w))
+        d = new_pool_desc()
+        d.out_dtype, d.pool, d.index, d.lut, d.out = _DT[out.dtype], pool.data_ptr(), index.data_ptr(), lut.data_ptr(), out.data_ptr()
+        d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
+        d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
+        return self._plain("sfk_u8_pool_gather", C.byref(d), keep=(d, pool, index, lut, out))
 
     def filter_transpose(self, src, dst, cout, wtaps, cin):
         return self._plain("sfk_filter_transpose", _ptr(src), _DT[src.dtype], _ptr(dst), _DT[dst.dtype], cout, wtaps,

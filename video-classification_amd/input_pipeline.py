@@ -11,6 +11,9 @@ What it replaces (reference dataset/chalearn_dataset.py):
            pinned host memory so that it is an asynchronous DMA.
 The reference's ChalearnVideoDataset is untouched: a loader that can hand over its ``img_cat`` frames (HWC uint8, :113)
 feeds ``DevicePreprocess``; loaders that deliver float32 batches keep the reference path (ModelManager.prepare_data).
+  :131-140 the uniform windows of a test video overlap (stride 4): ``uniform_windows`` restates them as an index table, a test
+           video travels as ONE pool of its frames plus that table (the pooled item), and ``FramePool`` uploads every frame
+           once and builds the float clips of a batch on the device with ``sfk_u8_pool_gather`` (include/sfk_pool.h).
 torchvision is not installed here, so ToTensor / Normalize / RandomCrop are restated from their documented semantics;
 numerically this step is "parity unpinned" against torchvision itself (tests/test_aux_cpu.py pins it to plain torch).
 """
@@ -130,6 +133,155 @@ class DevicePreprocess:
         out = torch.empty(n, t, c, h, w, dtype=self.out_dtype, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
         self.be.u8_normalize_crop(x, self.lut, crop, int(padding or 0), out)(stream)
+        return out
+
+
+MISSING_BYTE = 127               # dataset/chalearn_dataset.py:116: every byte of a frame whose file is missing
+
+
+def uniform_windows(seq_len: int, clip_len: int, stride: int = 4) -> torch.Tensor:
+    """(K, T) int32 frame indices of the reference's ``uniform_sampling`` (dataset/chalearn_dataset.py:131-140): a video of at
+    most clip_len frames gives ONE window that wraps around (its random_sampling draws randint(0, 0) = 0); a longer one gives
+    the windows starting at range(0, seq_len - clip_len, stride) -- the tail of a video may belong to no window, as there."""
+    assert seq_len >= 1 and clip_len >= 1 and stride >= 1, (seq_len, clip_len, stride)
+    if seq_len <= clip_len:
+        return torch.tensor([[i % seq_len for i in range(clip_len)]], dtype=torch.int32)
+    starts = torch.arange(0, seq_len - clip_len, stride, dtype=torch.int32)
+    return starts[:, None] + torch.arange(clip_len, dtype=torch.int32)[None, :]
+
+
+def pool_key(key: str) -> str:
+    return key + "_pool"
+
+
+def make_pooled_item(key: str, windows: torch.Tensor, label, read) -> dict:
+    """The pooled item of one test video: {'<key>_pool': (F, S, S, P) uint8 HWC, 'windows': (K, T) int32, 'label'}.
+    windows holds indices into the VIDEO; read(i) returns frame i as (S, S, P) uint8, or None when it is missing, and is
+    called once per frame that some window references.  Only those frames that exist enter the pool, renumbered densely
+    in ascending order; a missing frame becomes -1 in 'windows'."""
+    windows = torch.as_tensor(windows, dtype=torch.int32)
+    remap, frames = {}, []
+    for i in sorted(set(windows.flatten().tolist())):
+        f = read(i)
+        if f is None:
+            remap[i] = -1
+        else:
+            remap[i] = len(frames)
+            frames.append(torch.as_tensor(f))
+    if not frames:
+        raise ValueError("a pooled video needs at least one frame that exists")
+    local = torch.tensor([[remap[i] for i in row] for row in windows.tolist()], dtype=torch.int32)
+    return {pool_key(key): torch.stack(frames), "windows": local, "label": label}
+
+
+def unpool_item(item: dict) -> list:
+    """A pooled item as the list of clip dicts it stands for, [{'<key>_u8': (T, S, S, P) uint8, 'label'}] -- the uint8
+    transport's test item -- with every missing frame (-1) materialised as bytes of 127."""
+    pk = next(k for k in item if k.endswith("_pool"))
+    pool, windows = item[pk], item["windows"]
+    ext = torch.cat([pool, torch.full_like(pool[:1], MISSING_BYTE)])       # the last entry stands for -1
+    idx = windows.long()
+    if int(idx.min()) < -1 or int(idx.max()) >= pool.shape[0]:
+        raise ValueError(f"window index outside [-1, {pool.shape[0]})")
+    return [{pk[:-len("_pool")] + "_u8": ext[row], "label": item["label"]} for row in idx]
+
+
+class FramePool:
+    """The device side of the pooled items: an arena of uint8 HWC frames (capacity, S, S, P) on the device, grown on demand.
+
+    ``add`` uploads the frames of one video ONCE, through pinned memory, into a free run of arena slots and returns the first
+    slot (its base); ``rows`` turns the video's window table into arena slots; ``gather`` builds the (N, T, c, S, S) float
+    clips of any mix of rows with one ``sfk_u8_pool_gather`` launch; ``release`` returns a video's slots once its last window
+    has been gathered.  A video whose windows straddle two batches simply stays in the arena until then.  Every copy and
+    launch goes on the current stream, so a slot is never overwritten before the gather that read it has run.
+    ``bytes_uploaded`` counts the frame bytes sent host to device."""
+
+    def __init__(self, device="cuda", backend=None, fill: int = MISSING_BYTE):
+        if backend is None:
+            from ._lib import HipBackend
+            backend = HipBackend()              # raises when libsfk.so is missing: no CPU path
+        self.be, self.device, self.fill = backend, torch.device(device), int(fill)
+        self.lut = normalize_lut().to(self.device)
+        self.arena: Optional[torch.Tensor] = None
+        self.live = {}                          # base -> frames of that video
+        self.bytes_uploaded = 0
+
+    def _h2d(self, t: torch.Tensor) -> torch.Tensor:
+        if t.device.type == "cpu" and self.device.type == "cuda" and not t.is_pinned():
+            t = t.pin_memory()
+        return t.to(self.device, non_blocking=True)
+
+    @staticmethod
+    def check_windows(windows: torch.Tensor, frames: int) -> None:
+        """every index is -1 (a missing frame) or inside its video's pool; anything else is a ValueError"""
+        w = torch.as_tensor(windows)
+        if w.numel() and (int(w.min()) < -1 or int(w.max()) >= frames):
+            raise ValueError(f"window index outside its video's pool: [{int(w.min())}, {int(w.max())}] against {frames} frames")
+
+    def _place(self, f: int) -> Optional[int]:
+        """the first free run of f slots (first fit over the gaps between the live videos), or None"""
+        at = 0
+        for base in sorted(self.live):
+            if base - at >= f:
+                return at
+            at = base + self.live[base]
+        return at if self.arena is not None and self.arena.shape[0] - at >= f else None
+
+    def _grow(self, f: int, like: torch.Tensor) -> None:
+        used = max((b + n for b, n in self.live.items()), default=0)
+        cap = max(used + f, 2 * (0 if self.arena is None else self.arena.shape[0]))
+        new = torch.empty((cap,) + tuple(like.shape[1:]), dtype=torch.uint8, device=self.device)
+        for b, n in self.live.items():          # device to device, on the current stream: not an upload
+            new[b:b + n].copy_(self.arena[b:b + n], non_blocking=True)
+        self.arena = new
+
+    def add(self, video_frames: torch.Tensor, windows: Optional[torch.Tensor] = None) -> int:
+        """upload (F, S, S, P) uint8 frames; windows, when given, is checked against F BEFORE anything is uploaded"""
+        assert video_frames.dtype == torch.uint8 and video_frames.dim() == 4 and video_frames.shape[0] > 0
+        f = int(video_frames.shape[0])
+        if windows is not None:
+            self.check_windows(windows, f)
+        if self.arena is not None and tuple(self.arena.shape[1:]) != tuple(video_frames.shape[1:]):
+            if self.live:
+                raise ValueError(f"frames of {tuple(video_frames.shape[1:])} in a pool of {tuple(self.arena.shape[1:])}")
+            self.arena = None
+        base = self._place(f)
+        if base is None:
+            self._grow(f, video_frames)
+            base = self._place(f)
+        src = video_frames.contiguous()
+        if src.device.type == "cpu" and self.device.type == "cuda" and not src.is_pinned():
+            src = src.pin_memory()
+        self.arena[base:base + f].copy_(src, non_blocking=True)
+        self.live[base] = f
+        self.bytes_uploaded += src.numel()
+        return base
+
+    def rows(self, base: int, windows: torch.Tensor) -> torch.Tensor:
+        """(K, T) int32 arena slots of a video's windows (-1 stays -1)"""
+        self.check_windows(windows, self.live[base])
+        w = torch.as_tensor(windows, dtype=torch.int32)
+        return torch.where(w < 0, w, w + base)
+
+    def release(self, base: int) -> None:
+        del self.live[base]
+
+    def gather(self, index_rows: torch.Tensor, out_dtype: torch.dtype = torch.float32, c0: int = 0,
+               c: Optional[int] = None) -> torch.Tensor:
+        """(N, T) arena slots (or -1) -> the (N, T, c, S, S) clips DevicePreprocess would write from the materialised frames"""
+        idx = torch.as_tensor(index_rows, dtype=torch.int32).contiguous()
+        assert idx.dim() == 2 and idx.numel() > 0 and self.arena is not None
+        ok = torch.zeros(self.arena.shape[0] + 1, dtype=torch.bool)      # the last entry stands for -1
+        ok[-1] = True
+        for b, n in self.live.items():
+            ok[b:b + n] = True
+        if int(idx.min()) < -1 or int(idx.max()) >= self.arena.shape[0] or not bool(ok[idx.long()].all()):
+            raise ValueError("gather: an index is neither -1 nor a slot of a video that is in the pool")
+        _, h, w, p = self.arena.shape
+        c = p - c0 if c is None else c
+        out = torch.empty(idx.shape[0], idx.shape[1], c, h, w, dtype=out_dtype, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+        self.be.u8_pool_gather(self.arena, self._h2d(idx), self.lut, self.fill, out, c0, c)(stream)
         return out
 
 

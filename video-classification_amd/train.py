@@ -12,7 +12,8 @@ What differs from /root/reference/train.py, and why:
     (the caller shards them, or every rank sees everything).  The reference is single-GPU;
   * datasets are injected (``train_loader`` / ``test_loader``) or built from the reference's own
     ``ChalearnVideoDataset`` when that module is importable; items keep its contract: a dict
-    {cfg.MODEL.R3D_INPUT: (T,21,S,S) float32, 'label': int} (lists of such dicts for the test set).
+    {cfg.MODEL.R3D_INPUT: (T,21,S,S) float32, 'label': int} (lists of such dicts for the test set); the uint8 transport
+    and the pooled test videos (``ChalearnVideoFramesU8``) are this engine's additions (input_pipeline.py).
 """
 from __future__ import annotations
 
@@ -403,10 +404,12 @@ def _identity(x):
 
 class SyntheticChalearn(torch.utils.data.Dataset):
     """Stand-in with the item contract of the reference's ChalearnVideoDataset (dataset/chalearn_dataset.py:162-185):
-    train -> dict, test -> list of dicts (uniform windows), values normalised like ToTensor+Normalize(0.45, 0.225)."""
+    train -> dict, test -> list of dicts (uniform windows), values normalised like ToTensor+Normalize(0.45, 0.225).
+    pooled=True: a test / valid item is ONE pooled video (input_pipeline.make_pooled_item) of F random frames, F drawn per
+    video from frames_per_video = (lo, hi), with the windows of ``uniform_windows(F, CLIP_LEN)``; nclips[i] is their count."""
 
     def __init__(self, cfg, name_of_set: str, num_videos: int = 8, clips_per_video=(1, 3), seed: int = 0,
-                 as_uint8: bool = False):
+                 as_uint8: bool = False, pooled: bool = False, frames_per_video=(8, 40)):
         self.cfg, self.name = cfg, name_of_set
         self.as_uint8 = as_uint8          # hand over the HWC uint8 frames (+ the train clip's crop offsets) instead
         self.key = cfg.MODEL.R3D_INPUT
@@ -416,9 +419,23 @@ class SyntheticChalearn(torch.utils.data.Dataset):
         self.labels = torch.randint(0, cfg.CHALEARN.NUM_CLASS, (num_videos,), generator=g).tolist()
         self.nclips = torch.randint(clips_per_video[0], clips_per_video[1] + 1, (num_videos,), generator=g).tolist()
         self.seed = seed
+        self.pooled = bool(pooled) and name_of_set != 'train'
+        if self.pooled:                   # a generator of its own: the draws above are what they are without the flag
+            from .input_pipeline import uniform_windows
+            gp = torch.Generator().manual_seed(seed * 104729 + 1)
+            lo, hi = frames_per_video
+            self.nframes = torch.randint(int(lo), int(hi) + 1, (num_videos,), generator=gp).tolist()
+            self.windows = [uniform_windows(f, self.t) for f in self.nframes]
+            self.nclips = [int(w.shape[0]) for w in self.windows]
 
     def __len__(self):
         return len(self.labels)
+
+    def _pooled(self, i):
+        from .input_pipeline import make_pooled_item
+        g = torch.Generator().manual_seed(self.seed * 7919 + i * 31 + 17)
+        frames = torch.randint(0, 256, (self.nframes[i], self.size, self.size, 21), generator=g, dtype=torch.uint8)
+        return make_pooled_item(self.key, self.windows[i], self.labels[i], lambda k: frames[k])
 
     def _clip(self, i, j):
         g = torch.Generator().manual_seed(self.seed * 7919 + i * 31 + j)
@@ -439,7 +456,105 @@ class SyntheticChalearn(torch.utils.data.Dataset):
     def __getitem__(self, i):
         if self.name == 'train':
             return self._clip(i, 0)
+        if self.pooled:
+            return self._pooled(i)
         return [self._clip(i, j) for j in range(self.nclips[i])]
+
+
+def cv2_read_frame(path, size: int):
+    """One frame's (size, size, 21) uint8 HWC image as the reference builds it (dataset/chalearn_dataset.py:99-116): the BGR
+    image, its U_ and V_ gray images, the five 3-channel flow images F0_ .. F4_ and the D_ gray image beside it, concatenated
+    on the channel axis, zero-padded to a square about its centre and resized with cv2.INTER_CUBIC; None when the file is
+    missing.  cv2 is imported here, on first use."""
+    try:
+        import cv2
+    except Exception as e:
+        raise RuntimeError("ChalearnVideoFramesU8's default frame reader needs OpenCV (cv2), which is not importable here "
+                           f"({e}); install it or pass read_frame=") from e
+    path = Path(path)
+    if not path.exists():
+        return None
+
+    def side(prefix, gray):
+        f = str(Path(path.parent, prefix + path.name))
+        return cv2.imread(f, cv2.IMREAD_GRAYSCALE)[..., np.newaxis] if gray else cv2.imread(f)
+
+    img = np.concatenate([cv2.imread(str(path)), side('U_', True), side('V_', True)] +
+                         [side(f'F{k}_', False) for k in range(5)] + [side('D_', True)], axis=-1)
+    h, w, c = img.shape
+    m = max(h, w)
+    nx, ny = (m - w) // 2, (m - h) // 2
+    sq = np.zeros((m, m, c), dtype=img.dtype)
+    sq[ny:ny + h, nx:nx + w, :] = img
+    return cv2.resize(sq, (size, size), interpolation=cv2.INTER_CUBIC)
+
+
+class ChalearnVideoFramesU8(torch.utils.data.Dataset):
+    """The reference's ChalearnVideoDataset (dataset/chalearn_dataset.py:26-185) for the uint8 transport: normalisation and
+    the RandomCrop are left to the device, and a test video is handed over as ONE pooled item instead of its windows.
+
+    labels: the reference's ``get_labels(name_of_set)`` list of (rgb path, depth path, 1-based label) (default: that call,
+    when the reference's utils.chalearn is importable).  'train': one ``random_sampling`` window,
+    {'<R3D_INPUT>_u8': (T, S, S, 21) uint8, 'crop': (2,) int32, 'label': label - 1} (+ 'jitter' under MODEL.COLOR_JITTER).
+    'test' / 'valid': {'<R3D_INPUT>_pool': (F, S, S, 21) uint8, 'windows': (K, T) int32, 'label'} -- the frames some uniform
+    window references, each read ONCE, a missing frame file as -1 -- or, with pooled=False, the list of
+    {'<R3D_INPUT>_u8', 'label'} clips.  read_frame(path, size) -> (size, size, 21) uint8 or None is injectable (default:
+    ``cv2_read_frame``)."""
+
+    def __init__(self, cfg, name_of_set: str, labels=None, read_frame: Optional[Callable] = None, pooled: bool = True):
+        assert name_of_set in ("train", "test", "valid")
+        if labels is None:
+            try:
+                from utils.chalearn import get_labels               # the reference's module, unchanged
+            except Exception as e:
+                raise RuntimeError(f"no labels were given and the reference's utils.chalearn is not importable here ({e})") from e
+            labels = get_labels(name_of_set)
+        self.cfg, self.name, self.labels = cfg, name_of_set, list(labels)
+        self.key = cfg.MODEL.R3D_INPUT
+        self.size = crop_resize_dict[self.key]
+        self.clip_len = int(cfg.CHALEARN.CLIP_LEN)
+        self.read_frame = read_frame or cv2_read_frame
+        self.pooled = bool(pooled)
+        import random
+        self.rng = random
+
+    def __len__(self):
+        return len(self.labels)
+
+    def _video(self, index):
+        """(the video's folder below a crop folder, its sorted frame file names, label - 1): :163-169"""
+        m, _k, l = self.labels[index]
+        folder = Path(m).parent / Path(m).stem
+        files = sorted(glob.glob(str(Path(self.cfg.CHALEARN.ROOT, self.cfg.CHALEARN.IMG, folder) / "*")))
+        return folder, [Path(f).name for f in files], int(l) - 1
+
+    def _read(self, folder, name):
+        f = self.read_frame(Path(self.cfg.CHALEARN.ROOT, self.key, folder, name), self.size)
+        if f is None:
+            return None
+        f = torch.as_tensor(f)
+        assert f.dtype == torch.uint8 and tuple(f.shape) == (self.size, self.size, 21), (f.dtype, tuple(f.shape))
+        return f
+
+    def __getitem__(self, index):
+        from .input_pipeline import (MISSING_BYTE, draw_color_jitter, draw_crop_offsets, make_pooled_item, uniform_windows,
+                                     unpool_item)
+        folder, names, label = self._video(index)
+        seq_len = len(names)
+        if self.name == "train":
+            start = self.rng.randint(0, max(0, seq_len - self.clip_len))           # random_sampling, :123-129
+            frames = []
+            for i in range(start, start + self.clip_len):
+                f = self._read(folder, names[i % seq_len])
+                frames.append(torch.full((self.size, self.size, 21), MISSING_BYTE, dtype=torch.uint8) if f is None else f)
+            item = {self.key + "_u8": torch.stack(frames), "crop": draw_crop_offsets(1, self.size // 10)[0], "label": label}
+            ranges = jitter_ranges(self.cfg)
+            if ranges is not None:
+                item["jitter"] = draw_color_jitter(1, *ranges)[0]
+            return item
+        item = make_pooled_item(self.key, uniform_windows(seq_len, self.clip_len), label,
+                                lambda i: self._read(folder, names[i]))
+        return item if self.pooled else unpool_item(item)
 
 
 class Trainer:
@@ -586,10 +701,36 @@ class Trainer:
         (train.py:287-370).  Returns {'ps','t','acc','sv'} as train_sparse.py:76-84 consumes it.
         The logits of every batch stay on the device; softmax, the per-video mean, argmax and the accuracy count are
         ONE ``sfk_eval_aggregate`` launch at the end, followed by one device->host copy of the result (the reference
-        copies logits and labels to the host after every batch, train.py:308-309)."""
+        copies logits and labels to the host after every batch, train.py:308-309).
+        A loader element that is a pooled item (a dict with '<R3D_INPUT>_pool' and 'windows', input_pipeline.py) is one
+        video whose frames are uploaded once into ``self.frame_pool``; its windows join the batches as (video, row)
+        references, and a batch of them is ONE ``sfk_u8_pool_gather`` launch that writes the float clip, handed to
+        prepare_data under the float key (whatever MODEL.U8_STEM says).  ``frame_pool.bytes_uploaded`` counts this call's."""
         loader = self.test_loader if dataset_loader is None else dataset_loader
         logit_list, true_list, batch_collect, samples_per_video = [], [], [], []
         self.model.eval()
+        key = self.cfg.MODEL.R3D_INPUT
+        if getattr(self, "frame_pool", None) is not None:
+            self.frame_pool.bytes_uploaded = 0
+
+        def pool_video(b):
+            if getattr(self, "frame_pool", None) is None:
+                from .input_pipeline import FramePool
+                self.frame_pool = FramePool(self.device, self.mm.backend)
+            base = self.frame_pool.add(b[key + "_pool"], b["windows"])
+            video = {"base": base, "rows": self.frame_pool.rows(base, b["windows"]), "label": int(b["label"]),
+                     "left": int(b["windows"].shape[0])}
+            return [(video, r) for r in range(video["left"])]
+
+        def collate(items):
+            if not isinstance(items[0], tuple):
+                return default_collate(items)
+            clip = self.frame_pool.gather(torch.stack([v["rows"][r] for v, r in items]))
+            for v, _ in items:
+                v["left"] -= 1
+                if v["left"] == 0:                             # its last window is in this gather: the slots are free
+                    self.frame_pool.release(v["base"])         # for uploads queued behind it on the same stream
+            return {key: clip, "label": torch.tensor([v["label"] for v, _ in items])}
 
         def test_batch(collect):
             x, y_true = self.mm.prepare_data(collect)
@@ -600,17 +741,19 @@ class Trainer:
 
         for step, batch in enumerate(loader):
             for b in batch:
+                if isinstance(b, dict) and key + "_pool" in b:   # a pooled video
+                    b = pool_video(b)
                 samples_per_video.append(len(b))
                 batch_collect.extend(b)
             if len(batch_collect) < self.batch_size:
                 continue
             while len(batch_collect) > self.batch_size:          # strict '>' as the reference (train.py:322)
-                test_batch(default_collate(batch_collect[:self.batch_size]))
+                test_batch(collate(batch_collect[:self.batch_size]))
                 batch_collect = batch_collect[self.batch_size:]
             if self.debug and step > 5:
                 break
         if len(batch_collect) > 0:
-            test_batch(default_collate(batch_collect))
+            test_batch(collate(batch_collect))
         if logit_list:
             logits = torch.cat(logit_list, dim=0).contiguous()
             labels = torch.cat(true_list, dim=0).to(torch.int64).contiguous()
