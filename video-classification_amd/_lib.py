@@ -233,6 +233,14 @@ class _PoolDesc(C.Structure):
                 ("lut", C.c_void_p), ("fill", C.c_int32), ("out", C.c_void_p)]
 
 
+class _ResizeDesc(C.Structure):
+    """include/sfk_resize.h sfk_resize_desc: frame f is the contiguous HWC bytes src[offset[f] ...] of hw[f] = (h, w) pixels
+    and c channels; its padded, cubic-resized (size, size, c) frame lands at out + f*out_frame_stride"""
+    _fields_ = [("struct_size", C.c_uint32), ("fill", C.c_int32), ("src", C.c_void_p), ("src_bytes", C.c_int64),
+                ("offset", C.c_void_p), ("hw", C.c_void_p), ("frames", C.c_int32), ("c", C.c_int32), ("size", C.c_int32),
+                ("max_side", C.c_int32), ("out", C.c_void_p), ("out_frame_stride", C.c_int64)]
+
+
 class _Tuning(C.Structure):
     """sfk_tuning: the write-once kernel-selection table of sfk_init (defaults = the measured best)."""
     _fields_ = [("struct_size", C.c_uint32), ("igemm_short_k", C.c_int32), ("igemm_small_k", C.c_int32), ("igemm_wide_store", C.c_int32),
@@ -352,6 +360,22 @@ SIGNATURES_POOL = {
     "sfk_pool_abi_version": [],
     "sfk_u8_pool_gather": [C.POINTER(_PoolDesc), _PV],
 }
+# include/sfk_resize.h: the v1 loader's pad + bicubic resize of ragged crops on the device, same library, its own header and
+# version
+RESIZE_ABI_VERSION = 1     # include/sfk_resize.h SFK_RESIZE_ABI_VERSION
+RESIZE_MAX_LDS_BYTES = 128 * 1024   # include/sfk_resize.h SFK_RESIZE_MAX_LDS_BYTES
+
+
+def resize_lds_bytes(max_side: int, c: int, size: int) -> int:
+    """include/sfk_resize.h SFK_RESIZE_LDS_BYTES: the LDS one workgroup of sfk_u8_pad_resize_cubic needs"""
+    row16 = lambda b: (b + 30) // 16 * 16
+    return max_side * ((c + 3) // 4) * 16 + 4 * (row16(max_side * c) + 16) + row16(size * c) + size * 36
+
+
+SIGNATURES_RESIZE = {
+    "sfk_resize_abi_version": [],
+    "sfk_u8_pad_resize_cubic": [C.POINTER(_ResizeDesc), _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
@@ -399,6 +423,12 @@ def new_pool_desc() -> "_PoolDesc":
     return d
 
 
+def new_resize_desc() -> "_ResizeDesc":
+    d = _ResizeDesc()
+    d.struct_size = C.sizeof(_ResizeDesc)
+    return d
+
+
 def new_tuning() -> "_Tuning":
     t = _Tuning()
     t.struct_size = C.sizeof(_Tuning)
@@ -416,7 +446,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"{path} not found: build it with `python video-classification_amd/build.py` "
                        "(there is no CPU or PyTorch fallback for the SlowFast path)")
     lib = C.CDLL(path)
-    for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL):
+    for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL,
+                  SIGNATURES_RESIZE):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -433,6 +464,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk aug ABI version mismatch: library {lib.sfk_aug_abi_version()}, binding {AUG_ABI_VERSION}")
     if lib.sfk_pool_abi_version() != POOL_ABI_VERSION:
         raise SfkError(f"libsfk pool ABI version mismatch: library {lib.sfk_pool_abi_version()}, binding {POOL_ABI_VERSION}")
+    if lib.sfk_resize_abi_version() != RESIZE_ABI_VERSION:
+        raise SfkError(f"libsfk resize ABI version mismatch: library {lib.sfk_resize_abi_version()}, binding {RESIZE_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -945,6 +978,28 @@ class HipBackend:
         d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
         d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
         return self._plain("sfk_u8_pool_gather", C.byref(d), keep=(d, pool, index, lut, out))
+
+    def u8_pad_resize_cubic(self, src, offset, hw, out, size: int, max_side: int, fill: int):
+        """sfk_u8_pad_resize_cubic (include/sfk_resize.h): src 1-D uint8, the frames' HWC bytes; offset (F,) int64 and hw (F, 2)
+        int32 on the device, read when the launch runs; out (F, size, size, c) uint8 -- or (N, T, size, size, c), F = N*T --
+        whose frames are contiguous and evenly spaced: out_frame_stride is the tensor's.  A frame with a non-positive or
+        oversized (h, w), or a span outside src, becomes bytes of fill."""
+        assert src.dtype == torch.uint8 and src.dim() == 1 and src.is_contiguous()
+        assert offset.dtype == torch.int64 and offset.dim() == 1 and offset.is_contiguous()
+        f = offset.shape[0]
+        assert hw.dtype == torch.int32 and tuple(hw.shape) == (f, 2) and hw.is_contiguous()
+        assert out.dtype == torch.uint8 and out.dim() in (4, 5)
+        c = out.shape[-1]
+        assert tuple(out.shape[-3:]) == (size, size, c) and tuple(out.stride()[-3:]) == (size * c, c, 1), tuple(out.stride())
+        if out.dim() == 5:
+            assert out.shape[0] * out.shape[1] == f and (out.shape[0] == 1 or out.stride(0) == out.shape[1] * out.stride(1))
+        else:
+            assert out.shape[0] == f
+        d = new_resize_desc()
+        d.src, d.src_bytes, d.offset, d.hw, d.out = src.data_ptr(), src.numel(), offset.data_ptr(), hw.data_ptr(), out.data_ptr()
+        d.frames, d.c, d.size, d.max_side, d.fill = f, c, int(size), int(max_side), int(fill)
+        d.out_frame_stride = out.stride(-4)
+        return self._plain("sfk_u8_pad_resize_cubic", C.byref(d), keep=(d, src, offset, hw, out))
 
     def filter_transpose(self, src, dst, cout, wtaps, cin):
         return self._plain("sfk_filter_transpose", _ptr(src), _DT[src.dtype], _ptr(dst), _DT[dst.dtype], cout, wtaps,

@@ -14,6 +14,10 @@ feeds ``DevicePreprocess``; loaders that deliver float32 batches keep the refere
   :131-140 the uniform windows of a test video overlap (stride 4): ``uniform_windows`` restates them as an index table, a test
            video travels as ONE pool of its frames plus that table (the pooled item), and ``FramePool`` uploads every frame
            once and builds the float clips of a batch on the device with ``sfk_u8_pool_gather`` (include/sfk_pool.h).
+  :60-71   ``_pad_resize_img`` -- zero-pad the 21-channel crop to a square, cv2.resize(INTER_CUBIC) to S x S: a loader may ship
+           the crops at their native, ragged sizes (the raw items) and ``PadResize`` writes the (S, S, 21) uint8 frames on
+           the device with one ``sfk_u8_pad_resize_cubic`` launch (include/sfk_resize.h); cv2 is not installed here, the
+           arithmetic is pinned to tests/ref_resize.py, parity with cv2 itself unpinned.
 torchvision is not installed here, so ToTensor / Normalize / RandomCrop are restated from their documented semantics;
 numerically this step is "parity unpinned" against torchvision itself (tests/test_aux_cpu.py pins it to plain torch).
 """
@@ -205,6 +209,7 @@ class FramePool:
         self.arena: Optional[torch.Tensor] = None
         self.live = {}                          # base -> frames of that video
         self.bytes_uploaded = 0
+        self._resize = {}                       # (size, channels) -> the PadResize of add_raw
 
     def _h2d(self, t: torch.Tensor) -> torch.Tensor:
         if t.device.type == "cpu" and self.device.type == "cuda" and not t.is_pinned():
@@ -227,13 +232,25 @@ class FramePool:
             at = base + self.live[base]
         return at if self.arena is not None and self.arena.shape[0] - at >= f else None
 
-    def _grow(self, f: int, like: torch.Tensor) -> None:
+    def _grow(self, f: int, frame_shape: tuple) -> None:
         used = max((b + n for b, n in self.live.items()), default=0)
         cap = max(used + f, 2 * (0 if self.arena is None else self.arena.shape[0]))
-        new = torch.empty((cap,) + tuple(like.shape[1:]), dtype=torch.uint8, device=self.device)
+        new = torch.empty((cap,) + tuple(frame_shape), dtype=torch.uint8, device=self.device)
         for b, n in self.live.items():          # device to device, on the current stream: not an upload
             new[b:b + n].copy_(self.arena[b:b + n], non_blocking=True)
         self.arena = new
+
+    def _reserve(self, f: int, frame_shape: tuple) -> int:
+        """the base of a free run of f arena slots of frame_shape (the arena grows, or starts over in a new shape when empty)"""
+        if self.arena is not None and tuple(self.arena.shape[1:]) != tuple(frame_shape):
+            if self.live:
+                raise ValueError(f"frames of {tuple(frame_shape)} in a pool of {tuple(self.arena.shape[1:])}")
+            self.arena = None
+        base = self._place(f)
+        if base is None:
+            self._grow(f, frame_shape)
+            base = self._place(f)
+        return base
 
     def add(self, video_frames: torch.Tensor, windows: Optional[torch.Tensor] = None) -> int:
         """upload (F, S, S, P) uint8 frames; windows, when given, is checked against F BEFORE anything is uploaded"""
@@ -241,20 +258,36 @@ class FramePool:
         f = int(video_frames.shape[0])
         if windows is not None:
             self.check_windows(windows, f)
-        if self.arena is not None and tuple(self.arena.shape[1:]) != tuple(video_frames.shape[1:]):
-            if self.live:
-                raise ValueError(f"frames of {tuple(video_frames.shape[1:])} in a pool of {tuple(self.arena.shape[1:])}")
-            self.arena = None
-        base = self._place(f)
-        if base is None:
-            self._grow(f, video_frames)
-            base = self._place(f)
+        base = self._reserve(f, tuple(video_frames.shape[1:]))
         src = video_frames.contiguous()
         if src.device.type == "cpu" and self.device.type == "cuda" and not src.is_pinned():
             src = src.pin_memory()
         self.arena[base:base + f].copy_(src, non_blocking=True)
         self.live[base] = f
         self.bytes_uploaded += src.numel()
+        return base
+
+    def add_raw(self, raw_bytes: torch.Tensor, hw: torch.Tensor, size: int, windows: Optional[torch.Tensor] = None,
+                channels: int = 21) -> int:
+        """a raw pooled video: its F frames at their native sizes, (h, w, channels) HWC bytes end to end in raw_bytes with
+        hw (F, 2) -- upload the BYTES once, reserve F arena slots of (size, size, channels) and let ``PadResize`` write the
+        padded, cubic-resized frames straight into them.  windows and the table are checked BEFORE anything is uploaded;
+        ``bytes_uploaded`` counts the raw bytes."""
+        hw = torch.as_tensor(hw, dtype=torch.int32)
+        assert hw.dim() == 2 and hw.shape[1] == 2 and hw.shape[0] > 0
+        f = int(hw.shape[0])
+        if windows is not None:
+            self.check_windows(windows, f)
+        key = (int(size), int(channels))
+        if key not in self._resize:
+            self._resize[key] = PadResize(size, self.device, self.be, fill=self.fill, channels=channels)
+        pr = self._resize[key]
+        offset = raw_offsets(hw, channels)
+        pr.check_table(int(raw_bytes.numel()), offset, hw)
+        base = self._reserve(f, (int(size), int(size), int(channels)))
+        pr(raw_bytes, offset, hw, out=self.arena[base:base + f])
+        self.live[base] = f
+        self.bytes_uploaded += int(raw_bytes.numel())
         return base
 
     def rows(self, base: int, windows: torch.Tensor) -> torch.Tensor:
@@ -282,6 +315,160 @@ class FramePool:
         out = torch.empty(idx.shape[0], idx.shape[1], c, h, w, dtype=out_dtype, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
         self.be.u8_pool_gather(self.arena, self._h2d(idx), self.lut, self.fill, out, c0, c)(stream)
+        return out
+
+
+def raw_key(key: str) -> str:
+    return key + "_raw"
+
+
+def rawpool_key(key: str) -> str:
+    return key + "_rawpool"
+
+
+def raw_offsets(hw: torch.Tensor, channels: int) -> torch.Tensor:
+    """int64 first byte of every frame of hw (..., 2) = (h, w) when the frames' HWC bytes lie end to end in table order; a
+    frame with a non-positive side has no bytes"""
+    hw = torch.as_tensor(hw).to(torch.int64)
+    nbytes = (hw[..., 0].clamp(min=0) * hw[..., 1].clamp(min=0) * int(channels)).flatten()
+    return (torch.cumsum(nbytes, 0) - nbytes).reshape(hw.shape[:-1])
+
+
+def pack_raw_frames(frames) -> tuple:
+    """[(h, w, c) uint8 HWC frame, or None for a missing one] -> (their bytes end to end, 1-D uint8; hw (F, 2) int32 with
+    (0, 0) for a missing frame)"""
+    parts, hw = [], []
+    for f in frames:
+        if f is None:
+            hw.append((0, 0))
+            continue
+        f = torch.as_tensor(f)
+        assert f.dtype == torch.uint8 and f.dim() == 3, (f.dtype, tuple(f.shape))
+        parts.append(f.contiguous().reshape(-1))
+        hw.append((int(f.shape[0]), int(f.shape[1])))
+    raw = torch.cat(parts) if parts else torch.empty(0, dtype=torch.uint8)
+    return raw, torch.tensor(hw, dtype=torch.int32).reshape(-1, 2)
+
+
+def make_raw_item(key: str, frames, label) -> dict:
+    """The raw train item of one clip: {'<key>_raw': 1-D uint8, 'raw_hw': (T, 2) int32, 'label'} from its T frames (None: a
+    missing frame, (0, 0) in raw_hw, which PadResize fills with 127)."""
+    raw, hw = pack_raw_frames(frames)
+    return {raw_key(key): raw, "raw_hw": hw, "label": label}
+
+
+def make_raw_pooled_item(key: str, windows: torch.Tensor, label, read) -> dict:
+    """``make_pooled_item`` for frames at their native sizes: {'<key>_rawpool': 1-D uint8, 'raw_hw': (F, 2) int32, 'windows':
+    (K, T) int32, 'label'}.  read(i) returns frame i as (h, w, c) uint8 HWC, or None when it is missing, once per frame that
+    some window references; only the frames that exist are kept, renumbered densely, a missing one is -1 in 'windows'."""
+    windows = torch.as_tensor(windows, dtype=torch.int32)
+    remap, frames = {}, []
+    for i in sorted(set(windows.flatten().tolist())):
+        f = read(i)
+        if f is None:
+            remap[i] = -1
+        else:
+            remap[i] = len(frames)
+            frames.append(f)
+    if not frames:
+        raise ValueError("a pooled video needs at least one frame that exists")
+    local = torch.tensor([[remap[i] for i in row] for row in windows.tolist()], dtype=torch.int32)
+    raw, hw = pack_raw_frames(frames)
+    return {rawpool_key(key): raw, "raw_hw": hw, "windows": local, "label": label}
+
+
+def collate_raw(items):
+    """``default_collate`` for a list of item dicts whose '<key>_raw' entries are ragged: those byte buffers are concatenated
+    into ONE 1-D uint8 tensor, in item order, and 'raw_offset' (N, T) int64 holds the first byte of every frame in it (a
+    missing frame has no bytes); 'raw_hw' and everything else is collated as default_collate does.  Items without a raw
+    entry are left to default_collate."""
+    from torch.utils.data.dataloader import default_collate
+    if not (isinstance(items[0], dict) and any(k.endswith("_raw") for k in items[0])):
+        return default_collate(items)
+    rk = next(k for k in items[0] if k.endswith("_raw"))
+    out = default_collate([{k: v for k, v in it.items() if k != rk} for it in items])
+    bufs = [torch.as_tensor(it[rk]).reshape(-1) for it in items]
+    hw = out["raw_hw"]
+    per_frame = hw[..., 0].clamp(min=0).to(torch.int64) * hw[..., 1].clamp(min=0).to(torch.int64)
+    pixels = per_frame.sum(dim=tuple(range(1, per_frame.dim())))
+    starts, at = [], 0
+    for it, b, px in zip(items, bufs, pixels.tolist()):
+        if px == 0 or b.numel() % px:
+            if b.numel():
+                raise ValueError(f"{rk}: {b.numel()} bytes for {px} pixels")
+            c = 1
+        else:
+            c = b.numel() // px
+        starts.append(raw_offsets(torch.as_tensor(it["raw_hw"]), c) + at)
+        at += b.numel()
+    out[rk] = torch.cat(bufs)
+    out["raw_offset"] = torch.stack(starts)
+    return out
+
+
+class PadResize:
+    """The reference's ``_pad_resize_img`` (dataset/chalearn_dataset.py:60-71) on the device: crops at their native sizes, HWC
+    bytes in one 1-D uint8 buffer with a table of byte offsets and (h, w) pairs, -> the (F, S, S, c) uint8 frames every
+    consumer of the uint8 transport reads, by ONE ``sfk_u8_pad_resize_cubic`` launch (include/sfk_resize.h).  The table is
+    validated on the host BEFORE anything is uploaded (a span outside the buffer or a negative size is a ValueError; a
+    (0, 0) entry is a missing frame and becomes bytes of ``fill``), max_side comes from the table, and bytes and table
+    cross through pinned memory.  The arithmetic is integer and pinned to tests/ref_resize.py; cv2 is not installed here,
+    parity with cv2.resize(INTER_CUBIC) itself is unpinned.  ``bytes_uploaded`` counts the raw bytes sent."""
+
+    def __init__(self, size: int, device="cuda", backend=None, fill: int = MISSING_BYTE, channels: int = 21):
+        if backend is None:
+            from ._lib import HipBackend
+            backend = HipBackend()              # raises when libsfk.so is missing: no CPU path
+        self.be, self.device = backend, torch.device(device)
+        self.size, self.fill, self.channels = int(size), int(fill), int(channels)
+        assert self.size > 0 and 0 <= self.fill <= 255 and self.channels > 0
+        self.bytes_uploaded = 0
+
+    def _h2d(self, t: torch.Tensor) -> torch.Tensor:
+        if t.device.type == "cpu" and self.device.type == "cuda" and not t.is_pinned():
+            t = t.pin_memory()
+        return t.to(self.device, non_blocking=True)
+
+    def check_table(self, nbytes: int, offset: torch.Tensor, hw: torch.Tensor) -> int:
+        """ValueError for a table the kernel would answer with fill bytes although a frame was meant (or could not stage);
+        returns max_side"""
+        from ._lib import RESIZE_MAX_LDS_BYTES, resize_lds_bytes
+        hw, offset = torch.as_tensor(hw), torch.as_tensor(offset)
+        if hw.dim() != 2 or hw.shape[1] != 2 or offset.dim() != 1 or offset.shape[0] != hw.shape[0] or hw.shape[0] == 0:
+            raise ValueError(f"offset {tuple(offset.shape)} and hw {tuple(hw.shape)}: (F,) and (F, 2), F > 0")
+        h, w = hw[:, 0].to(torch.int64), hw[:, 1].to(torch.int64)
+        if int(h.min()) < 0 or int(w.min()) < 0:
+            raise ValueError("a frame of negative size")
+        there = (h > 0) & (w > 0)
+        off, end = offset.to(torch.int64), offset.to(torch.int64) + h * w * self.channels
+        if bool((there & ((off < 0) | (end > int(nbytes)))).any()):
+            raise ValueError(f"a frame's bytes lie outside the buffer of {int(nbytes)} bytes")
+        max_side = max(1, int(torch.where(there, torch.maximum(h, w), torch.zeros_like(h)).max()))
+        if resize_lds_bytes(max_side, self.channels, self.size) > RESIZE_MAX_LDS_BYTES:
+            raise ValueError(f"frames of up to {max_side} pixels a side and {self.channels} channels to size {self.size} need more "
+                             "LDS than sfk_u8_pad_resize_cubic stages (include/sfk_resize.h)")
+        return max_side
+
+    def __call__(self, raw_bytes: torch.Tensor, offset: torch.Tensor, hw: torch.Tensor,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        assert raw_bytes.dtype == torch.uint8 and raw_bytes.dim() == 1
+        offset = torch.as_tensor(offset).to(torch.int64).reshape(-1)
+        hw = torch.as_tensor(hw).to(torch.int32).reshape(-1, 2)
+        max_side = self.check_table(int(raw_bytes.numel()), offset, hw)
+        f, s, c = int(hw.shape[0]), self.size, self.channels
+        if out is None:
+            out = torch.empty(f, s, s, c, dtype=torch.uint8, device=self.device)
+        if raw_bytes.numel() == 0:              # every frame is missing: the kernel reads nothing, but wants a pointer
+            raw_bytes = torch.zeros(1, dtype=torch.uint8)
+            nbytes = 0
+        else:
+            nbytes = int(raw_bytes.numel())
+        if raw_bytes.device.type == "cpu":
+            self.bytes_uploaded += nbytes
+        src = self._h2d(raw_bytes.contiguous())
+        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+        self.be.u8_pad_resize_cubic(src[:nbytes] if nbytes else src, self._h2d(offset.contiguous()), self._h2d(hw.contiguous()),
+                                    out, s, max_side, self.fill)(stream)
         return out
 
 

@@ -191,6 +191,7 @@ class ModelManager:
         self._pre = None
         self._lut = None
         self._jit = None
+        self._resize = None
         name = cfg.MODEL.NAME
         self.arch = str(cfg.MODEL.get("ARCH", "ref")).lower()
         if self.arch not in ("ref", "canonical8x8"):
@@ -225,6 +226,27 @@ class ModelManager:
     def _u8_key(self, batch) -> Optional[str]:
         key = self.cfg.MODEL.R3D_INPUT + "_u8"
         return key if key in batch else None
+
+    # ---- the raw transport: a batch carrying <R3D_INPUT>_raw (the clips' crops at their native sizes, HWC bytes end to end)
+    #      and raw_hw (N,T,2) -- collate_raw's -- instead of the resized frames.  PadResize writes the (N,T,S,S,21) uint8
+    #      frames on the device and the batch goes on as a <R3D_INPUT>_u8 batch whose frames are already there.
+    def _resized(self, batch):
+        key = self.cfg.MODEL.R3D_INPUT
+        if key + "_raw" not in batch:
+            return batch
+        from .input_pipeline import PadResize, raw_offsets
+        size = crop_resize_dict[key]
+        if self._resize is None:
+            self._resize = PadResize(size, self.device, self.backend)
+        hw = torch.as_tensor(batch["raw_hw"])
+        assert hw.dim() == 3 and hw.shape[2] == 2, tuple(hw.shape)
+        n, t = int(hw.shape[0]), int(hw.shape[1])
+        offset = batch["raw_offset"] if "raw_offset" in batch else raw_offsets(hw, self._resize.channels)
+        frames = torch.empty(n, t, size, size, self._resize.channels, dtype=torch.uint8, device=self.device)
+        self._resize(batch[key + "_raw"], offset, hw, out=frames)
+        rest = {k: v for k, v in batch.items() if k not in (key + "_raw", "raw_hw", "raw_offset")}
+        rest[key + "_u8"] = frames
+        return rest
 
     def _u8_stem(self) -> bool:
         return bool(self.cfg.MODEL.get("U8_STEM", False))
@@ -304,6 +326,7 @@ class ModelManager:
         """(N,T,21,S,S)[:, :, :5] -> (N, T*5, S, S): frames stacked on the channel axis (train.py:70-76).  Engine backend:
         the pinned (N,T,21,S,S) batch on the device, handed over as the strided (N,T,5,S,S) view -- no reshape copy; the
         stem reads frame t, channel c as input channel t*5 + c (Engine.input_view)."""
+        batch = self._resized(batch)
         if self._res2d_backend() == "engine":
             if self._u8_key(batch):                      # the uint8 transport
                 if self._u8_stem():
@@ -371,6 +394,7 @@ class ModelManager:
     def _prepare_res3d_data(self, batch):
         """(N,T,21,S,S) -> BGR+UV (N,5,T,S,S) strided view (train.py:85-89; 5 channels as train.py:72 / the 5-channel
         stem of :81).  A uint8 batch: DevicePreprocess's float clip, or (MODEL.U8_STEM) a U8Clip over channels 0:5."""
+        batch = self._resized(batch)
         if self._u8_key(batch):
             if self._u8_stem():
                 return self._u8_clips(batch, [(0, 5)])[0], self._h2d(batch['label'])
@@ -387,6 +411,7 @@ class ModelManager:
         tensor takes the uint8 transport: normalise + RandomCrop run on the device (input_pipeline.py), or, with
         MODEL.U8_STEM, inside the two stems, which read the frames as U8Clips over channels 0:5 and 5:20.
         An optional ``jitter`` (N,8) entry applies ColorJitter to the B, G, R planes of the float clip (_jitter_v1)."""
+        batch = self._resized(batch)
         if self._u8_key(batch):
             if self._u8_stem():
                 return self._u8_clips(batch, [(0, 5), (5, 15)]), self._h2d(batch['label'])
@@ -406,10 +431,14 @@ class SyntheticChalearn(torch.utils.data.Dataset):
     """Stand-in with the item contract of the reference's ChalearnVideoDataset (dataset/chalearn_dataset.py:162-185):
     train -> dict, test -> list of dicts (uniform windows), values normalised like ToTensor+Normalize(0.45, 0.225).
     pooled=True: a test / valid item is ONE pooled video (input_pipeline.make_pooled_item) of F random frames, F drawn per
-    video from frames_per_video = (lo, hi), with the windows of ``uniform_windows(F, CLIP_LEN)``; nclips[i] is their count."""
+    video from frames_per_video = (lo, hi), with the windows of ``uniform_windows(F, CLIP_LEN)``; nclips[i] is their count.
+    raw=True: the raw transport's items (input_pipeline.make_raw_item / make_raw_pooled_item) -- every frame a crop of ragged
+    (h, w), each side drawn from raw_side = (lo, hi) by a generator of the frame's own; a train item keeps the uint8 item's
+    'crop' (and 'jitter'), a test / valid item is one raw pooled video (raw implies pooled there)."""
 
     def __init__(self, cfg, name_of_set: str, num_videos: int = 8, clips_per_video=(1, 3), seed: int = 0,
-                 as_uint8: bool = False, pooled: bool = False, frames_per_video=(8, 40)):
+                 as_uint8: bool = False, pooled: bool = False, frames_per_video=(8, 40), raw: bool = False,
+                 raw_side=(24, 96)):
         self.cfg, self.name = cfg, name_of_set
         self.as_uint8 = as_uint8          # hand over the HWC uint8 frames (+ the train clip's crop offsets) instead
         self.key = cfg.MODEL.R3D_INPUT
@@ -419,7 +448,11 @@ class SyntheticChalearn(torch.utils.data.Dataset):
         self.labels = torch.randint(0, cfg.CHALEARN.NUM_CLASS, (num_videos,), generator=g).tolist()
         self.nclips = torch.randint(clips_per_video[0], clips_per_video[1] + 1, (num_videos,), generator=g).tolist()
         self.seed = seed
-        self.pooled = bool(pooled) and name_of_set != 'train'
+        self.raw, self.raw_side = bool(raw), (int(raw_side[0]), int(raw_side[1]))
+        if self.raw:                      # only a raw set has one (Trainer._make_loaders)
+            from .input_pipeline import collate_raw
+            self.collate_fn = collate_raw
+        self.pooled = (bool(pooled) or self.raw) and name_of_set != 'train'
         if self.pooled:                   # a generator of its own: the draws above are what they are without the flag
             from .input_pipeline import uniform_windows
             gp = torch.Generator().manual_seed(seed * 104729 + 1)
@@ -431,8 +464,18 @@ class SyntheticChalearn(torch.utils.data.Dataset):
     def __len__(self):
         return len(self.labels)
 
+    def _raw_frame(self, i, j, k):
+        """frame k of clip j (or of the pooled video, j = -1) of video i: ragged (h, w, 21) random bytes, a generator of its own"""
+        g = torch.Generator().manual_seed(((self.seed * 15485863 + i) * 1009 + j + 1) * 2003 + k)
+        lo, hi = self.raw_side
+        h, w = torch.randint(lo, hi + 1, (2,), generator=g).tolist()
+        return torch.randint(0, 256, (h, w, 21), generator=g, dtype=torch.uint8)
+
     def _pooled(self, i):
         from .input_pipeline import make_pooled_item
+        if self.raw:
+            from .input_pipeline import make_raw_pooled_item
+            return make_raw_pooled_item(self.key, self.windows[i], self.labels[i], lambda k: self._raw_frame(i, -1, k))
         g = torch.Generator().manual_seed(self.seed * 7919 + i * 31 + 17)
         frames = torch.randint(0, 256, (self.nframes[i], self.size, self.size, 21), generator=g, dtype=torch.uint8)
         return make_pooled_item(self.key, self.windows[i], self.labels[i], lambda k: frames[k])
@@ -440,7 +483,13 @@ class SyntheticChalearn(torch.utils.data.Dataset):
     def _clip(self, i, j):
         g = torch.Generator().manual_seed(self.seed * 7919 + i * 31 + j)
         u8 = torch.randint(0, 256, (self.t, 21, self.size, self.size), generator=g, dtype=torch.uint8)
-        if self.as_uint8:
+        if self.raw:                      # (u8 is drawn all the same: 'crop' and 'jitter' below are the uint8 item's draws)
+            from .input_pipeline import make_raw_item
+            item = make_raw_item(self.key, [self._raw_frame(i, j, k) for k in range(self.t)], self.labels[i])
+            if self.name == 'train':
+                from .input_pipeline import draw_crop_offsets
+                item['crop'] = draw_crop_offsets(1, self.size // 10, g)[0]
+        elif self.as_uint8:
             item = {self.key + "_u8": u8.permute(0, 2, 3, 1).contiguous(), 'label': self.labels[i]}
             if self.name == 'train':
                 from .input_pipeline import draw_crop_offsets
@@ -489,6 +538,27 @@ def cv2_read_frame(path, size: int):
     return cv2.resize(sq, (size, size), interpolation=cv2.INTER_CUBIC)
 
 
+def cv2_read_frame_raw(path):
+    """``cv2_read_frame`` without the pad and the resize: the (h, w, 21) uint8 HWC concatenation of a frame's images at the
+    crop's own size (dataset/chalearn_dataset.py:99-113), for the raw transport -- ``PadResize`` does the rest on the
+    device; None when the file is missing."""
+    try:
+        import cv2
+    except Exception as e:
+        raise RuntimeError("ChalearnVideoFramesU8's default raw frame reader needs OpenCV (cv2), which is not importable "
+                           f"here ({e}); install it or pass read_frame=") from e
+    path = Path(path)
+    if not path.exists():
+        return None
+
+    def side(prefix, gray):
+        f = str(Path(path.parent, prefix + path.name))
+        return cv2.imread(f, cv2.IMREAD_GRAYSCALE)[..., np.newaxis] if gray else cv2.imread(f)
+
+    return np.concatenate([cv2.imread(str(path)), side('U_', True), side('V_', True)] +
+                          [side(f'F{k}_', False) for k in range(5)] + [side('D_', True)], axis=-1)
+
+
 class ChalearnVideoFramesU8(torch.utils.data.Dataset):
     """The reference's ChalearnVideoDataset (dataset/chalearn_dataset.py:26-185) for the uint8 transport: normalisation and
     the RandomCrop are left to the device, and a test video is handed over as ONE pooled item instead of its windows.
@@ -499,10 +569,23 @@ class ChalearnVideoFramesU8(torch.utils.data.Dataset):
     'test' / 'valid': {'<R3D_INPUT>_pool': (F, S, S, 21) uint8, 'windows': (K, T) int32, 'label'} -- the frames some uniform
     window references, each read ONCE, a missing frame file as -1 -- or, with pooled=False, the list of
     {'<R3D_INPUT>_u8', 'label'} clips.  read_frame(path, size) -> (size, size, 21) uint8 or None is injectable (default:
-    ``cv2_read_frame``)."""
+    ``cv2_read_frame``).
+    resize='device': the raw transport.  read_frame(path) -> (h, w, 21) uint8 at the crop's own size, or None (default:
+    ``cv2_read_frame_raw``); 'train': {'<R3D_INPUT>_raw': 1-D uint8, 'raw_hw': (T, 2) int32, 'crop', 'label'} (+ 'jitter'),
+    a missing frame as (0, 0); 'test' / 'valid': {'<R3D_INPUT>_rawpool': 1-D uint8, 'raw_hw': (F, 2) int32, 'windows',
+    'label'}.  The set then has ``collate_fn = collate_raw``, which the Trainer's train loader uses."""
 
-    def __init__(self, cfg, name_of_set: str, labels=None, read_frame: Optional[Callable] = None, pooled: bool = True):
+    def __init__(self, cfg, name_of_set: str, labels=None, read_frame: Optional[Callable] = None, pooled: bool = True,
+                 resize: str = "host"):
         assert name_of_set in ("train", "test", "valid")
+        if resize not in ("host", "device"):
+            raise ValueError(f"resize={resize!r}: 'host' or 'device'")
+        if resize == "device" and name_of_set != "train" and not pooled:
+            raise ValueError("resize='device' hands a test video over as one raw pooled item: pooled=False has no raw form")
+        self.resize = resize
+        if resize == "device":
+            from .input_pipeline import collate_raw
+            self.collate_fn = collate_raw
         if labels is None:
             try:
                 from utils.chalearn import get_labels               # the reference's module, unchanged
@@ -513,7 +596,7 @@ class ChalearnVideoFramesU8(torch.utils.data.Dataset):
         self.key = cfg.MODEL.R3D_INPUT
         self.size = crop_resize_dict[self.key]
         self.clip_len = int(cfg.CHALEARN.CLIP_LEN)
-        self.read_frame = read_frame or cv2_read_frame
+        self.read_frame = read_frame or (cv2_read_frame_raw if resize == "device" else cv2_read_frame)
         self.pooled = bool(pooled)
         import random
         self.rng = random
@@ -536,13 +619,29 @@ class ChalearnVideoFramesU8(torch.utils.data.Dataset):
         assert f.dtype == torch.uint8 and tuple(f.shape) == (self.size, self.size, 21), (f.dtype, tuple(f.shape))
         return f
 
+    def _read_raw(self, folder, name):
+        f = self.read_frame(Path(self.cfg.CHALEARN.ROOT, self.key, folder, name))
+        if f is None:
+            return None
+        f = torch.as_tensor(f)
+        assert f.dtype == torch.uint8 and f.dim() == 3 and f.shape[2] == 21, (f.dtype, tuple(f.shape))
+        return f
+
     def __getitem__(self, index):
-        from .input_pipeline import (MISSING_BYTE, draw_color_jitter, draw_crop_offsets, make_pooled_item, uniform_windows,
-                                     unpool_item)
+        from .input_pipeline import (MISSING_BYTE, draw_color_jitter, draw_crop_offsets, make_pooled_item, make_raw_item,
+                                     make_raw_pooled_item, uniform_windows, unpool_item)
         folder, names, label = self._video(index)
         seq_len = len(names)
         if self.name == "train":
             start = self.rng.randint(0, max(0, seq_len - self.clip_len))           # random_sampling, :123-129
+            if self.resize == "device":
+                item = make_raw_item(self.key, [self._read_raw(folder, names[i % seq_len])
+                                                for i in range(start, start + self.clip_len)], label)
+                item["crop"] = draw_crop_offsets(1, self.size // 10)[0]
+                ranges = jitter_ranges(self.cfg)
+                if ranges is not None:
+                    item["jitter"] = draw_color_jitter(1, *ranges)[0]
+                return item
             frames = []
             for i in range(start, start + self.clip_len):
                 f = self._read(folder, names[i % seq_len])
@@ -552,6 +651,9 @@ class ChalearnVideoFramesU8(torch.utils.data.Dataset):
             if ranges is not None:
                 item["jitter"] = draw_color_jitter(1, *ranges)[0]
             return item
+        if self.resize == "device":
+            return make_raw_pooled_item(self.key, uniform_windows(seq_len, self.clip_len), label,
+                                        lambda i: self._read_raw(folder, names[i]))
         item = make_pooled_item(self.key, uniform_windows(seq_len, self.clip_len), label,
                                 lambda i: self._read(folder, names[i]))
         return item if self.pooled else unpool_item(item)
@@ -613,18 +715,21 @@ class Trainer:
         epoch cut into disjoint per-rank shards (every rank runs the same number of steps), test videos round-robin."""
         pin = torch.device(self.device).type == "cuda"
         kw = dict(num_workers=self.num_workers, pin_memory=pin)
+        tkw = dict(kw)                                   # the train loader: a dataset's own collate (the raw items' collate_raw)
+        if getattr(tr, "collate_fn", None) is not None:
+            tkw["collate_fn"] = tr.collate_fn
         if self.world > 1:
             self.train_sampler = sdist.EpochShardSampler(len(tr), self.rank, self.world, seed=0,
                                                          drop_last=self.train_drop_last)
             train = torch.utils.data.DataLoader(tr, batch_size=self.batch_size, sampler=self.train_sampler,
-                                                drop_last=self.train_drop_last, **kw)
+                                                drop_last=self.train_drop_last, **tkw)
             test = torch.utils.data.DataLoader(te, batch_size=self.batch_size, drop_last=False, collate_fn=_identity,
                                                sampler=sdist.VideoShardSampler(len(te), self.rank, self.world), **kw)
             test.sfk_shard = (self.rank, self.world, len(te))
         else:
             self.train_sampler = None
             train = torch.utils.data.DataLoader(tr, batch_size=self.batch_size, shuffle=True,
-                                                drop_last=self.train_drop_last, **kw)
+                                                drop_last=self.train_drop_last, **tkw)
             test = torch.utils.data.DataLoader(te, batch_size=self.batch_size, shuffle=False, drop_last=False,
                                                collate_fn=_identity, **kw)
         return train, test
@@ -705,7 +810,9 @@ class Trainer:
         A loader element that is a pooled item (a dict with '<R3D_INPUT>_pool' and 'windows', input_pipeline.py) is one
         video whose frames are uploaded once into ``self.frame_pool``; its windows join the batches as (video, row)
         references, and a batch of them is ONE ``sfk_u8_pool_gather`` launch that writes the float clip, handed to
-        prepare_data under the float key (whatever MODEL.U8_STEM says).  ``frame_pool.bytes_uploaded`` counts this call's."""
+        prepare_data under the float key (whatever MODEL.U8_STEM says).  ``frame_pool.bytes_uploaded`` counts this call's.
+        A raw pooled item ('<R3D_INPUT>_rawpool' + 'raw_hw': the frames at their native sizes) differs only in how its arena
+        slots are filled: ``FramePool.add_raw`` uploads the raw bytes and ``sfk_u8_pad_resize_cubic`` writes the frames."""
         loader = self.test_loader if dataset_loader is None else dataset_loader
         logit_list, true_list, batch_collect, samples_per_video = [], [], [], []
         self.model.eval()
@@ -717,7 +824,10 @@ class Trainer:
             if getattr(self, "frame_pool", None) is None:
                 from .input_pipeline import FramePool
                 self.frame_pool = FramePool(self.device, self.mm.backend)
-            base = self.frame_pool.add(b[key + "_pool"], b["windows"])
+            if key + "_rawpool" in b:                      # the frames at their native sizes: resized into the arena slots
+                base = self.frame_pool.add_raw(b[key + "_rawpool"], b["raw_hw"], crop_resize_dict[key], b["windows"])
+            else:
+                base = self.frame_pool.add(b[key + "_pool"], b["windows"])
             video = {"base": base, "rows": self.frame_pool.rows(base, b["windows"]), "label": int(b["label"]),
                      "left": int(b["windows"].shape[0])}
             return [(video, r) for r in range(video["left"])]
@@ -741,7 +851,7 @@ class Trainer:
 
         for step, batch in enumerate(loader):
             for b in batch:
-                if isinstance(b, dict) and key + "_pool" in b:   # a pooled video
+                if isinstance(b, dict) and (key + "_pool" in b or key + "_rawpool" in b):   # a pooled video
                     b = pool_video(b)
                 samples_per_video.append(len(b))
                 batch_collect.extend(b)
