@@ -1,0 +1,547 @@
+"""TEST INFRASTRUCTURE: everything after the last bottleneck -- head pooling with dropout, the linear layer, softmax
+cross-entropy, Adam -- restated in float64 on whatever device the inputs live on, the bounds those kernels are held to
+element by element, the case tables, and the checks that run one case on a backend (HipBackend on the GPU, EmuBackend and
+its mutants on the CPU) and return the verdicts.
+
+Every restatement returns (value, a) with a = the same expression over |terms|; the tolerance policy is ref64's
+(compare / elem_bound / ulp_out), used as it stands.  The dropout keep decision is emu_backend.keep_mask, the independent
+numpy restatement of csrc/pool_head.hip::keep_of (bound here at import: a test that patches emu_backend.keep_mask to build
+a wrong backend does not move the reference).
+
+Two bounds carry a term of their own, both derived from the float64 reference and both needed by an honest float32
+evaluation (tests/test_head_opt_ref_cpu.py pins that):
+  * softmax: exp(x - max) is evaluated at the ROUNDED difference, whose error 2^-24 |x - max| is relative to the difference
+    and not to the result; it moves p_i by p_i |x_i - max| 2^-24 directly and by p_i sum_j p_j |x_j - max| 2^-24 through the
+    normaliser -> 2 * 2^-24 (|x_i - max| p_i + p_i sum_j p_j |x_j - max|) / n * gscale (softmax_ce, `extra`);
+  * Adam's p': |p| + |dp| with K = 4 covers the roundings of the update's own chain, but not the rounding of m' and v'
+    where their two terms cancel (|m'| << |b1 m| + |(1-b1) g|): that error reaches p' through dp = -(lr/bc1) m' / den, so
+    the bound carries |d dp / d m'| bound(m') + |d dp / d v'| bound(v') (adam_bounds, `prop`)."""
+from __future__ import annotations
+
+import math
+from typing import List, Tuple
+
+import numpy as np
+import torch
+
+import ref64
+from emu_backend import keep_mask
+from ref64 import EPS32, F64, compare, elem_bound, ulp_out
+from video_classification_amd._lib import FMap
+
+F32, BF16 = torch.float32, torch.bfloat16
+FEAT_SENTINEL = -7.5          # exactly representable in bf16 and fp32
+SEED = 0x1234_5678_9ABC
+
+
+def f32(x: float) -> float:
+    """the value a `float` argument of the C ABI carries"""
+    return float(np.float32(x))
+
+
+class Exact:
+    """a yes/no property (bits kept, an exact zero, an integer count) reported beside the Verdicts"""
+    __slots__ = ("name", "ok", "detail", "worst")
+
+    def __init__(self, name: str, ok: bool, detail: str = ""):
+        self.name, self.ok, self.detail, self.worst = name, bool(ok), detail, 0.0
+
+    def __repr__(self):
+        return f"{self.name}[exact] {self.detail} {'ok' if self.ok else 'FAIL'}"
+
+
+class ElemOnly:
+    """a Verdict judged by its element bound alone (one scalar whose terms cancel: the aggregate ratio says nothing)"""
+    __slots__ = ("v", "ok", "worst", "name")
+
+    def __init__(self, v):
+        self.v, self.ok, self.worst, self.name = v, v.worst <= 1.0, v.worst, v.name
+
+    def __repr__(self):
+        return f"{self.v.name}[elem only] worst {self.v.worst:.3g} n {self.v.n} {'ok' if self.ok else 'FAIL'}"
+
+
+def worst_of(vs) -> float:
+    return max([v.worst for v in vs] + [0.0])
+
+
+def failures(vs):
+    return [v for v in vs if not v.ok]
+
+
+def _sync(dev):
+    if torch.device(dev).type == "cuda":
+        torch.cuda.synchronize()
+
+
+def _stream(dev):
+    return torch.cuda.current_stream().cuda_stream if torch.device(dev).type == "cuda" else 0
+
+
+# ----------------------------------------------------------------------------- head pooling
+def positions(dims, k) -> Tuple[int, int, int]:
+    return tuple(d - kk + 1 for d, kk in zip(dims, k))
+
+
+def head_pool_fwd(X: torch.Tensor, k, keep: torch.Tensor, rate: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """feat[n, ch] = mean over positions of keep * (window mean) / (1 - rate).  X (N,T,H,W,C), keep (N,C,P) bool"""
+    x = X.to(F64)
+    n, c = x.shape[0], x.shape[4]
+    u = x.unfold(1, k[0], 1).unfold(2, k[1], 1).unfold(3, k[2], 1)          # n pt ph pw c kt kh kw
+    win = float(k[0] * k[1] * k[2])
+    wm, wa = u.sum((-1, -2, -3)) / win, u.abs().sum((-1, -2, -3)) / win
+    sc = keep.to(F64) / (1.0 - f32(rate))
+    wm, wa = wm.reshape(n, -1, c).permute(0, 2, 1), wa.reshape(n, -1, c).permute(0, 2, 1)
+    return (wm * sc).mean(2), (wa * sc).mean(2)
+
+
+def head_pool_bwd(g: torch.Tensor, dims, k, keep: torch.Tensor, rate: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dx[n, t, h, w, ch] = sum over the kept windows that contain the pixel of g[n, ch] / ((1 - rate) window positions)"""
+    n, c = g.shape
+    pt, ph, pw = positions(dims, k)
+    win, P = k[0] * k[1] * k[2], pt * ph * pw
+    wgt = keep.to(F64) / (1.0 - f32(rate)) * g.to(F64).unsqueeze(2) / float(P * win)
+    wgt = wgt.permute(0, 2, 1).reshape(n, pt, ph, pw, c)
+    dx = torch.zeros(n, *dims, c, dtype=F64, device=g.device)
+    a = torch.zeros_like(dx)
+    for i in range(k[0]):
+        for j in range(k[1]):
+            for l in range(k[2]):
+                dx[:, i:i + pt, j:j + ph, l:l + pw] += wgt
+                a[:, i:i + pt, j:j + ph, l:l + pw] += wgt.abs()
+    return dx, a
+
+
+def _part(c, dims, k=None, ld=None, off=0, f_off=0):
+    return dict(c=c, dims=tuple(dims), k=tuple(k or dims), ld=ld or c, off=off, f_off=f_off)
+
+
+def _pool(name, dtype, n, rate, parts, feat_ld=None):
+    parts = list(parts)
+    return dict(name=name, dtype=dtype, n=n, rate=rate, parts=parts,
+                feat_ld=feat_ld or max(p["f_off"] + p["c"] for p in parts) + 4)
+
+
+def _pool1_cases():
+    out = []
+    for dtype, c, tag in ((BF16, 264, "bf16"), (F32, 260, "f32")):
+        for dims in ((2, 3, 3), (4, 7, 7)):          # 18 pixels: fewer than the slices; 196: a slice remainder
+            for rate in (0.0, 0.5):
+                out.append(_pool(f"{tag}-c{c}-{dims[0]}x{dims[1]}x{dims[2]}-r{rate}", dtype, 2, rate,
+                                 [_part(c, dims, f_off=4)]))
+        out.append(_pool(f"{tag}-c{c}-strided", dtype, 2, 0.5, [_part(c, (4, 7, 7), ld=c + 8, off=8, f_off=4)]))
+    for rate in (0.0, 0.5):                          # 257 channel groups: a second y-block in the backward
+        out.append(_pool(f"f32-c1028-r{rate}", F32, 1, rate, [_part(1028, (1, 2, 2))]))
+    # the production pairing: slow then fast pathway into one feat, at the production channel counts on tiny maps
+    out.append(_pool("bf16-pair-2048+256", BF16, 2, 0.5, [_part(2048, (2, 2, 2)), _part(256, (2, 2, 2), f_off=2048)]))
+    out.append(_pool("f32-pair-260+8", F32, 2, 0.5, [_part(260, (2, 3, 3)), _part(8, (4, 7, 7), f_off=260)]))
+    return out
+
+
+def _poolg_cases():
+    out = []
+    for dtype, tag in ((BF16, "bf16"), (F32, "f32")):
+        out.append(_pool(f"{tag}-windows", dtype, 2, 0.5, [_part(24, (6, 4, 4), k=(4, 2, 2), f_off=8)]))
+        out.append(_pool(f"{tag}-c10-full-window", dtype, 2, 0.5, [_part(10, (2, 3, 3), f_off=3)]))
+    return out
+
+
+POOL1_CASES = _pool1_cases()       # the window equals the map and the channels are a vector multiple: head_pool1_*
+POOLG_CASES = _poolg_cases()       # the general kernels
+POOL_CASES = POOL1_CASES + POOLG_CASES
+
+
+def check_pool(be, dev, case, seed_no: int = 0) -> List:
+    """forward of every part into one feat, then the backward of every part, each against float64"""
+    dtype, n, rate, feat_ld = case["dtype"], case["n"], case["rate"], case["feat_ld"]
+    kind = "map_bf16" if dtype == BF16 else "map_f32"
+    gen = torch.Generator().manual_seed(100 + seed_no)
+    st = _stream(dev)
+    seed = torch.tensor([SEED], dtype=torch.int64, device=dev)
+    feat = torch.full((n * feat_ld,), FEAT_SENTINEL, device=dev)
+    dfeat = torch.randn(n * feat_ld, generator=gen).to(dev)
+    maps, grads, masks = [], [], []
+    for p in case["parts"]:
+        px = n * p["dims"][0] * p["dims"][1] * p["dims"][2]
+        x = FMap(torch.randn(px * p["ld"], generator=gen).to(dtype).to(dev), n, *p["dims"], p["c"], p["ld"], p["off"])
+        be.head_pool_fwd(x, p["k"], rate, seed, feat, feat_ld, p["f_off"])(st)
+        maps.append(x)
+    for p in case["parts"]:
+        px = n * p["dims"][0] * p["dims"][1] * p["dims"][2]
+        dx = FMap(torch.full((px * p["ld"],), FEAT_SENTINEL, dtype=dtype, device=dev), n, *p["dims"], p["c"], p["ld"], p["off"])
+        be.head_pool_bwd(dfeat, feat_ld, p["f_off"], p["k"], rate, seed, dx)(st)
+        grads.append(dx)
+        P = math.prod(positions(p["dims"], p["k"]))
+        m = torch.full((n * p["c"] * P,), 9, dtype=torch.uint8, device=dev)
+        if rate > 0:
+            be.head_dropout_mask(n, p["c"], p["f_off"], P, rate, seed, m)(st)
+        masks.append(m)
+    _sync(dev)
+    vs = []
+    fv = feat.view(n, feat_ld)
+    written = torch.zeros(feat_ld, dtype=torch.bool, device=dev)
+    for p, x, dx, m in zip(case["parts"], maps, grads, masks):
+        c, k, dims, f_off = p["c"], p["k"], p["dims"], p["f_off"]
+        tag = f"{case['name']}@{f_off}"
+        P = math.prod(positions(dims, k))
+        win = k[0] * k[1] * k[2]
+        keep_np = keep_mask(SEED, n, c, f_off, P, rate)
+        keep = torch.from_numpy(keep_np).to(dev)
+        if rate > 0:
+            vs.append(Exact(f"mask {tag}", torch.equal(m.view(n, c, P), keep.to(torch.uint8)), f"kept {float(keep_np.mean()):.3f}"))
+        r, a = head_pool_fwd(x.view5(), k, keep, rate)
+        y = fv[:, f_off:f_off + c]
+        vs.append(compare(f"feat {tag}", y, r, a, win * P, F32, "sum_f32"))
+        if P == 1:
+            vs.append(Exact(f"feat dropped == 0 {tag}", bool((y[~keep[:, :, 0]] == 0).all()), f"{int((~keep).sum())} dropped"))
+        written[f_off:f_off + c] = True
+        g = dfeat.view(n, feat_ld)[:, f_off:f_off + c]
+        r, a = head_pool_bwd(g, dims, k, keep, rate)
+        yd = dx.view5()
+        vs.append(compare(f"dx {tag}", yd, r, a, 1 if P == 1 else P, dtype, kind))
+        dead = (a == 0)
+        vs.append(Exact(f"dx dropped == 0 {tag}", bool((yd[dead] == 0).all()), f"{int(dead.sum())} dead"))
+        wide = dx.buf[: dx.pixels * dx.ld].view(-1, dx.ld)
+        pad = torch.ones(dx.ld, dtype=torch.bool, device=dev)
+        pad[p["off"]:p["off"] + c] = False
+        vs.append(Exact(f"dx padding {tag}", bool((wide[:, pad] == FEAT_SENTINEL).all()), f"{int(pad.sum())} columns"))
+    vs.append(Exact(f"feat sentinel {case['name']}", bool((fv[:, ~written] == FEAT_SENTINEL).all()),
+                    f"{int((~written).sum())} columns"))
+    return vs
+
+
+# ----------------------------------------------------------------------------- linear
+def fc_fwd(feat, w, b):
+    f_, w_ = feat.to(F64), w.to(F64)
+    r, a = f_ @ w_.t(), f_.abs() @ w_.abs().t()
+    if b is not None:
+        r, a = r + b.to(F64), a + b.to(F64).abs()
+    return r, a
+
+
+def fc_bwd(dl, feat, w, dw_in, db_in):
+    """-> (dfeat, a), (dw_in + dl^T feat, a), (db_in + sum dl, a)"""
+    d, f_, w_ = dl.to(F64), feat.to(F64), w.to(F64)
+    dfeat = (d @ w_, d.abs() @ w_.abs())
+    dw = (dw_in.to(F64) + d.t() @ f_, dw_in.to(F64).abs() + d.abs().t() @ f_.abs())
+    db = (db_in.to(F64) + d.sum(0), db_in.to(F64).abs() + d.abs().sum(0))
+    return dfeat, dw, db
+
+
+FC_CASES = [(3, 70, 11), (3, 70, 7), (5, 64, 9), (1, 1, 1), (32, 2304, 249)]      # the last one is the real head
+FC_MODES = [("fused", True), ("split", True), ("fused", False)]                   # (launch form, bias and db present)
+
+
+def check_fc(be, dev, case, mode, bias: bool, seed_no: int = 0) -> List:
+    n, f, k = case
+    gen = torch.Generator().manual_seed(200 + seed_no)
+    st = _stream(dev)
+    rn = lambda *s, scale=1.0: (torch.randn(*s, generator=gen) * scale).to(dev)
+    feat, w = rn(n * f), rn(k * f, scale=f ** -0.5)
+    b = rn(k) if bias else None
+    dl = rn(n * k, scale=1.0 / n)
+    dw_in, db_in = rn(k * f), rn(k)
+    logits = torch.full((n * k,), float("nan"), device=dev)
+    dfeat = torch.full((n * f,), float("nan"), device=dev)
+    dw, db = dw_in.clone(), (db_in.clone() if bias else None)
+    be.fc_fwd(feat, w, b, logits, n, f, k)(st)
+    if mode == "fused":
+        be.fc_bwd(dl, feat, w, dfeat, dw, db, n, f, k)(st)
+    else:                                  # as the engine runs it: dfeat on the trunk, dw / db on the filter-gradient lane
+        be.fc_bwd(dl, feat, w, dfeat, None, None, n, f, k)(st)
+        be.fc_bwd(dl, feat, w, None, dw, db, n, f, k)(st)
+    _sync(dev)
+    tag = f"n{n}-f{f}-k{k}-{mode}{'' if bias else '-nobias'}"
+    r, a = fc_fwd(feat.view(n, f), w.view(k, f), b)
+    vs = [compare(f"logits {tag}", logits, r, a, f, F32, "sum_f32")]
+    (rf, af), (rw, aw), (rb, ab) = fc_bwd(dl.view(n, k), feat.view(n, f), w.view(k, f), dw_in.view(k, f), db_in)
+    vs.append(compare(f"dfeat {tag}", dfeat, rf, af, k, F32, "sum_f32"))
+    vs.append(compare(f"dw {tag}", dw, rw, aw, n, F32, "sum_f32"))
+    if bias:
+        vs.append(compare(f"db {tag}", db, rb, ab, n, F32, "sum_f32"))
+    return vs
+
+
+# ----------------------------------------------------------------------------- softmax cross-entropy
+def softmax_ce(logits: torch.Tensor, labels: torch.Tensor, gscale: float, diff_term: bool = True):
+    """float64 from the float32 logits: -> dict(dl, a (the extra term folded in, see the module docstring), loss, a_loss,
+    correct = rows whose FIRST maximum is the label).  diff_term False: the bound without that term, for the pin that
+    shows an honest float32 softmax needs it"""
+    x = logits.to(F64)
+    n, k = x.shape
+    gs = f32(gscale)
+    mx = x.max(1, keepdim=True).values
+    d = x - mx
+    e = d.exp()
+    s = e.sum(1, keepdim=True)
+    p = e / s
+    onehot = torch.zeros_like(p)
+    onehot[torch.arange(n, device=x.device), labels] = 1.0
+    dl = (p - onehot) / n * gs
+    a = (p + onehot) / n * abs(gs)
+    dist = torch.where(torch.isinf(d), torch.zeros_like(d), -d)               # |x - max|; p is exactly 0 where it is inf
+    extra = 2.0 * EPS32 * (dist * p + p * (p * dist).sum(1, keepdim=True)) / n * abs(gs)
+    a_eff = a + (extra / (EPS32 * (16.0 + 2.0 * math.sqrt(k))) if diff_term else 0.0)   # elem_bound(r, a_eff, k) = its own + extra
+    xl = x.gather(1, labels.view(n, 1))
+    loss = (s.log() + mx - xl).sum() / n
+    a_loss = (s.log().abs() + mx.abs() + xl.abs()).sum() / n
+    idx = torch.arange(k, device=x.device).expand(n, k)
+    first = torch.where(x == mx, idx, torch.full_like(idx, k)).min(1).values
+    return dict(dl=dl, a=a_eff, loss=loss, a_loss=a_loss, correct=int((first == labels).sum()))
+
+
+CE_K = [1, 11, 249, 256, 257, 600]
+CE_N = [1, 5]
+CE_GSCALE = [1.0, 0.37]
+CE_SETS = ["sd1", "sd40", "shift3e4", "equal", "neginf"]
+CE_CASES = [(k, n, gs, s) for k in CE_K for n in CE_N for gs in CE_GSCALE for s in CE_SETS if not (s == "neginf" and k < 2)]
+# (first index of the duplicated maximum, second index, label): i and i + 256 are one thread's consecutive strides, the
+# other pairs sit in different threads -- with the lower index in the lower and in the higher thread
+CE_TIES = [(40, 296, 40), (40, 296, 296), (17, 300, 17), (17, 300, 300), (200, 270, 200)]
+CE_TIE_K = 600
+
+
+def ce_logits(k, n, kind, gen):
+    x = torch.randn(n, k, generator=gen)
+    labels = torch.randint(0, k, (n,), generator=gen)
+    if kind == "sd40":
+        x = x * 40.0
+    elif kind == "shift3e4":
+        x = x + 3.0e4
+    elif kind == "equal":
+        x = torch.full((n, k), 1.25)
+    elif kind == "neginf":
+        x[torch.arange(n), (labels + 1) % k] = -float("inf")
+    return x, labels
+
+
+def ce_tie_logits(gen):
+    x = torch.randn(len(CE_TIES), CE_TIE_K, generator=gen)
+    for r, (i, j, _) in enumerate(CE_TIES):
+        x[r, i] = x[r, j] = 7.5
+    return x, torch.tensor([t[2] for t in CE_TIES])
+
+
+def _check_ce_run(be, dev, x, labels, gscale, tag) -> List:
+    """the training form onto preloaded accumulators, then the evaluation form (dlogits NULL, loss_out NULL) from zero"""
+    n, k = x.shape
+    st = _stream(dev)
+    x, labels = x.to(dev), labels.to(dev)
+    pre_l, pre_s, pre_c = 1.5, -2.25, 7
+    dl = torch.full((n, k), float("nan"), device=dev)
+    lo, ls = torch.full((1,), pre_l, device=dev), torch.full((1,), pre_s, device=dev)
+    co = torch.full((1,), pre_c, dtype=torch.int32, device=dev)
+    be.softmax_ce(x, labels, n, k, gscale, dl, lo, ls, co)(st)
+    ls2, co2 = torch.zeros(1, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    be.softmax_ce(x, labels, n, k, gscale, None, None, ls2, co2)(st)
+    _sync(dev)
+    ref = softmax_ce(x, labels, gscale)
+    vs = [compare(f"dlogits {tag}", dl, ref["dl"], ref["a"], k, F32, "map_f32")]
+    bnd = elem_bound(ref["dl"], ref["a"], k, F32)
+    rs, rb = dl.double().sum(1).abs(), bnd.sum(1)
+    ok = bool((torch.nan_to_num(rs, nan=float("inf")) <= rb).all())
+    vs.append(Exact(f"dlogits rows sum to 0 {tag}", ok, f"worst {float(torch.nan_to_num(rs / rb, nan=float('inf')).max()):.3g} of the bound"))
+    for name, got, pre in (("loss_out", lo, pre_l), ("loss_sum", ls, pre_s), ("loss_sum eval", ls2, 0.0)):
+        vs.append(ElemOnly(compare(f"{name} {tag}", got, ref["loss"] + pre, ref["a_loss"] + abs(pre), n, F32, "sum_f32")))
+    vs.append(Exact(f"correct {tag}", int(co[0]) == pre_c + ref["correct"], f"{int(co[0])} want {pre_c + ref['correct']}"))
+    vs.append(Exact(f"correct eval {tag}", int(co2[0]) == ref["correct"], f"{int(co2[0])} want {ref['correct']}"))
+    return vs
+
+
+def check_ce(be, dev, case, seed_no: int = 0) -> List:
+    k, n, gscale, kind = case
+    gen = torch.Generator().manual_seed(300 + seed_no + 7 * k + n)
+    x, labels = ce_logits(k, n, kind, gen)
+    return _check_ce_run(be, dev, x, labels, gscale, f"k{k}-n{n}-g{gscale}-{kind}")
+
+
+def check_ce_ties(be, dev) -> List:
+    """the batch of tie rows, then every row alone (n = 1), so each row's verdict on `correct` is its own"""
+    x, labels = ce_tie_logits(torch.Generator().manual_seed(399))
+    vs = _check_ce_run(be, dev, x, labels, 1.0, "ties")
+    for r in range(x.shape[0]):
+        vs += _check_ce_run(be, dev, x[r:r + 1].clone(), labels[r:r + 1].clone(), 0.37, f"tie-row{r}")
+    return vs
+
+
+# ----------------------------------------------------------------------------- Adam
+ADAM_LR, ADAM_BETAS, ADAM_EPS = 1e-3, (0.9, 0.999), 1e-8
+ADAM_GRID_CAP = 16384 * 1024                      # elements one trip of the capped grid covers (csrc/optim_misc.hip)
+ADAM_BIG = ADAM_GRID_CAP + 1029                   # crosses the cap, ends in the scalar tail
+ADAM_COUNTS = [1, 2, 3, 4, 5, 1023, 4096 + 1, 4096 + 2, 4096 + 3, ADAM_BIG]
+ADAM_STEPS0 = [0, 1, 9999]
+ADAM_GSCALE = [1.0, 0.5]
+ADAM_SHADOW = [None, F32, BF16]
+ADAM_PAD = 16
+ADAM_SENTINEL = 3.0
+
+
+def adam_cases(count):
+    """every (step preset, gscale, shadow) at the small counts; the 16.8 M-element count once"""
+    if count == ADAM_BIG:
+        return [(9999, 0.5, BF16)]
+    return [(s, g, sh) for s in ADAM_STEPS0 for g in ADAM_GSCALE for sh in ADAM_SHADOW]
+
+
+def adam_ref(p, g, m, v, t: int, lr, b1, b2, eps, gscale, abi: bool = True):
+    """float64 Adam.  abi: the hyper-parameters are the float32 values the C ABI carries, and 1 - beta is formed from them
+    (exact in float32: Sterbenz); otherwise Python doubles, as torch.optim.Adam and EmuBackend.adam take them."""
+    if abi:
+        lr, b1, b2, eps, gscale = f32(lr), f32(b1), f32(b2), f32(eps), f32(gscale)
+    p_, gg, m_, v_ = p.to(F64), g.to(F64) * gscale, m.to(F64), v.to(F64)
+    m1, a_m = b1 * m_ + (1 - b1) * gg, (b1 * m_).abs() + ((1 - b1) * gg).abs()
+    v1, a_v = b2 * v_ + (1 - b2) * gg * gg, b2 * v_ + (1 - b2) * gg * gg
+    bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
+    den = v1.sqrt() / math.sqrt(bc2) + eps
+    dp = -(lr / bc1) * m1 / den
+    return dict(m=m1, a_m=a_m, v=v1, a_v=a_v, dp=dp, p=p_ + dp, p0=p_, den=den, c1=lr / bc1, sbc2=math.sqrt(bc2))
+
+
+def adam_bounds(r):
+    """element bounds of m', v' (K = 2) and p' (K = 4, a = |p| + |dp|, plus the propagated rounding of m' and v')"""
+    bm = elem_bound(r["m"], r["a_m"], 2, F32)
+    bv = elem_bound(r["v"], r["a_v"], 2, F32)
+    a_p = r["p0"].abs() + r["dp"].abs()
+    # d dp / d m' = -c1 / den;  d dp / d v' = c1 m' / den^2 / (2 sqrt(v') sqrt(bc2)); sqrt(v' (1 +- e)) moves by sqrt(v') e / 2
+    sq = r["v"].sqrt()
+    dsq = torch.minimum(bv / (2.0 * sq).clamp_min(1e-300), bv.sqrt())        # |sqrt(v' + e) - sqrt(v')| <= both
+    prop = r["c1"] / r["den"] * bm + r["c1"] * r["m"].abs() / (r["den"] * r["den"]) * dsq / r["sbc2"]
+    return bm, bv, a_p, prop
+
+
+def compare_p(name, y, r) -> "ref64.Verdict":
+    """ref64.compare with `prop` folded into a, as softmax_ce folds its term: bound = elem_bound(p', |p| + |dp|, 4) + prop"""
+    _, _, a_p, prop = adam_bounds(r)
+    return compare(name, y, r["p"], a_p + prop / (EPS32 * (16.0 + 2.0 * math.sqrt(4.0))), 4, F32, "map_f32")
+
+
+def adam_inputs(count, step0, gen):
+    """on gen's device: p with a quarter of its entries at 1e-8 N(0,1); gradients of magnitude 1e-12 .. 1; m, v of the
+    gradients' scale (zero before the first step); a block of entries with g = m = v = 0"""
+    dev = gen.device
+    rn = lambda: torch.randn(count, generator=gen, device=dev)
+    ru = lambda: torch.rand(count, generator=gen, device=dev)
+    s = 10.0 ** (-12.0 * ru())
+    p = rn()
+    p[1::4] *= 1e-8
+    g = rn() * s
+    if step0 == 0:
+        m, v = torch.zeros(count, device=dev), torch.zeros(count, device=dev)
+    else:
+        m = 0.3 * rn() * s
+        v = (0.25 + ru()) * s * s
+    z0, z1 = count // 2, count // 2 + count // 8
+    g[z0:z1], m[z0:z1], v[z0:z1] = 0.0, 0.0, 0.0
+    return p, g, m, v, (z0, z1)
+
+
+def _padded(x, dev, dtype=F32):
+    out = torch.full((x.numel() + ADAM_PAD,), ADAM_SENTINEL, dtype=dtype, device=dev)
+    out[: x.numel()] = x.to(dtype)
+    return out
+
+
+def check_adam(be, dev, count, step0, gscale, shadow_dtype, with_torch: bool = True, seed_no: int = 0):
+    """one launch against the ABI reference, the torch.optim.Adam distance, the sentinels, the shadow and the zero block.
+    -> (verdicts, worst kernel-to-torch distance in ulps of the updated p)"""
+    gen = torch.Generator(device=dev).manual_seed(400 + seed_no + count % 1000 + step0)
+    p0, g0, m0, v0, (z0, z1) = adam_inputs(count, step0, gen)
+    st = _stream(dev)
+    p, g, m, v = (_padded(x, dev) for x in (p0, g0, m0, v0))
+    sh = None if shadow_dtype is None else torch.full((count + ADAM_PAD,), ADAM_SENTINEL, dtype=shadow_dtype, device=dev)
+    step = torch.full((1,), step0, dtype=torch.int64, device=dev)
+    lr, (b1, b2), eps = ADAM_LR, ADAM_BETAS, ADAM_EPS
+    be.adam(p, g, m, v, count, lr, b1, b2, eps, gscale, step, sh)(st)
+    _sync(dev)
+    tag = f"count {count} step {step0 + 1} gscale {gscale} shadow {shadow_dtype}"
+    r = adam_ref(p0, g0, m0, v0, step0 + 1, lr, b1, b2, eps, gscale)
+    vs = [Exact(f"step {tag}", int(step[0]) == step0 + 1, f"{int(step[0])}"),
+          compare(f"m {tag}", m[:count], r["m"], r["a_m"], 2, F32, "map_f32"),
+          compare(f"v {tag}", v[:count], r["v"], r["a_v"], 2, F32, "map_f32"),
+          compare_p(f"p {tag}", p[:count], r)]
+    same = torch.equal(p[z0:z1].view(torch.int32), p0[z0:z1].view(torch.int32))
+    vs.append(Exact(f"zero block keeps p {tag}", same, f"{z1 - z0} entries"))
+    tails = [p, m, v, g] + ([sh] if sh is not None else [])
+    vs.append(Exact(f"sentinels {tag}", all(bool((x[count:].float() == ADAM_SENTINEL).all()) for x in tails), f"{ADAM_PAD} x {len(tails)}"))
+    if sh is not None:
+        vs.append(Exact(f"shadow {tag}", torch.equal(sh[:count], p[:count].to(shadow_dtype)), str(shadow_dtype)))
+    dist = float("nan")
+    if with_torch:
+        tp = p0.clone().requires_grad_(True)
+        opt = torch.optim.Adam([tp], lr=lr, betas=(b1, b2), eps=eps, foreach=False)
+        opt.state[tp] = dict(step=torch.tensor(float(step0)), exp_avg=m0.clone(), exp_avg_sq=v0.clone())
+        tp.grad = g0 * gscale                     # gscale 1 and 0.5: exact
+        opt.step()
+        rd = adam_ref(p0, g0, m0, v0, step0 + 1, lr, b1, b2, eps, gscale, abi=False)
+        (_, _, a1, pr1), (_, _, a2, pr2) = adam_bounds(r), adam_bounds(rd)
+        tol = (elem_bound(r["p"], a1, 4, F32) + pr1) + (r["p"] - rd["p"]).abs() + (elem_bound(rd["p"], a2, 4, F32) + pr2)
+        d = (p[:count].double() - tp.detach().double()).abs()
+        dist = float((d / ulp_out(rd["p"], F32)).max())
+        ratio = float((d / tol).max())
+        vs.append(Exact(f"torch.optim.Adam {tag}", ratio <= 1.0, f"worst {ratio:.3g} of the allowance, {dist:.3g} ulp of p"))
+    return vs, dist
+
+
+def check_adam_split(be, dev, count, cut, step0, gscale, shadow_dtype=None, seed_no: int = 0) -> List:
+    """[cut:] with the step counter, then [:cut] with a scratch counter set to step - 1 (Engine.adam_split_ops as TrainStep
+    drives it), bit for bit against the single launch from the same state"""
+    gen = torch.Generator(device=dev).manual_seed(500 + seed_no + count % 1000 + cut)
+    p0, g0, m0, v0, _ = adam_inputs(count, step0, gen)
+    st = _stream(dev)
+    lr, (b1, b2), eps = ADAM_LR, ADAM_BETAS, ADAM_EPS
+    mk = lambda: [_padded(x, dev) for x in (p0, g0, m0, v0)]
+    mksh = lambda: None if shadow_dtype is None else torch.full((count + ADAM_PAD,), ADAM_SENTINEL, dtype=shadow_dtype, device=dev)
+    p, g, m, v = mk()
+    sh = mksh()
+    step = torch.full((1,), step0, dtype=torch.int64, device=dev)
+    be.adam(p, g, m, v, count, lr, b1, b2, eps, gscale, step, sh)(st)
+    P, G, M, V = mk()
+    SH = mksh()
+    step2 = torch.full((1,), step0, dtype=torch.int64, device=dev)
+    tail = torch.zeros(1, dtype=torch.int64, device=dev)
+    be.adam(P[cut:], G[cut:], M[cut:], V[cut:], count - cut, lr, b1, b2, eps, gscale, step2, None if SH is None else SH[cut:])(st)
+    torch.sub(step2, 1, out=tail)
+    be.adam(P[:cut], G[:cut], M[:cut], V[:cut], cut, lr, b1, b2, eps, gscale, tail, None if SH is None else SH[:cut])(st)
+    _sync(dev)
+    tag = f"count {count} cut {cut} step {step0 + 1}"
+    bits = lambda a, b: torch.equal(a.view(torch.int32), b.view(torch.int32))
+    vs = [Exact(f"split {n_} {tag}", bits(a, b), "bit-equal to one launch") for n_, a, b in (("p", P, p), ("m", M, m), ("v", V, v))]
+    vs.append(Exact(f"split counters {tag}", int(step2[0]) == step0 + 1 == int(tail[0]) == int(step[0]), f"{int(step2[0])}, {int(tail[0])}"))
+    if sh is not None:
+        vs.append(Exact(f"split shadow {tag}", torch.equal(SH, sh), str(shadow_dtype)))
+    return vs
+
+
+class AbiAdam:
+    """a float32 evaluation of sfk_adam's contract, operation by operation as csrc/optim_misc.hip states it (float32
+    hyper-parameters, 1 - beta from them, bias corrections in double and rounded to float32, the step read after the
+    increment).  Mix-in over a backend; the class attributes switch on the mutations the CPU pins must see rejected."""
+    step_off = 0                 # 1: step - 1 in the bias corrections
+    no_eps = False
+    gscale_on_g_only = False     # g * gscale in m, g (unscaled) squared in v
+    skip_mod4_tail = False       # the last count % 4 elements are not updated
+    grid_cap = None              # elements beyond it are not updated
+
+    def adam(self, p, g, m, v, count, lr, b1, b2, eps, gscale, step, shadow=None):
+        def run(stream):
+            step.add_(1)
+            t = int(step[0]) - self.step_off
+            f = np.float32
+            lr_, b1_, b2_, eps_, gs_ = f(lr), f(b1), f(b2), f(0.0 if self.no_eps else eps), f(gscale)
+            with np.errstate(divide="ignore"):
+                bc1, bc2 = f(1.0 - float(b1_) ** t), f(1.0 - float(b2_) ** t)
+                step_size, inv_sqrt_bc2 = f(lr_ / bc1), f(f(1.0) / np.sqrt(bc2))
+            n_upd = count
+            if self.skip_mod4_tail:
+                n_upd = count - count % 4
+            if self.grid_cap is not None:
+                n_upd = min(n_upd, self.grid_cap)
+            gj = g[:n_upd] * float(gs_)
+            gv = g[:n_upd] if self.gscale_on_g_only else gj
+            m1 = float(b1_) * m[:n_upd] + float(f(1.0) - b1_) * gj
+            v1 = float(b2_) * v[:n_upd] + float(f(1.0) - b2_) * gv * gv
+            p1 = p[:n_upd] - float(step_size) * m1 / (v1.sqrt() * float(inv_sqrt_bc2) + float(eps_))
+            m[:n_upd], v[:n_upd], p[:n_upd] = m1, v1, p1
+            if shadow is not None:
+                shadow[:n_upd].copy_(p[:n_upd])
+        return run
