@@ -233,6 +233,15 @@ class _PoolDesc(C.Structure):
                 ("lut", C.c_void_p), ("fill", C.c_int32), ("out", C.c_void_p)]
 
 
+class _PoolCropDesc(C.Structure):
+    """include/sfk_resident.h sfk_pool_crop_desc: sfk_pool_desc plus the per-clip crop table (n, 2) = (top, left), or NULL,
+    and RandomCrop's pad"""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_int32), ("pool", C.c_void_p), ("frame_stride", C.c_int64),
+                ("row_stride", C.c_int64), ("pixel_pitch", C.c_int32), ("frames", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("c0", C.c_int32), ("c", C.c_int32), ("n", C.c_int32), ("t", C.c_int32), ("index", C.c_void_p),
+                ("lut", C.c_void_p), ("crop", C.c_void_p), ("fill", C.c_int32), ("pad", C.c_int32), ("out", C.c_void_p)]
+
+
 class _ResizeDesc(C.Structure):
     """include/sfk_resize.h sfk_resize_desc: frame f is the contiguous HWC bytes src[offset[f] ...] of hw[f] = (h, w) pixels
     and c channels; its padded, cubic-resized (size, size, c) frame lands at out + f*out_frame_stride"""
@@ -376,6 +385,13 @@ SIGNATURES_RESIZE = {
     "sfk_resize_abi_version": [],
     "sfk_u8_pad_resize_cubic": [C.POINTER(_ResizeDesc), _PV],
 }
+# include/sfk_resident.h: the device-resident train set (cropped clips gathered from the frame pool), same library, its own
+# header and version
+RESIDENT_ABI_VERSION = 1   # include/sfk_resident.h SFK_RESIDENT_ABI_VERSION
+SIGNATURES_RESIDENT = {
+    "sfk_resident_abi_version": [],
+    "sfk_u8_pool_gather_crop": [C.POINTER(_PoolCropDesc), _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
@@ -423,6 +439,12 @@ def new_pool_desc() -> "_PoolDesc":
     return d
 
 
+def new_pool_crop_desc() -> "_PoolCropDesc":
+    d = _PoolCropDesc()
+    d.struct_size = C.sizeof(_PoolCropDesc)
+    return d
+
+
 def new_resize_desc() -> "_ResizeDesc":
     d = _ResizeDesc()
     d.struct_size = C.sizeof(_ResizeDesc)
@@ -447,7 +469,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
                        "(there is no CPU or PyTorch fallback for the SlowFast path)")
     lib = C.CDLL(path)
     for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL,
-                  SIGNATURES_RESIZE):
+                  SIGNATURES_RESIZE, SIGNATURES_RESIDENT):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -466,6 +488,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk pool ABI version mismatch: library {lib.sfk_pool_abi_version()}, binding {POOL_ABI_VERSION}")
     if lib.sfk_resize_abi_version() != RESIZE_ABI_VERSION:
         raise SfkError(f"libsfk resize ABI version mismatch: library {lib.sfk_resize_abi_version()}, binding {RESIZE_ABI_VERSION}")
+    if lib.sfk_resident_abi_version() != RESIDENT_ABI_VERSION:
+        raise SfkError(f"libsfk resident ABI version mismatch: library {lib.sfk_resident_abi_version()}, binding {RESIDENT_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -978,6 +1002,27 @@ class HipBackend:
         d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
         d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
         return self._plain("sfk_u8_pool_gather", C.byref(d), keep=(d, pool, index, lut, out))
+
+    def u8_pool_gather_crop(self, pool, index, lut, fill: int, crop, pad: int, out, c0: int = 0, c: Optional[int] = None):
+        """sfk_u8_pool_gather_crop (include/sfk_resident.h): ``u8_pool_gather`` with RandomCrop's shift -- crop (N,2) int32
+        (top, left) on the device, read when the launch runs, or None (no shift); out[n,t,ch,y,x] is 0 where
+        (y + top - pad, x + left - pad) lies outside the frame, else the gathered value (lut[fill] for a missing frame)."""
+        f, h, w, p = pool.shape
+        c = p - c0 if c is None else c
+        assert pool.dtype == torch.uint8 and pool.stride(3) == 1 and 0 <= c0 and 0 < c and c0 + c <= p
+        assert index.dtype == torch.int32 and index.dim() == 2 and index.is_contiguous()
+        n, t = index.shape
+        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
+        assert out.is_contiguous() and tuple(out.shape) == (n, t, c, h, w), (tuple(out.shape), (n, t, c, h, w))
+        if crop is not None:
+            assert crop.dtype == torch.int32 and tuple(crop.shape) == (n, 2) and crop.is_contiguous()
+            assert crop.device == index.device
+        d = new_pool_crop_desc()
+        d.out_dtype, d.pool, d.index, d.lut, d.out = _DT[out.dtype], pool.data_ptr(), index.data_ptr(), lut.data_ptr(), out.data_ptr()
+        d.crop, d.pad = (None if crop is None else crop.data_ptr()), int(pad)
+        d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
+        d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
+        return self._plain("sfk_u8_pool_gather_crop", C.byref(d), keep=(d, pool, index, lut, crop, out))
 
     def u8_pad_resize_cubic(self, src, offset, hw, out, size: int, max_side: int, fill: int):
         """sfk_u8_pad_resize_cubic (include/sfk_resize.h): src 1-D uint8, the frames' HWC bytes; offset (F,) int64 and hw (F, 2)

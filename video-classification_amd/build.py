@@ -8,7 +8,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsfk.so")
 SOURCES = ["conv_igemm.hip", "conv_igemm_p8.hip", "conv_halo.hip", "conv_pw.hip", "conv_wgrad.hip", "conv_wgrad_p8.hip", "conv_wgrad_band.hip", "stem_conv.hip", "bn.hip", "bn_tail.hip", "pool_head.hip",
-           "optim_misc.hip", "eval_input.hip", "stem2d.hip", "roi_resize.hip", "sgd.hip", "color_jitter.hip", "frame_pool.hip", "pad_resize.hip"]
+           "optim_misc.hip", "eval_input.hip", "stem2d.hip", "roi_resize.hip", "sgd.hip", "color_jitter.hip", "frame_pool.hip", "pad_resize.hip", "frame_pool_crop.hip"]
 
 
 def _newer(a, b):
@@ -24,7 +24,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     deps = [os.path.join(CSRC, "sfk_common.h"), os.path.join(CSRC, "conv_igemm_epi.h"), os.path.join(CSRC, "conv_wgrad_common.h"), os.path.join(CSRC, "conv_wgrad_band_acc.inc"), os.path.join(ROOT, "include", "sfk.h"),
             os.path.join(ROOT, "include", "sfk_stem2d.h"), os.path.join(ROOT, "include", "sfk_u8stem.h"),
             os.path.join(ROOT, "include", "sfk_v2.h"), os.path.join(ROOT, "include", "sfk_aug.h"),
-            os.path.join(ROOT, "include", "sfk_pool.h"), os.path.join(ROOT, "include", "sfk_resize.h")]
+            os.path.join(ROOT, "include", "sfk_pool.h"), os.path.join(ROOT, "include", "sfk_resize.h"),
+            os.path.join(ROOT, "include", "sfk_resident.h")]
     flags = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
     flags += os.environ.get("SFK_EXTRA_FLAGS", "").split()          # experiment builds (tools/), with SFK_LIB_OUT
 

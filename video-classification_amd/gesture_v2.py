@@ -275,6 +275,8 @@ class Trainer(_train.Trainer):
     last smaller batch, uniform non-overlapping test windows; checkpoints, eval and the multi-process path as train.Trainer."""
     train_drop_last = False                              # :815
     momentum = 0.9                                       # :832
+    resident_refused = ("gesture_v2's frames are uncropped 240 x 320 x 7 and go through RoiResize, which has no index table "
+                        "to gather them from a frame pool")
 
     def _model_manager(self, cfg, device, backend):
         return ModelManager(cfg, device=device, backend=backend)

@@ -198,9 +198,12 @@ class FramePool:
     clips of any mix of rows with one ``sfk_u8_pool_gather`` launch; ``release`` returns a video's slots once its last window
     has been gathered.  A video whose windows straddle two batches simply stays in the arena until then.  Every copy and
     launch goes on the current stream, so a slot is never overwritten before the gather that read it has run.
-    ``bytes_uploaded`` counts the frame bytes sent host to device."""
+    ``bytes_uploaded`` counts the frame bytes sent host to device.
+    capacity: a FIXED number of arena slots -- the arena is allocated once, at the first ``add``, and never grows or moves
+    (a video that finds no room is a RuntimeError; ``fits`` asks beforehand); ``gather`` with a crop table builds the
+    RandomCrop-ped train clips with ``sfk_u8_pool_gather_crop`` (include/sfk_resident.h).  ``ResidentTrainSet`` uses both."""
 
-    def __init__(self, device="cuda", backend=None, fill: int = MISSING_BYTE):
+    def __init__(self, device="cuda", backend=None, fill: int = MISSING_BYTE, capacity: Optional[int] = None):
         if backend is None:
             from ._lib import HipBackend
             backend = HipBackend()              # raises when libsfk.so is missing: no CPU path
@@ -210,6 +213,9 @@ class FramePool:
         self.live = {}                          # base -> frames of that video
         self.bytes_uploaded = 0
         self._resize = {}                       # (size, channels) -> the PadResize of add_raw
+        self.capacity = None if capacity is None else int(capacity)
+        if self.capacity is not None and self.capacity <= 0:
+            raise ValueError(f"FramePool: capacity {capacity} frames")
 
     def _h2d(self, t: torch.Tensor) -> torch.Tensor:
         if t.device.type == "cpu" and self.device.type == "cuda" and not t.is_pinned():
@@ -243,14 +249,30 @@ class FramePool:
     def _reserve(self, f: int, frame_shape: tuple) -> int:
         """the base of a free run of f arena slots of frame_shape (the arena grows, or starts over in a new shape when empty)"""
         if self.arena is not None and tuple(self.arena.shape[1:]) != tuple(frame_shape):
-            if self.live:
+            if self.live or self.capacity is not None:
                 raise ValueError(f"frames of {tuple(frame_shape)} in a pool of {tuple(self.arena.shape[1:])}")
             self.arena = None
+        if self.capacity is not None:           # a fixed arena: allocated once, never grown, never moved
+            if self.arena is None and f <= self.capacity:
+                self.arena = torch.empty((self.capacity,) + tuple(frame_shape), dtype=torch.uint8, device=self.device)
+            base = self._place(f)
+            if base is None:
+                raise RuntimeError(f"FramePool: no room for {f} more frames in its fixed capacity of {self.capacity} "
+                                   f"({sum(self.live.values())} in use)")
+            return base
         base = self._place(f)
         if base is None:
             self._grow(f, frame_shape)
             base = self._place(f)
         return base
+
+    def fits(self, f: int) -> bool:
+        """would ``add`` of f frames find room?  (a pool without a capacity grows: always)"""
+        if self.capacity is None:
+            return True
+        if self.arena is None:
+            return 0 < int(f) <= self.capacity
+        return self._place(int(f)) is not None
 
     def add(self, video_frames: torch.Tensor, windows: Optional[torch.Tensor] = None) -> int:
         """upload (F, S, S, P) uint8 frames; windows, when given, is checked against F BEFORE anything is uploaded"""
@@ -300,8 +322,10 @@ class FramePool:
         del self.live[base]
 
     def gather(self, index_rows: torch.Tensor, out_dtype: torch.dtype = torch.float32, c0: int = 0,
-               c: Optional[int] = None) -> torch.Tensor:
-        """(N, T) arena slots (or -1) -> the (N, T, c, S, S) clips DevicePreprocess would write from the materialised frames"""
+               c: Optional[int] = None, crop: Optional[torch.Tensor] = None, padding: Optional[int] = None) -> torch.Tensor:
+        """(N, T) arena slots (or -1) -> the (N, T, c, S, S) clips DevicePreprocess would write from the materialised frames;
+        crop (N, 2) int32 (top, left): with that RandomCrop (padding defaults to S // 10, as DevicePreprocess's), by ONE
+        ``sfk_u8_pool_gather_crop`` launch instead of the ``sfk_u8_pool_gather`` one"""
         idx = torch.as_tensor(index_rows, dtype=torch.int32).contiguous()
         assert idx.dim() == 2 and idx.numel() > 0 and self.arena is not None
         ok = torch.zeros(self.arena.shape[0] + 1, dtype=torch.bool)      # the last entry stands for -1
@@ -314,6 +338,13 @@ class FramePool:
         c = p - c0 if c is None else c
         out = torch.empty(idx.shape[0], idx.shape[1], c, h, w, dtype=out_dtype, device=self.device)
         stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+        if crop is not None:
+            crop = torch.as_tensor(crop).to(torch.int32).contiguous()
+            assert tuple(crop.shape) == (idx.shape[0], 2), tuple(crop.shape)
+            padding = h // 10 if padding is None else int(padding)
+            self.be.u8_pool_gather_crop(self.arena, self._h2d(idx), self.lut, self.fill, self._h2d(crop), padding, out, c0,
+                                        c)(stream)
+            return out
         self.be.u8_pool_gather(self.arena, self._h2d(idx), self.lut, self.fill, out, c0, c)(stream)
         return out
 
@@ -580,3 +611,183 @@ class RoiResize:
         stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
         self.be.roi_resize(x, self.lut, box, out, self.antialias, crop, pad)(stream)
         return out
+
+
+# ---- the device-resident train set (MODEL.RESIDENT_TRAIN)
+RESIDENT_METHODS = ("seq_len", "label", "video_item")
+
+
+def offers_resident(train_set) -> bool:
+    """does the dataset offer the three cheap methods ``ResidentTrainSet`` reads it through?"""
+    return all(callable(getattr(train_set, m, None)) for m in RESIDENT_METHODS)
+
+
+class _VideoRequests(torch.utils.data.Dataset):
+    """the reads an epoch of ``ResidentTrainSet`` still needs, in plan order: (video, None) = the whole video, (video,
+    indices) = those frames only; a DataLoader over it lets workers decode ahead of the step that consumes them"""
+
+    def __init__(self, train_set, requests):
+        self.train_set, self.requests = train_set, requests
+
+    def __len__(self):
+        return len(self.requests)
+
+    def __getitem__(self, k):
+        i, indices = self.requests[k]
+        return self.train_set.video_item(i) if indices is None else self.train_set.video_item(i, indices)
+
+
+class ResidentTrainSet:
+    """The train set of the v1 loader with its decoded frames kept on the device: one ``FramePool(capacity=)`` arena, a
+    deterministic sampling plan drawn here, in the main process, and a dataset that is consulted only for frames that are not
+    on the device yet.  The reference's train loop draws one random window per video per epoch (dataset/chalearn_dataset.py:
+    123-129) and decodes its frames again every time; here a video is decoded ONCE, when a clip first touches it, and every
+    batch after that is one ``sfk_u8_pool_gather_crop`` launch (include/sfk_resident.h) plus the H2D of two small tables.
+
+    train_set offers ``seq_len(i)`` (frame names of video i, nothing read), ``label(i)`` (0-based) and ``video_item(i,
+    indices=None)`` (``make_pooled_item`` / ``make_raw_pooled_item`` over those frames, default all, 'windows' of shape
+    (1, len(indices))).
+
+    Arena: capacity_frames slots (default floor(MODEL.RESIDENT_GB * 2^30 / (S*S*21))); the last batch_size * CLIP_LEN of
+    them are the spill region, the rest the resident region.
+    Plan: a function of (seed, epoch) only.  ``plan(e)`` = the batches of torch.randperm(len, manual_seed(seed + e)), each
+    (videos, indices (N, T), crop (N, 2), jitter (N, 8) | None); per clip a generator seeded from (seed, epoch, video) draws
+    the start (random_sampling: randint(0, max(0, seq_len - clip_len)), indices (start + k) % seq_len), then the crop
+    (``draw_crop_offsets``), then, under MODEL.COLOR_JITTER, the jitter row (``draw_color_jitter``).
+    Residency: decided in plan order and never revoked.  A video met for the first time becomes resident if resident_used +
+    seq_len(i) still fits the resident region: it is read whole, once, and kept for the life of this object.  One that does
+    not fit is spilled: only its clip's distinct frames are read, into slots released right after the batch's gather is
+    enqueued (stream order keeps them intact until that gather has run).  Within a batch the resident uploads precede the
+    spilled ones, so the resident videos pack densely from slot 0 and the spills never fragment their region.
+    ``epoch(e)`` yields {'<key>': (N, T, 21, S, S) float32 on the device, 'label': (N,), optionally 'jitter': (N, 8)}: what
+    every model's prepare_data takes under the float key (like pooled eval, whatever MODEL.U8_STEM says).
+    Counters: bytes_uploaded (the pool's), resident_videos, resident_frames (arena slots they hold), spilled_clips (of the
+    epoch running or last run), spill_peak (most spill slots ever live at once)."""
+
+    def __init__(self, train_set, cfg, device="cuda", backend=None, batch_size: int = 1, drop_last: bool = True, seed: int = 0,
+                 capacity_frames: Optional[int] = None, num_workers: int = 0, jitter=None):
+        if not offers_resident(train_set):
+            raise ValueError("ResidentTrainSet: the train set must offer seq_len(i), label(i) and video_item(i, indices=None)")
+        from .config import crop_resize_dict
+        self.train_set, self.cfg, self.device = train_set, cfg, torch.device(device)
+        self.key = cfg.MODEL.R3D_INPUT
+        self.size = int(crop_resize_dict[self.key])
+        self.clip_len = int(cfg.CHALEARN.CLIP_LEN)
+        self.batch_size, self.drop_last, self.seed = int(batch_size), bool(drop_last), int(seed)
+        self.num_workers, self.jitter = int(num_workers), (None if jitter is None else tuple(jitter))
+        if capacity_frames is None:
+            capacity_frames = int(float(cfg.MODEL.RESIDENT_GB) * 2 ** 30 // (self.size * self.size * 21))
+        self.capacity, self.spill_slots = int(capacity_frames), self.batch_size * self.clip_len
+        self.resident_slots = self.capacity - self.spill_slots
+        if self.resident_slots <= 0:
+            raise ValueError(f"ResidentTrainSet: {self.capacity} arena frames leave no resident slot beside the spill region of "
+                             f"batch_size * CLIP_LEN = {self.spill_slots}")
+        self.pool = FramePool(self.device, backend, capacity=self.capacity)
+        self._seq_len = {}                      # video -> seq_len(i), asked once
+        self._resident = {}                     # video -> True (resident) | False (spilled for good), in decision order
+        self._rows = {}                         # loaded resident video -> (seq_len,) int32 arena slot of every frame, -1 missing
+        self.resident_used = 0                  # sum of seq_len over the videos decided resident
+        self.resident_frames = 0
+        self.spilled_clips = 0
+        self.spill_peak = 0
+
+    # ---- counters
+    @property
+    def bytes_uploaded(self) -> int:
+        return self.pool.bytes_uploaded
+
+    @property
+    def resident_videos(self) -> int:
+        return len(self._rows)
+
+    # ---- the plan: pure host
+    def seq_len(self, i: int) -> int:
+        if i not in self._seq_len:
+            self._seq_len[i] = int(self.train_set.seq_len(i))
+            assert self._seq_len[i] >= 1, (i, self._seq_len[i])
+        return self._seq_len[i]
+
+    def _clip_generator(self, epoch: int, video: int) -> torch.Generator:
+        return torch.Generator().manual_seed(((self.seed * 1000003 + int(epoch)) * 1000003 + int(video)) % (2 ** 63 - 1))
+
+    def plan(self, epoch: int) -> list:
+        n = len(self.train_set)
+        order = torch.randperm(n, generator=torch.Generator().manual_seed(self.seed + int(epoch))).tolist()
+        batches = []
+        for at in range(0, n, self.batch_size):
+            videos = order[at:at + self.batch_size]
+            if len(videos) < self.batch_size and self.drop_last:
+                break
+            indices, crop, jitter = [], [], []
+            for v in videos:
+                g, length = self._clip_generator(epoch, v), self.seq_len(v)
+                start = int(torch.randint(0, max(0, length - self.clip_len) + 1, (1,), generator=g))
+                indices.append([(start + k) % length for k in range(self.clip_len)])
+                crop.append(draw_crop_offsets(1, self.size // 10, g)[0])
+                if self.jitter is not None:
+                    jitter.append(draw_color_jitter(1, *self.jitter, generator=g)[0])
+            batches.append((videos, torch.tensor(indices, dtype=torch.int32), torch.stack(crop),
+                            torch.stack(jitter) if jitter else None))
+        return batches
+
+    # ---- residency and loading
+    def _decide(self, video: int) -> bool:
+        if video not in self._resident:
+            fits = self.resident_used + self.seq_len(video) <= self.resident_slots
+            self._resident[video] = fits
+            if fits:
+                self.resident_used += self.seq_len(video)
+        return self._resident[video]
+
+    def _add(self, item) -> tuple:
+        """(base, (L,) int32 arena slot of every requested frame, -1 for a missing one) of a pooled or raw pooled item"""
+        windows = torch.as_tensor(item["windows"], dtype=torch.int32)
+        if rawpool_key(self.key) in item:
+            base = self.pool.add_raw(item[rawpool_key(self.key)], item["raw_hw"], self.size, windows)
+        else:
+            base = self.pool.add(item[pool_key(self.key)], windows)
+        return base, self.pool.rows(base, windows)[0]
+
+    def epoch(self, epoch: int):
+        plan = self.plan(epoch)
+        requests, per_batch = [], []            # per batch: (videos that become resident now, [(clip n, distinct indices)])
+        for videos, indices, _, _ in plan:
+            new, spill = [], []
+            for n, v in enumerate(videos):
+                if self._decide(v):
+                    if v not in self._rows:     # (a video occurs once an epoch: the order is a permutation)
+                        new.append(v)
+                else:
+                    spill.append((n, sorted(set(indices[n].tolist()))))
+            requests += [(v, None) for v in new] + [(videos[n], ind) for n, ind in spill]
+            per_batch.append((new, spill))
+        items = None
+        if requests:                            # an epoch with nothing to read builds no loader
+            items = iter(torch.utils.data.DataLoader(_VideoRequests(self.train_set, requests), batch_size=None, shuffle=False,
+                                                     num_workers=self.num_workers))
+        self.spilled_clips = 0
+        for (videos, indices, crop, jitter), (new, spill) in zip(plan, per_batch):
+            for v in new:                       # the resident uploads first: no spill slot is live, they pack densely
+                base, rows = self._add(next(items))
+                assert rows.numel() == self.seq_len(v), (v, rows.numel(), self.seq_len(v))
+                self._rows[v] = rows
+                self.resident_frames += self.pool.live[base]
+            table, bases = torch.empty_like(indices), []
+            spilled = dict(spill)
+            for n, v in enumerate(videos):
+                if n in spilled:
+                    base, rows = self._add(next(items))
+                    bases.append(base)
+                    slot = dict(zip(spilled[n], rows.tolist()))
+                    table[n] = torch.tensor([slot[k] for k in indices[n].tolist()], dtype=torch.int32)
+                else:
+                    table[n] = self._rows[v][indices[n].long()]
+            self.spilled_clips += len(bases)
+            self.spill_peak = max(self.spill_peak, sum(self.pool.live[b] for b in bases))
+            clip = self.pool.gather(table, torch.float32, 0, None, crop=crop)
+            for b in bases:                     # free for the uploads queued behind that gather on the same stream
+                self.pool.release(b)
+            batch = {self.key: clip, "label": torch.tensor([int(self.train_set.label(v)) for v in videos], dtype=torch.int64)}
+            if jitter is not None:
+                batch["jitter"] = jitter
+            yield batch

@@ -434,7 +434,10 @@ class SyntheticChalearn(torch.utils.data.Dataset):
     video from frames_per_video = (lo, hi), with the windows of ``uniform_windows(F, CLIP_LEN)``; nclips[i] is their count.
     raw=True: the raw transport's items (input_pipeline.make_raw_item / make_raw_pooled_item) -- every frame a crop of ragged
     (h, w), each side drawn from raw_side = (lo, hi) by a generator of the frame's own; a train item keeps the uint8 item's
-    'crop' (and 'jitter'), a test / valid item is one raw pooled video (raw implies pooled there)."""
+    'crop' (and 'jitter'), a test / valid item is one raw pooled video (raw implies pooled there).
+    An as_uint8 or raw set also offers what ``input_pipeline.ResidentTrainSet`` reads a train set through: ``seq_len(i)``
+    (vframes[i], drawn per video from frames_per_video by a generator of its own), ``label(i)`` and ``video_item(i, indices)``,
+    whose frame k of video i has the same bytes however it is asked for.  The items above keep their bytes."""
 
     def __init__(self, cfg, name_of_set: str, num_videos: int = 8, clips_per_video=(1, 3), seed: int = 0,
                  as_uint8: bool = False, pooled: bool = False, frames_per_video=(8, 40), raw: bool = False,
@@ -460,9 +463,35 @@ class SyntheticChalearn(torch.utils.data.Dataset):
             self.nframes = torch.randint(int(lo), int(hi) + 1, (num_videos,), generator=gp).tolist()
             self.windows = [uniform_windows(f, self.t) for f in self.nframes]
             self.nclips = [int(w.shape[0]) for w in self.windows]
+        gv = torch.Generator().manual_seed(seed * 86028121 + 3)                 # the resident view's frame counts: its own draws
+        self.vframes = torch.randint(int(frames_per_video[0]), int(frames_per_video[1]) + 1, (num_videos,), generator=gv).tolist()
 
     def __len__(self):
         return len(self.labels)
+
+    # ---- what input_pipeline.ResidentTrainSet reads a train set through
+    def seq_len(self, i) -> int:
+        return self.vframes[i]
+
+    def label(self, i) -> int:
+        return self.labels[i]
+
+    def _video_frame(self, i, k):
+        """frame k of video i of the resident view: (S, S, 21) random bytes, or ragged ones (raw), a generator of its own"""
+        g = torch.Generator().manual_seed((self.seed * 32452843 + i) * 4099 + k)
+        if self.raw:
+            h, w = torch.randint(self.raw_side[0], self.raw_side[1] + 1, (2,), generator=g).tolist()
+            return torch.randint(0, 256, (h, w, 21), generator=g, dtype=torch.uint8)
+        return torch.randint(0, 256, (self.size, self.size, 21), generator=g, dtype=torch.uint8)
+
+    def video_item(self, i, indices=None) -> dict:
+        from .input_pipeline import make_pooled_item, make_raw_pooled_item
+        if not (self.as_uint8 or self.raw):
+            raise ValueError("SyntheticChalearn.video_item: a float32 set has no uint8 frames; build it with as_uint8=True or raw=True")
+        indices = list(range(self.vframes[i])) if indices is None else [int(k) for k in indices]
+        assert all(0 <= k < self.vframes[i] for k in indices), (i, indices)
+        make = make_raw_pooled_item if self.raw else make_pooled_item
+        return make(self.key, [indices], self.labels[i], lambda k: self._video_frame(i, k))
 
     def _raw_frame(self, i, j, k):
         """frame k of clip j (or of the pooled video, j = -1) of video i: ragged (h, w, 21) random bytes, a generator of its own"""
@@ -573,7 +602,10 @@ class ChalearnVideoFramesU8(torch.utils.data.Dataset):
     resize='device': the raw transport.  read_frame(path) -> (h, w, 21) uint8 at the crop's own size, or None (default:
     ``cv2_read_frame_raw``); 'train': {'<R3D_INPUT>_raw': 1-D uint8, 'raw_hw': (T, 2) int32, 'crop', 'label'} (+ 'jitter'),
     a missing frame as (0, 0); 'test' / 'valid': {'<R3D_INPUT>_rawpool': 1-D uint8, 'raw_hw': (F, 2) int32, 'windows',
-    'label'}.  The set then has ``collate_fn = collate_raw``, which the Trainer's train loader uses."""
+    'label'}.  The set then has ``collate_fn = collate_raw``, which the Trainer's train loader uses.
+    ``seq_len(i)`` (the number of frame names, no image read), ``label(i)`` and ``video_item(i, indices=None)`` (one pooled
+    item, or raw pooled item, over those frames of the video, default all) are what ``input_pipeline.ResidentTrainSet`` reads
+    a train set through (MODEL.RESIDENT_TRAIN)."""
 
     def __init__(self, cfg, name_of_set: str, labels=None, read_frame: Optional[Callable] = None, pooled: bool = True,
                  resize: str = "host"):
@@ -610,6 +642,20 @@ class ChalearnVideoFramesU8(torch.utils.data.Dataset):
         folder = Path(m).parent / Path(m).stem
         files = sorted(glob.glob(str(Path(self.cfg.CHALEARN.ROOT, self.cfg.CHALEARN.IMG, folder) / "*")))
         return folder, [Path(f).name for f in files], int(l) - 1
+
+    def seq_len(self, index) -> int:
+        return len(self._video(index)[1])                # the reference's len(img_names), :163-169
+
+    def label(self, index) -> int:
+        return int(self.labels[index][2]) - 1
+
+    def video_item(self, index, indices=None) -> dict:
+        from .input_pipeline import make_pooled_item, make_raw_pooled_item
+        folder, names, label = self._video(index)
+        indices = list(range(len(names))) if indices is None else [int(k) for k in indices]
+        if self.resize == "device":
+            return make_raw_pooled_item(self.key, [indices], label, lambda i: self._read_raw(folder, names[i]))
+        return make_pooled_item(self.key, [indices], label, lambda i: self._read(folder, names[i]))
 
     def _read(self, folder, name):
         f = self.read_frame(Path(self.cfg.CHALEARN.ROOT, self.key, folder, name), self.size)
@@ -678,6 +724,8 @@ class Trainer:
             train_loader, test_loader = self._make_loaders(train_set, test_set)
         self.train_loader, self.test_loader = train_loader, test_loader
         self.mm = self._model_manager(cfg, device, backend)
+        if bool(cfg.MODEL.get("RESIDENT_TRAIN", False)):
+            self.resident = self._make_resident(train_set, backend)
         self.model = self.mm.init_model()
         self.num_step = 0
         self.ckpt_dir = Path(cfg.CHALEARN.ROOT, cfg.MODEL.LOGS, cfg.MODEL.CKPT_DIR, cfg.MODEL.NAME)
@@ -709,6 +757,29 @@ class Trainer:
             raise RuntimeError("no datasets / loaders were given and the reference's dataset.chalearn_dataset is not "
                                f"importable here ({e}); pass train_set/test_set (e.g. SyntheticChalearn)") from e
         return ChalearnVideoDataset(self.cfg, 'train'), ChalearnVideoDataset(self.cfg, 'test')
+
+    resident_refused = None                              # a derived trainer that cannot train from a frame pool says why
+
+    def _make_resident(self, train_set, backend):
+        """MODEL.RESIDENT_TRAIN: the ResidentTrainSet train_epoch iterates instead of the train loader"""
+        from .input_pipeline import ResidentTrainSet, offers_resident
+        why = None
+        if self.resident_refused:
+            why = self.resident_refused
+        elif train_set is None:
+            why = ("it needs the train SET (train_set=), whose frames it keeps on the device; a ready-made train_loader= only "
+                   "hands over finished batches")
+        elif not offers_resident(train_set):
+            why = (f"{type(train_set).__name__} does not offer seq_len(i), label(i) and video_item(i, indices=None) "
+                   "(ChalearnVideoFramesU8 and SyntheticChalearn(as_uint8 / raw) do)")
+        elif self.world > 1:
+            why = "a per-rank partition of the resident set is not built yet: WORLD_SIZE must be 1"
+        elif self.cfg.MODEL.NAME == "res2d" and self.mm._res2d_backend() == "torch":
+            why = "MODEL.NAME res2d with the torch backend is host plumbing and has no device kernels; use RES2D_BACKEND = 'engine'"
+        if why is not None:
+            raise ValueError(f"MODEL.RESIDENT_TRAIN: {why}")
+        return ResidentTrainSet(train_set, self.cfg, self.device, backend, batch_size=self.batch_size,
+                                drop_last=self.train_drop_last, num_workers=self.num_workers, jitter=jitter_ranges(self.cfg))
 
     def _make_loaders(self, tr, te):
         """train.py:164,170: train = shuffle + drop_last, test = whole videos, identity collate.  world > 1: one shuffled
@@ -764,7 +835,8 @@ class Trainer:
         self.model.train()
         if getattr(self, "train_sampler", None) is not None:
             self.train_sampler.set_epoch(self.epoch)     # a new permutation of the epoch, the same on every rank
-        for batch in self.train_loader:
+        resident = getattr(self, "resident", None)       # MODEL.RESIDENT_TRAIN: clips gathered from the frames on the device
+        for batch in (self.train_loader if resident is None else resident.epoch(self.epoch)):
             x, y_true = self.mm.prepare_data(batch)
             if isinstance(x, (torch.Tensor, U8Clip)):    # res3d / res2d: one input tensor (or uint8 clip)
                 self.step(x, None, y_true)
