@@ -15,7 +15,8 @@
  * An index outside [0, frames) names a MISSING frame: every element of that (n, t) slab is lut[fill] and the pool is not
  * read (the reference's "frame file missing -> constant 127 image", :116).  No index value can make the kernel read outside
  * the pool.  The index CONTENTS are read on the device when the launch runs, so a captured graph follows new windows
- * written into the same buffer.  There is no crop: test and valid clips have none.
+ * written into the same buffer.  There is no crop: test and valid clips have none.  sfk_u8_pool_gather_crop
+ * (include/sfk_resident.h) is this entry point with one; the two share one kernel, the crop a compile-time switch of it.
  *
  * One launch, one output row (all c channels) per workgroup of 256 threads: the row's source bytes, from the first byte of
  * channel c0 of its first pixel to the last byte of channel c0 + c - 1 of its last pixel, are staged through LDS -- as

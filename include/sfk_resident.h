@@ -17,7 +17,8 @@
  * with byte (f, y, x, ch) at pool[f*frame_stride + y*row_stride + x*pixel_pitch + c0 + ch] and (top, left) = crop[n].  The
  * values are the ones sfk_u8_normalize_crop (include/sfk.h) writes, with the same crop and pad, from the same frames stacked
  * clip by clip, bit for bit: a MISSING frame (an index outside [0, frames)) is the reference's constant-127 image (:116),
- * normalised and then zero-padded by the crop like any other frame.  With crop == NULL it is sfk_u8_pool_gather, bit for bit.
+ * normalised and then zero-padded by the crop like any other frame.  With crop == NULL it is sfk_u8_pool_gather, bit for bit
+ * and launch for launch: the two entry points share one kernel, whose crop is a compile-time switch taken from crop != NULL.
  *
  * Every crop value and every index value is memory-safe: a row or a column wholly outside the frame writes zeros and reads
  * nothing, a missing frame reads nothing, and no byte outside the needed part of the source row's span -- from the first byte

@@ -986,10 +986,9 @@ class HipBackend:
         d.c_off, d.bgr, d.mean, d.std = c_off, 1 if bgr else 0, mean, std
         return self._plain("sfk_color_jitter", C.byref(d), keep=(d, clip, params, workspace))
 
-    def u8_pool_gather(self, pool, index, lut, fill: int, out, c0: int = 0, c: Optional[int] = None):
-        """sfk_u8_pool_gather (include/sfk_pool.h): pool (F,H,W,P) uint8 with unit channel stride (the byte strides are the
-        tensor's), index (N,T) int32 on the device, read when the launch runs; out (N,T,c,H,W) f32|bf16 contiguous =
-        lut[pool[index[n,t], y, x, c0 + ch]], or lut[fill] everywhere in a slab whose index is outside [0, F)."""
+    @staticmethod
+    def _fill_pool_desc(d, pool, index, lut, fill, out, c0, c):
+        """what sfk_pool_desc and sfk_pool_crop_desc share: the assertions on pool, index, lut and out, and those fields of d"""
         f, h, w, p = pool.shape
         c = p - c0 if c is None else c
         assert pool.dtype == torch.uint8 and pool.stride(3) == 1 and 0 <= c0 and 0 < c and c0 + c <= p
@@ -997,31 +996,27 @@ class HipBackend:
         n, t = index.shape
         assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
         assert out.is_contiguous() and tuple(out.shape) == (n, t, c, h, w), (tuple(out.shape), (n, t, c, h, w))
-        d = new_pool_desc()
         d.out_dtype, d.pool, d.index, d.lut, d.out = _DT[out.dtype], pool.data_ptr(), index.data_ptr(), lut.data_ptr(), out.data_ptr()
         d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
         d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
+        return d
+
+    def u8_pool_gather(self, pool, index, lut, fill: int, out, c0: int = 0, c: Optional[int] = None):
+        """sfk_u8_pool_gather (include/sfk_pool.h): pool (F,H,W,P) uint8 with unit channel stride (the byte strides are the
+        tensor's), index (N,T) int32 on the device, read when the launch runs; out (N,T,c,H,W) f32|bf16 contiguous =
+        lut[pool[index[n,t], y, x, c0 + ch]], or lut[fill] everywhere in a slab whose index is outside [0, F)."""
+        d = self._fill_pool_desc(new_pool_desc(), pool, index, lut, fill, out, c0, c)
         return self._plain("sfk_u8_pool_gather", C.byref(d), keep=(d, pool, index, lut, out))
 
     def u8_pool_gather_crop(self, pool, index, lut, fill: int, crop, pad: int, out, c0: int = 0, c: Optional[int] = None):
         """sfk_u8_pool_gather_crop (include/sfk_resident.h): ``u8_pool_gather`` with RandomCrop's shift -- crop (N,2) int32
         (top, left) on the device, read when the launch runs, or None (no shift); out[n,t,ch,y,x] is 0 where
         (y + top - pad, x + left - pad) lies outside the frame, else the gathered value (lut[fill] for a missing frame)."""
-        f, h, w, p = pool.shape
-        c = p - c0 if c is None else c
-        assert pool.dtype == torch.uint8 and pool.stride(3) == 1 and 0 <= c0 and 0 < c and c0 + c <= p
-        assert index.dtype == torch.int32 and index.dim() == 2 and index.is_contiguous()
-        n, t = index.shape
-        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
-        assert out.is_contiguous() and tuple(out.shape) == (n, t, c, h, w), (tuple(out.shape), (n, t, c, h, w))
+        d = self._fill_pool_desc(new_pool_crop_desc(), pool, index, lut, fill, out, c0, c)
         if crop is not None:
-            assert crop.dtype == torch.int32 and tuple(crop.shape) == (n, 2) and crop.is_contiguous()
+            assert crop.dtype == torch.int32 and tuple(crop.shape) == (d.n, 2) and crop.is_contiguous()
             assert crop.device == index.device
-        d = new_pool_crop_desc()
-        d.out_dtype, d.pool, d.index, d.lut, d.out = _DT[out.dtype], pool.data_ptr(), index.data_ptr(), lut.data_ptr(), out.data_ptr()
         d.crop, d.pad = (None if crop is None else crop.data_ptr()), int(pad)
-        d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
-        d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
         return self._plain("sfk_u8_pool_gather_crop", C.byref(d), keep=(d, pool, index, lut, crop, out))
 
     def u8_pad_resize_cubic(self, src, offset, hw, out, size: int, max_side: int, fill: int):

@@ -8,7 +8,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsfk.so")
 SOURCES = ["conv_igemm.hip", "conv_igemm_p8.hip", "conv_halo.hip", "conv_pw.hip", "conv_wgrad.hip", "conv_wgrad_p8.hip", "conv_wgrad_band.hip", "stem_conv.hip", "bn.hip", "bn_tail.hip", "pool_head.hip",
-           "optim_misc.hip", "eval_input.hip", "stem2d.hip", "roi_resize.hip", "sgd.hip", "color_jitter.hip", "frame_pool.hip", "pad_resize.hip", "frame_pool_crop.hip"]
+           "optim_misc.hip", "eval_input.hip", "stem2d.hip", "roi_resize.hip", "sgd.hip", "color_jitter.hip", "u8_pool_gather.hip", "pad_resize.hip"]
 
 
 def _newer(a, b):

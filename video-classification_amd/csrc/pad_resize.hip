@@ -35,7 +35,7 @@ __device__ __forceinline__ int clipi(int v, int lo, int hi) { return v < lo ? lo
 //   acc  int32[max_side*cp]  the vertically filtered row: pixel X of the padded square at acc[X*cp .. X*cp + c), so that four
 //                            channels of a pixel are one aligned 16-byte LDS access (the cp - c tail columns hold rubbish)
 //   raw  4 x uint8[raw_b]    the four source rows; row i's byte k at raw_i[shift_i + k], shift_i = its address & 15, so that
-//                            LDS and global addresses share their 16-byte phase (as frame_pool.hip stages its row)
+//                            LDS and global addresses share their 16-byte phase (as u8_pool_gather.hip stages its row)
 //   obuf uint8[ROW16(S*c)]   the output row, byte e at obuf[oshift + e], oshift = the output row's address & 15
 //   xt   int4[S][2]          per output coordinate: the four taps' offsets X_j*cp into acc, and the four coefficients
 //   xs   int32[S]            per output coordinate: s, unclipped (the row pass reads entry y of the same table)

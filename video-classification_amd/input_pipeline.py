@@ -71,6 +71,27 @@ def draw_color_jitter(n: int, brightness: float = 0.5, contrast: float = 0.3, sa
     return out
 
 
+def h2d(t: torch.Tensor, device) -> torch.Tensor:
+    """through pinned host memory: the uint8 batch crosses PCIe as an asynchronous DMA behind the previous step's
+    kernels (from pageable memory `non_blocking=True` is a synchronous staged copy)"""
+    if t.device.type == "cpu" and torch.device(device).type == "cuda" and not t.is_pinned():
+        t = t.pin_memory()
+    return t.to(device, non_blocking=True)
+
+
+def stream_of(device) -> int:
+    """the handle of the current stream of a cuda device; 0 (the emulator backends ignore it) for any other"""
+    return torch.cuda.current_stream(device).cuda_stream if torch.device(device).type == "cuda" else 0
+
+
+def hip_backend(backend=None):
+    """backend, or the library's own when None"""
+    if backend is None:
+        from ._lib import HipBackend
+        backend = HipBackend()                  # raises when libsfk.so is missing: no CPU path
+    return backend
+
+
 class ColorJitter:
     """torchvision's ColorJitter (the reference's train-time colour augmentation, dataset/chalearn_dataset.py:48-50) on the
     three colour planes of a float clip batch (N, T, C, H, W) that already lives on the device, IN PLACE, by
@@ -80,16 +101,8 @@ class ColorJitter:
     unpinned."""
 
     def __init__(self, device="cuda", backend=None):
-        if backend is None:
-            from ._lib import HipBackend
-            backend = HipBackend()              # raises when libsfk.so is missing: no CPU path
-        self.be, self.device = backend, torch.device(device)
+        self.be, self.device = hip_backend(backend), torch.device(device)
         self._ws = {}                           # (n, t, h, w) -> the float32 workspace of that geometry
-
-    def _h2d(self, t: torch.Tensor) -> torch.Tensor:
-        if t.device.type == "cpu" and self.device.type == "cuda" and not t.is_pinned():
-            t = t.pin_memory()
-        return t.to(self.device, non_blocking=True)
 
     def workspace(self, n: int, t: int, h: int, w: int) -> torch.Tensor:
         key = (n, t, h, w)
@@ -102,9 +115,9 @@ class ColorJitter:
                  std: float = 1.0) -> torch.Tensor:
         assert clip.dim() == 5 and clip.stride(4) == 1 and clip.device.type == self.device.type
         n, t, _, h, w = clip.shape
-        params = self._h2d(params.to(torch.float32)).contiguous()
+        params = h2d(params.to(torch.float32), self.device).contiguous()
         assert tuple(params.shape) == (n, 8), tuple(params.shape)
-        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+        stream = stream_of(self.device)
         self.be.color_jitter(clip, params, self.workspace(n, t, h, w), c_off, bgr, mean, std)(stream)
         return clip
 
@@ -113,29 +126,19 @@ class DevicePreprocess:
     """uint8 frames (N, T, S, S, C) -> normalised clip batch (N, T, C, S, S) on the device."""
 
     def __init__(self, device="cuda", backend=None, out_dtype: torch.dtype = torch.float32):
-        if backend is None:
-            from ._lib import HipBackend
-            backend = HipBackend()              # raises when libsfk.so is missing: no CPU path
-        self.be, self.device, self.out_dtype = backend, torch.device(device), out_dtype
+        self.be, self.device, self.out_dtype = hip_backend(backend), torch.device(device), out_dtype
         self.lut = normalize_lut().to(self.device)
-
-    def _h2d(self, t: torch.Tensor) -> torch.Tensor:
-        """through pinned host memory: the uint8 batch crosses PCIe as an asynchronous DMA behind the previous step's
-        kernels (from pageable memory `non_blocking=True` is a synchronous staged copy)"""
-        if t.device.type == "cpu" and self.device.type == "cuda" and not t.is_pinned():
-            t = t.pin_memory()
-        return t.to(self.device, non_blocking=True)
 
     def __call__(self, frames_u8: torch.Tensor, crop: Optional[torch.Tensor] = None, padding: Optional[int] = None):
         assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 5
         n, t, h, w, c = frames_u8.shape
-        x = self._h2d(frames_u8).contiguous()
+        x = h2d(frames_u8, self.device).contiguous()
         if crop is not None:
             padding = h // 10 if padding is None else padding
-            crop = self._h2d(crop.to(torch.int32)).contiguous()
+            crop = h2d(crop.to(torch.int32), self.device).contiguous()
             assert tuple(crop.shape) == (n, 2)
         out = torch.empty(n, t, c, h, w, dtype=self.out_dtype, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+        stream = stream_of(self.device)
         self.be.u8_normalize_crop(x, self.lut, crop, int(padding or 0), out)(stream)
         return out
 
@@ -158,11 +161,9 @@ def pool_key(key: str) -> str:
     return key + "_pool"
 
 
-def make_pooled_item(key: str, windows: torch.Tensor, label, read) -> dict:
-    """The pooled item of one test video: {'<key>_pool': (F, S, S, P) uint8 HWC, 'windows': (K, T) int32, 'label'}.
-    windows holds indices into the VIDEO; read(i) returns frame i as (S, S, P) uint8, or None when it is missing, and is
-    called once per frame that some window references.  Only those frames that exist enter the pool, renumbered densely
-    in ascending order; a missing frame becomes -1 in 'windows'."""
+def _read_referenced(windows: torch.Tensor, read) -> tuple:
+    """(the frames some window references that exist, each read ONCE, in ascending order; windows (K, T) int32 renumbered
+    densely into that list, -1 for a missing frame); a video with no existing frame is a ValueError"""
     windows = torch.as_tensor(windows, dtype=torch.int32)
     remap, frames = {}, []
     for i in sorted(set(windows.flatten().tolist())):
@@ -171,11 +172,20 @@ def make_pooled_item(key: str, windows: torch.Tensor, label, read) -> dict:
             remap[i] = -1
         else:
             remap[i] = len(frames)
-            frames.append(torch.as_tensor(f))
+            frames.append(f)
     if not frames:
         raise ValueError("a pooled video needs at least one frame that exists")
     local = torch.tensor([[remap[i] for i in row] for row in windows.tolist()], dtype=torch.int32)
-    return {pool_key(key): torch.stack(frames), "windows": local, "label": label}
+    return frames, local
+
+
+def make_pooled_item(key: str, windows: torch.Tensor, label, read) -> dict:
+    """The pooled item of one test video: {'<key>_pool': (F, S, S, P) uint8 HWC, 'windows': (K, T) int32, 'label'}.
+    windows holds indices into the VIDEO; read(i) returns frame i as (S, S, P) uint8, or None when it is missing, and is
+    called once per frame that some window references.  Only those frames that exist enter the pool, renumbered densely
+    in ascending order; a missing frame becomes -1 in 'windows'."""
+    frames, local = _read_referenced(windows, read)
+    return {pool_key(key): torch.stack([torch.as_tensor(f) for f in frames]), "windows": local, "label": label}
 
 
 def unpool_item(item: dict) -> list:
@@ -204,10 +214,7 @@ class FramePool:
     RandomCrop-ped train clips with ``sfk_u8_pool_gather_crop`` (include/sfk_resident.h).  ``ResidentTrainSet`` uses both."""
 
     def __init__(self, device="cuda", backend=None, fill: int = MISSING_BYTE, capacity: Optional[int] = None):
-        if backend is None:
-            from ._lib import HipBackend
-            backend = HipBackend()              # raises when libsfk.so is missing: no CPU path
-        self.be, self.device, self.fill = backend, torch.device(device), int(fill)
+        self.be, self.device, self.fill = hip_backend(backend), torch.device(device), int(fill)
         self.lut = normalize_lut().to(self.device)
         self.arena: Optional[torch.Tensor] = None
         self.live = {}                          # base -> frames of that video
@@ -216,11 +223,6 @@ class FramePool:
         self.capacity = None if capacity is None else int(capacity)
         if self.capacity is not None and self.capacity <= 0:
             raise ValueError(f"FramePool: capacity {capacity} frames")
-
-    def _h2d(self, t: torch.Tensor) -> torch.Tensor:
-        if t.device.type == "cpu" and self.device.type == "cuda" and not t.is_pinned():
-            t = t.pin_memory()
-        return t.to(self.device, non_blocking=True)
 
     @staticmethod
     def check_windows(windows: torch.Tensor, frames: int) -> None:
@@ -337,15 +339,15 @@ class FramePool:
         _, h, w, p = self.arena.shape
         c = p - c0 if c is None else c
         out = torch.empty(idx.shape[0], idx.shape[1], c, h, w, dtype=out_dtype, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+        stream = stream_of(self.device)
         if crop is not None:
             crop = torch.as_tensor(crop).to(torch.int32).contiguous()
             assert tuple(crop.shape) == (idx.shape[0], 2), tuple(crop.shape)
             padding = h // 10 if padding is None else int(padding)
-            self.be.u8_pool_gather_crop(self.arena, self._h2d(idx), self.lut, self.fill, self._h2d(crop), padding, out, c0,
-                                        c)(stream)
+            self.be.u8_pool_gather_crop(self.arena, h2d(idx, self.device), self.lut, self.fill, h2d(crop, self.device), padding,
+                                        out, c0, c)(stream)
             return out
-        self.be.u8_pool_gather(self.arena, self._h2d(idx), self.lut, self.fill, out, c0, c)(stream)
+        self.be.u8_pool_gather(self.arena, h2d(idx, self.device), self.lut, self.fill, out, c0, c)(stream)
         return out
 
 
@@ -392,18 +394,7 @@ def make_raw_pooled_item(key: str, windows: torch.Tensor, label, read) -> dict:
     """``make_pooled_item`` for frames at their native sizes: {'<key>_rawpool': 1-D uint8, 'raw_hw': (F, 2) int32, 'windows':
     (K, T) int32, 'label'}.  read(i) returns frame i as (h, w, c) uint8 HWC, or None when it is missing, once per frame that
     some window references; only the frames that exist are kept, renumbered densely, a missing one is -1 in 'windows'."""
-    windows = torch.as_tensor(windows, dtype=torch.int32)
-    remap, frames = {}, []
-    for i in sorted(set(windows.flatten().tolist())):
-        f = read(i)
-        if f is None:
-            remap[i] = -1
-        else:
-            remap[i] = len(frames)
-            frames.append(f)
-    if not frames:
-        raise ValueError("a pooled video needs at least one frame that exists")
-    local = torch.tensor([[remap[i] for i in row] for row in windows.tolist()], dtype=torch.int32)
+    frames, local = _read_referenced(windows, read)
     raw, hw = pack_raw_frames(frames)
     return {rawpool_key(key): raw, "raw_hw": hw, "windows": local, "label": label}
 
@@ -447,18 +438,10 @@ class PadResize:
     parity with cv2.resize(INTER_CUBIC) itself is unpinned.  ``bytes_uploaded`` counts the raw bytes sent."""
 
     def __init__(self, size: int, device="cuda", backend=None, fill: int = MISSING_BYTE, channels: int = 21):
-        if backend is None:
-            from ._lib import HipBackend
-            backend = HipBackend()              # raises when libsfk.so is missing: no CPU path
-        self.be, self.device = backend, torch.device(device)
+        self.be, self.device = hip_backend(backend), torch.device(device)
         self.size, self.fill, self.channels = int(size), int(fill), int(channels)
         assert self.size > 0 and 0 <= self.fill <= 255 and self.channels > 0
         self.bytes_uploaded = 0
-
-    def _h2d(self, t: torch.Tensor) -> torch.Tensor:
-        if t.device.type == "cpu" and self.device.type == "cuda" and not t.is_pinned():
-            t = t.pin_memory()
-        return t.to(self.device, non_blocking=True)
 
     def check_table(self, nbytes: int, offset: torch.Tensor, hw: torch.Tensor) -> int:
         """ValueError for a table the kernel would answer with fill bytes although a frame was meant (or could not stage);
@@ -496,10 +479,10 @@ class PadResize:
             nbytes = int(raw_bytes.numel())
         if raw_bytes.device.type == "cpu":
             self.bytes_uploaded += nbytes
-        src = self._h2d(raw_bytes.contiguous())
-        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
-        self.be.u8_pad_resize_cubic(src[:nbytes] if nbytes else src, self._h2d(offset.contiguous()), self._h2d(hw.contiguous()),
-                                    out, s, max_side, self.fill)(stream)
+        src = h2d(raw_bytes.contiguous(), self.device)
+        stream = stream_of(self.device)
+        self.be.u8_pad_resize_cubic(src[:nbytes] if nbytes else src, h2d(offset.contiguous(), self.device),
+                                    h2d(hw.contiguous(), self.device), out, s, max_side, self.fill)(stream)
         return out
 
 
@@ -583,32 +566,24 @@ class RoiResize:
 
     def __init__(self, size: int, device="cuda", backend=None, out_dtype: torch.dtype = torch.float32,
                  antialias: bool = True):
-        if backend is None:
-            from ._lib import HipBackend
-            backend = HipBackend()              # raises when libsfk.so is missing: no CPU path
-        self.be, self.device, self.out_dtype = backend, torch.device(device), out_dtype
+        self.be, self.device, self.out_dtype = hip_backend(backend), torch.device(device), out_dtype
         self.size, self.antialias = int(size), bool(antialias)
         self.lut = byte_lut().to(self.device)
-
-    def _h2d(self, t: torch.Tensor) -> torch.Tensor:
-        if t.device.type == "cpu" and self.device.type == "cuda" and not t.is_pinned():
-            t = t.pin_memory()
-        return t.to(self.device, non_blocking=True)
 
     def __call__(self, frames_u8: torch.Tensor, box: torch.Tensor, crop: Optional[torch.Tensor] = None,
                  padding: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 5
         n, t, h, w, c = frames_u8.shape
-        x = self._h2d(frames_u8)
-        box = self._h2d(box.to(torch.int32)).contiguous()
+        x = h2d(frames_u8, self.device)
+        box = h2d(box.to(torch.int32), self.device).contiguous()
         assert tuple(box.shape) == (n, 4)
         pad = 0
         if crop is not None:
             pad = self.size // 10 if padding is None else int(padding)
-            crop = self._h2d(crop.to(torch.int32)).contiguous()
+            crop = h2d(crop.to(torch.int32), self.device).contiguous()
         if out is None:
             out = torch.empty(n, t, c, self.size, self.size, dtype=self.out_dtype, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream if self.device.type == "cuda" else 0
+        stream = stream_of(self.device)
         self.be.roi_resize(x, self.lut, box, out, self.antialias, crop, pad)(stream)
         return out
 

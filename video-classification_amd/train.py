@@ -30,7 +30,7 @@ from torch.utils.data.dataloader import default_collate
 from . import dist as sdist
 from .config import crop_resize_dict
 from .engine import Engine
-from .input_pipeline import U8Clip
+from .input_pipeline import U8Clip, h2d
 from .slowfast import init_my_slowfast
 
 
@@ -216,9 +216,7 @@ class ModelManager:
         """host -> device through PINNED memory, so the copy is a DMA that overlaps the previous step's kernels (a
         pageable source makes `non_blocking=True` a synchronous staged copy: train.py:127's 1.5 GB batch would stall the
         host for its whole duration).  Loaders built by the Trainer already pin (pin_memory=True)."""
-        if t.device.type == "cpu" and torch.device(self.device).type == "cuda" and not t.is_pinned():
-            t = t.pin_memory()
-        return t.to(self.device, non_blocking=True)
+        return h2d(t, self.device)
 
     # ---- the uint8 transport: a batch carrying <R3D_INPUT>_u8 (N,T,S,S,P uint8 HWC frames, P >= the channels read, optional
     #      `crop` (N,2)) instead of the float32 tensor.  MODEL.U8_STEM False: DevicePreprocess writes the normalised, cropped
