@@ -242,6 +242,17 @@ class _PoolCropDesc(C.Structure):
                 ("lut", C.c_void_p), ("crop", C.c_void_p), ("fill", C.c_int32), ("pad", C.c_int32), ("out", C.c_void_p)]
 
 
+class _RoiPoolDesc(C.Structure):
+    """include/sfk_roi_pool.h sfk_roi_pool_desc: sfk_roi_desc with its source addressing replaced by a frame pool -- byte
+    (f, y, x, ch) at pool[f*frame_stride + y*row_stride + x*pixel_pitch + c0 + ch], clip n, time t reads frame index[n][t]"""
+    _fields_ = [("struct_size", C.c_uint32), ("antialias", C.c_int32), ("pool", C.c_void_p), ("frame_stride", C.c_int64),
+                ("row_stride", C.c_int64), ("pixel_pitch", C.c_int32), ("frames", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("c0", C.c_int32), ("c", C.c_int32), ("n", C.c_int32), ("t", C.c_int32), ("index", C.c_void_p),
+                ("lut", C.c_void_p), ("box", C.c_void_p), ("crop", C.c_void_p), ("pad", C.c_int32), ("fill", C.c_int32),
+                ("out_h", C.c_int32), ("out_w", C.c_int32), ("dst_dtype", C.c_int32), ("dst", C.c_void_p), ("dn", C.c_int64),
+                ("dt", C.c_int64), ("dc", C.c_int64), ("dh", C.c_int64), ("c_off", C.c_int32)]
+
+
 class _ResizeDesc(C.Structure):
     """include/sfk_resize.h sfk_resize_desc: frame f is the contiguous HWC bytes src[offset[f] ...] of hw[f] = (h, w) pixels
     and c channels; its padded, cubic-resized (size, size, c) frame lands at out + f*out_frame_stride"""
@@ -392,6 +403,13 @@ SIGNATURES_RESIDENT = {
     "sfk_resident_abi_version": [],
     "sfk_u8_pool_gather_crop": [C.POINTER(_PoolCropDesc), _PV],
 }
+# include/sfk_roi_pool.h: the v2 trainer's device-resident train set (ROI crop-resize from the frame pool), same library, its
+# own header and version
+ROI_POOL_ABI_VERSION = 1   # include/sfk_roi_pool.h SFK_ROI_POOL_ABI_VERSION
+SIGNATURES_ROI_POOL = {
+    "sfk_roi_pool_abi_version": [],
+    "sfk_roi_resize_pool": [C.POINTER(_RoiPoolDesc), _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
@@ -445,6 +463,12 @@ def new_pool_crop_desc() -> "_PoolCropDesc":
     return d
 
 
+def new_roi_pool_desc() -> "_RoiPoolDesc":
+    d = _RoiPoolDesc()
+    d.struct_size = C.sizeof(_RoiPoolDesc)
+    return d
+
+
 def new_resize_desc() -> "_ResizeDesc":
     d = _ResizeDesc()
     d.struct_size = C.sizeof(_ResizeDesc)
@@ -469,7 +493,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
                        "(there is no CPU or PyTorch fallback for the SlowFast path)")
     lib = C.CDLL(path)
     for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL,
-                  SIGNATURES_RESIZE, SIGNATURES_RESIDENT):
+                  SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -490,6 +514,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk resize ABI version mismatch: library {lib.sfk_resize_abi_version()}, binding {RESIZE_ABI_VERSION}")
     if lib.sfk_resident_abi_version() != RESIDENT_ABI_VERSION:
         raise SfkError(f"libsfk resident ABI version mismatch: library {lib.sfk_resident_abi_version()}, binding {RESIDENT_ABI_VERSION}")
+    if lib.sfk_roi_pool_abi_version() != ROI_POOL_ABI_VERSION:
+        raise SfkError(f"libsfk roi_pool ABI version mismatch: library {lib.sfk_roi_pool_abi_version()}, binding {ROI_POOL_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -1018,6 +1044,30 @@ class HipBackend:
             assert crop.device == index.device
         d.crop, d.pad = (None if crop is None else crop.data_ptr()), int(pad)
         return self._plain("sfk_u8_pool_gather_crop", C.byref(d), keep=(d, pool, index, lut, crop, out))
+
+    def roi_resize_pool(self, pool, index, lut, fill: int, box, out, antialias: bool, crop=None, pad: int = 0, c0: int = 0,
+                        c: Optional[int] = None, c_off: int = 0):
+        """sfk_roi_resize_pool (include/sfk_roi_pool.h): ``roi_resize`` whose clip (n, t) is frame index[n, t] of pool
+        (F,H,W,P) uint8 with unit channel stride, channels c0 .. c0+c-1 -- or the constant image of byte fill when the index
+        is outside [0, F); index (N,T) int32, box (N,4) int32 and crop (N,2) int32 | None on the device, read when the launch
+        runs; out (N,T,C',S,S') f32|bf16 with unit W stride, channels c_off .. c_off+c-1 written."""
+        f, h, w, p = pool.shape
+        c = p - c0 if c is None else c
+        assert pool.dtype == torch.uint8 and pool.stride(3) == 1 and 0 <= c0 and 0 < c and c0 + c <= p
+        assert index.dtype == torch.int32 and index.dim() == 2 and index.is_contiguous()
+        n, t = index.shape
+        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
+        assert box.dtype == torch.int32 and box.is_contiguous() and tuple(box.shape) == (n, 4)
+        assert out.dim() == 5 and out.stride(4) == 1 and out.shape[0] == n and out.shape[1] == t and c_off + c <= out.shape[2]
+        assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (n, 2))
+        d = new_roi_pool_desc()
+        d.antialias, d.pool, d.index, d.lut, d.box, d.crop = 1 if antialias else 0, pool.data_ptr(), index.data_ptr(), lut.data_ptr(), box.data_ptr(), _ptr(crop)
+        d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
+        d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.pad, d.fill = f, h, w, c0, c, n, t, int(pad), int(fill)
+        d.out_h, d.out_w = out.shape[3], out.shape[4]
+        d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
+        d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
+        return self._plain("sfk_roi_resize_pool", C.byref(d), keep=(d, pool, index, lut, box, out, crop))
 
     def u8_pad_resize_cubic(self, src, offset, hw, out, size: int, max_side: int, fill: int):
         """sfk_u8_pad_resize_cubic (include/sfk_resize.h): src 1-D uint8, the frames' HWC bytes; offset (F,) int64 and hw (F, 2)

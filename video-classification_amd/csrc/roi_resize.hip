@@ -1,12 +1,15 @@
 // sfk_roi_resize (include/sfk_v2.h): part-box crop + uint8 table lookup + separable bilinear resize (F.interpolate,
-// align_corners=False, with or without antialiasing) + optional RandomCrop shift, one launch per batch.
+// align_corners=False, with or without antialiasing) + optional RandomCrop shift, one launch per batch -- and
+// sfk_roi_resize_pool (include/sfk_roi_pool.h): the same from frames that lie in a pool, picked by a table of frame indices.
+// The two entry points share one kernel and one launcher; the source addressing is a compile-time switch.
 //
 // One workgroup owns a tile of B destination rows x TW destination columns of one (clip, frame), all channels:
 //   1. it reads the clip's box (and crop), builds the tap index / weight tables of its TW columns and B rows in LDS with
 //      torch's CPU arithmetic (upsample_bilinear2d's fused source index; _upsample_bilinear2d_aa's mixed float/double
 //      weights), and the byte table;
 //   2. it stages the source bytes its taps touch -- R rows x SP columns x c channels -- in LDS, as aligned dwords when the
-//      channels of a pixel are adjacent (HWC), as bytes otherwise (planar);
+//      channels of a pixel are adjacent (HWC; a pool's frames always are), as bytes otherwise (planar); a pooled frame whose
+//      index is outside the pool is staged as bytes of `fill` and reads nothing;
 //   3. horizontal pass: R x c x TW fp32 band in LDS (taps in torch's order, no contraction);
 //   4. vertical pass: one coalesced row store per (channel, row), zeros where the crop shift leaves the resized image.
 // The host sizes B, TW, R and SP from the worst-case ratio frame / output, so every box fits its LDS; the kernel still
@@ -15,7 +18,7 @@
 #include <math.h>
 
 #include "sfk_common.h"
-#include "sfk_v2.h"
+#include "sfk_roi_pool.h"
 
 namespace {
 
@@ -27,6 +30,13 @@ struct RoiGeo {
   int B, TW, R, SP, KH, KW;
   int row_tiles, col_tiles;
   int off_lut, off_xw, off_xi, off_yw, off_yi, off_sb, off_tmp, lds;
+};
+
+// what sfk_roi_resize_pool adds to the descriptor the kernel reads: there d.src = pool + c0, d.st = frame_stride, d.sh =
+// row_stride, d.sw = pixel_pitch, d.sc = 1 and d.sn is unused
+struct RoiPool {
+  const int32_t* index;
+  int frames, fill;
 };
 
 inline int align16(int v) { return (v + 15) & ~15; }
@@ -109,8 +119,8 @@ __device__ void roi_taps(int i, int in, int out, int aa, int K, int* idx, float*
   for (int k = 0; k < K; ++k) idx[k] = min(max(idx[k], 0), in - 1);
 }
 
-template <typename D>
-__global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, RoiGeo g) {
+template <typename D, bool POOL>
+__global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, RoiGeo g, RoiPool p) {
   extern __shared__ __align__(16) unsigned char smem[];
   float* lut = reinterpret_cast<float*>(smem + g.off_lut);
   float* xw = reinterpret_cast<float*>(smem + g.off_xw);
@@ -162,8 +172,21 @@ __global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, Ro
   const int ncol = min(xhi - xlo + 1, g.SP), nrow = min(yhi - ylo + 1, g.R);
 
   // 2. stage the window's bytes: sb[(row * SP + col) * C + ch]
-  const uint8_t* base = d.src + n * d.sn + t * d.st + (int64_t)(y1 + ylo) * d.sh + (int64_t)(x1 + xlo) * d.sw;
-  if (d.sc == 1 && d.sw >= C) {
+  const uint8_t* base = d.src + (int64_t)(y1 + ylo) * d.sh + (int64_t)(x1 + xlo) * d.sw;
+  bool miss = false;
+  if (POOL) {
+    const int f = p.index[(int64_t)n * d.t + t];          // read once per workgroup; block-uniform
+    miss = f < 0 || f >= p.frames;
+    base += (int64_t)(miss ? 0 : f) * d.st;               // 64-bit: a pool may exceed 2^31 bytes
+  } else {
+    base += n * d.sn + t * d.st;
+  }
+  if (POOL && miss) {
+    // a missing frame: the window's rows as dwords of the fill byte (sb is 16-byte aligned and nrow <= R), no global load
+    const uint32_t v = 0x01010101u * (uint32_t)p.fill;
+    const int nd = (nrow * g.SP * C + 3) >> 2;
+    for (int q = tid; q < nd; q += kThreads) reinterpret_cast<uint32_t*>(sb)[q] = v;
+  } else if (POOL || (d.sc == 1 && d.sw >= C)) {
     // one aligned dword per lane over each row's bytes [first pixel, last pixel's channel C-1]: every dword holds at
     // least one byte of an in-frame pixel of the window
     const int pitch = (int)d.sw;
@@ -233,10 +256,9 @@ __global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, Ro
   }
 }
 
-}  // namespace
-
-extern "C" int sfk_roi_resize(const sfk_roi_desc* d, sfk_stream_t stream) {
-  if (!d || d->struct_size != sizeof(sfk_roi_desc)) return SFK_ERR_INVALID;
+// every host-side check the two entry points share (each checks its own struct_size and its own source first), then the
+// launch: p == nullptr is sfk_roi_resize's strided source, otherwise the pool's
+int roi_resize(const sfk_roi_desc* d, const RoiPool* p, sfk_stream_t stream) {
   if (!d->src || !d->lut || !d->box || !d->dst) return SFK_ERR_INVALID;
   if (d->n <= 0 || d->t <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->out_h <= 0 || d->out_w <= 0) return SFK_ERR_INVALID;
   if (d->sn < 0 || d->st < 0 || d->sh < 0 || d->sw < 0 || d->sc < 0 || d->dn < 0 || d->dt < 0 || d->dc < 0 || d->dh < 0)
@@ -264,12 +286,40 @@ extern "C" int sfk_roi_resize(const sfk_roi_desc* d, sfk_stream_t stream) {
   if (tiles > 0x7fffffff || d->t > 65535 || d->n > 65535) return SFK_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)tiles, (unsigned)d->t, (unsigned)d->n);
-  if (d->dst_dtype == SFK_BF16)
-    hipLaunchKernelGGL(roi_resize_kernel<bf16_t>, grid, dim3(kThreads), g.lds, s, *d, g);
-  else
-    hipLaunchKernelGGL(roi_resize_kernel<float>, grid, dim3(kThreads), g.lds, s, *d, g);
+  const bool bf = d->dst_dtype == SFK_BF16;
+  const auto kernel = p ? (bf ? roi_resize_kernel<bf16_t, true> : roi_resize_kernel<float, true>)
+                        : (bf ? roi_resize_kernel<bf16_t, false> : roi_resize_kernel<float, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), g.lds, s, *d, g, p ? *p : RoiPool{});
   SFK_CHECK_LAUNCH();
   return SFK_OK;
 }
 
+}  // namespace
+
+extern "C" int sfk_roi_resize(const sfk_roi_desc* d, sfk_stream_t stream) {
+  if (!d || d->struct_size != sizeof(sfk_roi_desc)) return SFK_ERR_INVALID;
+  return roi_resize(d, nullptr, stream);
+}
+
+extern "C" int sfk_roi_resize_pool(const sfk_roi_pool_desc* d, sfk_stream_t stream) {
+  if (!d || d->struct_size != sizeof(sfk_roi_pool_desc)) return SFK_ERR_INVALID;
+  if (!d->pool || !d->index || d->frames <= 0) return SFK_ERR_INVALID;
+  if (d->frame_stride < 0 || d->row_stride < 0 || d->c0 < 0) return SFK_ERR_INVALID;
+  if ((int64_t)d->pixel_pitch < (int64_t)d->c0 + d->c) return SFK_ERR_INVALID;
+  if (d->fill < 0 || d->fill > 255) return SFK_ERR_INVALID;
+  sfk_roi_desc r{};
+  r.struct_size = sizeof(sfk_roi_desc);
+  r.antialias = d->antialias;
+  r.src = d->pool + d->c0;
+  r.sn = 0, r.st = d->frame_stride, r.sh = d->row_stride, r.sw = d->pixel_pitch, r.sc = 1;
+  r.n = d->n, r.t = d->t, r.h = d->h, r.w = d->w, r.c = d->c;
+  r.out_h = d->out_h, r.out_w = d->out_w;
+  r.lut = d->lut, r.box = d->box, r.crop = d->crop, r.pad = d->pad;
+  r.dst_dtype = d->dst_dtype, r.dst = d->dst;
+  r.dn = d->dn, r.dt = d->dt, r.dc = d->dc, r.dh = d->dh, r.c_off = d->c_off;
+  const RoiPool p{d->index, d->frames, d->fill};
+  return roi_resize(&r, &p, stream);
+}
+
+extern "C" int sfk_roi_pool_abi_version(void) { return SFK_ROI_POOL_ABI_VERSION; }
 extern "C" int sfk_v2_abi_version(void) { return SFK_V2_ABI_VERSION; }

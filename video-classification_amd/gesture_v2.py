@@ -168,11 +168,38 @@ class ChalearnGestureFrames(torch.utils.data.Dataset):
             item["jitter"] = draw_color_jitter(1, *self.jitter)[0]
         return item
 
-    def __getitem__(self, index):
-        rgb_path, _depth_path, label = self.label_list[index]
-        rgb_path = Path(self.root, self.sample_base, rgb_path)
+    def _rgb_path_and_boxes(self, index) -> tuple:
+        rgb_path = Path(self.root, self.sample_base, self.label_list[index][0])
         with change_base(rgb_path, self.box_base).with_suffix(".pkl").open("rb") as f:
-            boxes = pickle.load(f)
+            return rgb_path, pickle.load(f)
+
+    # ---- what input_pipeline.ResidentGestureSet reads the train set through (MODEL.RESIDENT_TRAIN)
+    def seq_len(self, i: int) -> int:
+        return len(self._rgb_path_and_boxes(i)[1]) - 1
+
+    def label(self, i: int) -> int:
+        return self.label_list[i][2] - 1
+
+    def frame_boxes(self, i: int) -> torch.Tensor:
+        """(seq_len, 4) int32: every frame's union box over the parts, ``NO_BOX`` where none is there; reads the box pickle only"""
+        from .input_pipeline import NO_BOX
+        _, boxes = self._rgb_path_and_boxes(i)
+        rows = [self.compose.combine_spatial_box_xyxy(pb, self.parts) for pb in boxes[:len(boxes) - 1]]
+        return torch.tensor([NO_BOX if b is None else [int(v) for v in b] for b in rows], dtype=torch.int32).reshape(-1, 4)
+
+    def video_item(self, i: int, indices=None) -> dict:
+        """{'frames_pool': (L, H, W, 7) uint8 of the frames at indices (default: all seq_len of them), 'windows': (1, L)}"""
+        rgb_path, boxes = self._rgb_path_and_boxes(i)
+        indices = list(range(len(boxes) - 1)) if indices is None else list(indices)
+        flow = self.read_video(change_base(rgb_path, self.flow_base), 2, indices, "gray")
+        uv = self.read_video(change_base(rgb_path, self.uv_base), 2, indices, "gray")
+        rgb = self.read_video(rgb_path, 0, indices, "rgb24")
+        x = torch.cat([rgb, uv, flow], dim=1).permute(0, 2, 3, 1).contiguous()
+        return {"frames_pool": x, "windows": torch.arange(len(indices), dtype=torch.int32)[None]}
+
+    def __getitem__(self, index):
+        label = self.label_list[index][2]
+        rgb_path, boxes = self._rgb_path_and_boxes(index)
         seq_len = len(boxes) - 1                    # as the reference: the reader's frame count is one short
         if self.sampling == "random":
             return self._features_from_indices(random_sampling(seq_len, self.clip_len, self.rng), boxes, rgb_path, label)
@@ -182,19 +209,74 @@ class ChalearnGestureFrames(torch.utils.data.Dataset):
 
 class SyntheticGesture(torch.utils.data.Dataset):
     """Seeded stand-in with ChalearnGestureFrames' item contract: random uint8 frames of h x w with a random box per clip
-    (train -> dict, test -> list of dicts), for tests and tools/bench_v2.py."""
+    (train -> dict, test -> list of dicts), for tests and tools/bench_v2.py.
+    videos=True (train only): every video is ONE fixed run of frames_per_video = (lo, hi) seeded frames with a seeded
+    per-frame box table (every no_box_every-th frame has none: a ``NO_BOX`` row), a train item is a random clip of it, and
+    the set offers what ``input_pipeline.ResidentGestureSet`` reads a train set through -- seq_len, label, video_item and
+    frame_boxes.  The default construction does not offer them."""
 
     def __init__(self, cfg, name_of_set: str, num_videos: int = 8, clips_per_video=(1, 3), seed: int = 0,
-                 h: int = 240, w: int = 320, min_box: int = 15):
+                 h: int = 240, w: int = 320, min_box: int = 15, videos: bool = False, frames_per_video=None,
+                 no_box_every: int = 5):
         self.cfg, self.name = cfg, name_of_set
         self.t, self.h, self.w, self.min_box = int(cfg.CHALEARN.CLIP_LEN), h, w, min_box
         g = torch.Generator().manual_seed(seed)
         self.labels = torch.randint(0, cfg.CHALEARN.NUM_CLASS, (num_videos,), generator=g).tolist()
         self.nclips = torch.randint(clips_per_video[0], clips_per_video[1] + 1, (num_videos,), generator=g).tolist()
         self.seed = seed
+        self.videos = bool(videos)
+        if self.videos:
+            assert name_of_set == "train", "SyntheticGesture(videos=True) is a train set"
+            lo, hi = frames_per_video or (max(2, self.t // 2), 3 * self.t)
+            gv = torch.Generator().manual_seed(seed * 86028121 + 5)             # its own draws: the default mode's stay as they are
+            self.vframes = torch.randint(lo, hi + 1, (num_videos,), generator=gv).tolist()
+            self.no_box_every, self.rng = int(no_box_every), random
+            self.seq_len, self.label, self.video_item, self.frame_boxes = (self._seq_len, self._label, self._video_item,
+                                                                           self._frame_boxes)
 
     def __len__(self):
         return len(self.labels)
+
+    # ---- videos=True: the resident contract
+    def _seq_len(self, i: int) -> int:
+        return self.vframes[i]
+
+    def _label(self, i: int) -> int:
+        return self.labels[i]
+
+    def _video_frame(self, i: int, k: int) -> torch.Tensor:
+        g = torch.Generator().manual_seed((self.seed * 7919 + i) * 100003 + k)
+        return torch.randint(0, 256, (self.h, self.w, 7), generator=g, dtype=torch.uint8)
+
+    def _frame_boxes(self, i: int) -> torch.Tensor:
+        """frame 0 always has a box; every no_box_every-th frame after it has none"""
+        from .input_pipeline import NO_BOX
+        g = torch.Generator().manual_seed(self.seed * 6007 + i * 17 + 1)
+        rows = []
+        for k in range(self.vframes[i]):
+            x1 = int(torch.randint(0, self.w - self.min_box, (1,), generator=g))
+            y1 = int(torch.randint(0, self.h - self.min_box, (1,), generator=g))
+            x2 = int(torch.randint(x1 + self.min_box, self.w + 1, (1,), generator=g))
+            y2 = int(torch.randint(y1 + self.min_box, self.h + 1, (1,), generator=g))
+            rows.append(NO_BOX if k and self.no_box_every and k % self.no_box_every == 0 else (x1, y1, x2, y2))
+        return torch.tensor(rows, dtype=torch.int32)
+
+    def _video_item(self, i: int, indices=None) -> dict:
+        indices = list(range(self.vframes[i])) if indices is None else list(indices)
+        return {"frames_pool": torch.stack([self._video_frame(i, k) for k in indices]),
+                "windows": torch.arange(len(indices), dtype=torch.int32)[None]}
+
+    def _video_clip(self, i: int) -> dict:
+        """a train item of the loader path: a random clip of video i, its frames' union box"""
+        idx = random_sampling(self.vframes[i], self.t, self.rng)
+        b = self._frame_boxes(i)[idx]
+        box = torch.stack([b[:, 0].min(), b[:, 1].min(), b[:, 2].max(), b[:, 3].max()])
+        item = {"frames_u8": self._video_item(i, idx)["frames_pool"], "box": box, "label": self.labels[i]}
+        ranges = _train.jitter_ranges(self.cfg)
+        if ranges is not None:
+            from .input_pipeline import draw_color_jitter
+            item["jitter"] = draw_color_jitter(1, *ranges)[0]
+        return item
 
     def _clip(self, i, j):
         g = torch.Generator().manual_seed(self.seed * 7919 + i * 31 + j)
@@ -211,6 +293,8 @@ class SyntheticGesture(torch.utils.data.Dataset):
         return item
 
     def __getitem__(self, i):
+        if self.videos:
+            return self._video_clip(i)
         if self.name == "train":
             return self._clip(i, 0)
         return [self._clip(i, j) for j in range(self.nclips[i])]
@@ -251,14 +335,15 @@ class ModelManager(_train.ModelManager):
 
     def _prepare_v2_data(self, batch):
         """-> [slow (N, 5, T, S, S), fast (N, 2, T, S, S)], labels.  The uint8 batch {'frames_u8', 'box'[, 'crop']} is
-        resized on the device into one (N, T, 7, S, S) tensor whose channel slices are the two pathways (no copy); the
+        resized on the device into one (N, T, 7, S, S) tensor whose channel slices are the two pathways (no copy); a
+        'clip_v2' batch (input_pipeline.ResidentGestureSet, MODEL.RESIDENT_TRAIN) already is that tensor; the
         float batch {'rgb', 'uv', 'flow'} is the reference's permute + cat (:761-769).  An optional 'jitter' (N, 8) entry
         (input_pipeline.draw_color_jitter) applies ColorJitter to the R, G, B planes on the device: after the resize and
         the crop of a uint8 batch ("Optional Augment (crop&pad, color jitter)", :608-611), to the device copy of 'rgb' of
         a float batch; the values are image values in [0, 1] (mean 0, std 1)."""
         y = self._h2d(batch["label"])
-        if "frames_u8" in batch:
-            x = self.roi_resize()(batch["frames_u8"], batch["box"], batch.get("crop"))
+        if "clip_v2" in batch or "frames_u8" in batch:
+            x = batch["clip_v2"] if "clip_v2" in batch else self.roi_resize()(batch["frames_u8"], batch["box"], batch.get("crop"))
             if "jitter" in batch:
                 self.color_jitter()(x, batch["jitter"])
             x = torch.permute(x, [0, 2, 1, 3, 4])
@@ -275,8 +360,9 @@ class Trainer(_train.Trainer):
     last smaller batch, uniform non-overlapping test windows; checkpoints, eval and the multi-process path as train.Trainer."""
     train_drop_last = False                              # :815
     momentum = 0.9                                       # :832
-    resident_refused = ("gesture_v2's frames are uncropped 240 x 320 x 7 and go through RoiResize, which has no index table "
-                        "to gather them from a frame pool")
+    resident_methods_missing = ("seq_len(i), label(i), video_item(i, indices=None) and frame_boxes(i), which ResidentGestureSet "
+                                "needs to gather RoiResize's uncropped 240 x 320 x 7 frames and their boxes from a frame pool "
+                                "(ChalearnGestureFrames and SyntheticGesture(videos=True) do)")
 
     def _model_manager(self, cfg, device, backend):
         return ModelManager(cfg, device=device, backend=backend)
@@ -284,6 +370,17 @@ class Trainer(_train.Trainer):
     def _make_step(self, eng, use_graph, reducer):
         return _train.TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer, optimizer="sgd",
                                 momentum=self.momentum)
+
+    def _offers_resident(self, train_set) -> bool:
+        from .input_pipeline import GESTURE_METHODS, offers_resident
+        return offers_resident(train_set, GESTURE_METHODS)
+
+    def _build_resident(self, train_set, backend):
+        """MODEL.RESIDENT_TRAIN: the uncropped frames stay on the device, a batch is one sfk_roi_resize_pool launch"""
+        from .input_pipeline import ResidentGestureSet
+        return ResidentGestureSet(train_set, self.cfg, self.device, backend, batch_size=self.batch_size,
+                                  drop_last=self.train_drop_last, num_workers=self.num_workers,
+                                  jitter=_train.jitter_ranges(self.cfg))
 
     def _reference_datasets(self):
         try:

@@ -18,6 +18,9 @@ feeds ``DevicePreprocess``; loaders that deliver float32 batches keep the refere
            the crops at their native, ragged sizes (the raw items) and ``PadResize`` writes the (S, S, 21) uint8 frames on
            the device with one ``sfk_u8_pad_resize_cubic`` launch (include/sfk_resize.h); cv2 is not installed here, the
            arithmetic is pinned to tests/ref_resize.py, parity with cv2 itself unpinned.
+  new_feature_test.py:590-661  the v2 part-box loader's crop + /255 + Resize: ``RoiResize`` (one ``sfk_roi_resize`` launch,
+           include/sfk_v2.h) from uploaded clips, ``FramePool.roi_gather`` / ``ResidentGestureSet`` (one ``sfk_roi_resize_pool``
+           launch, include/sfk_roi_pool.h) from the uncropped frames of the train videos kept in a pool on the device.
 torchvision is not installed here, so ToTensor / Normalize / RandomCrop are restated from their documented semantics;
 numerically this step is "parity unpinned" against torchvision itself (tests/test_aux_cpu.py pins it to plain torch).
 """
@@ -211,7 +214,9 @@ class FramePool:
     ``bytes_uploaded`` counts the frame bytes sent host to device.
     capacity: a FIXED number of arena slots -- the arena is allocated once, at the first ``add``, and never grows or moves
     (a video that finds no room is a RuntimeError; ``fits`` asks beforehand); ``gather`` with a crop table builds the
-    RandomCrop-ped train clips with ``sfk_u8_pool_gather_crop`` (include/sfk_resident.h).  ``ResidentTrainSet`` uses both."""
+    RandomCrop-ped train clips with ``sfk_u8_pool_gather_crop`` (include/sfk_resident.h).  ``ResidentTrainSet`` uses both.
+    ``roi_gather`` is ``RoiResize`` over the pool's frames: the part-box crop + /255 + bilinear resize of the v2 loader from a
+    table of arena slots, by ONE ``sfk_roi_resize_pool`` launch (include/sfk_roi_pool.h); ``ResidentGestureSet`` uses it."""
 
     def __init__(self, device="cuda", backend=None, fill: int = MISSING_BYTE, capacity: Optional[int] = None):
         self.be, self.device, self.fill = hip_backend(backend), torch.device(device), int(fill)
@@ -220,6 +225,7 @@ class FramePool:
         self.live = {}                          # base -> frames of that video
         self.bytes_uploaded = 0
         self._resize = {}                       # (size, channels) -> the PadResize of add_raw
+        self._byte_lut = None                   # roi_gather's table, made at its first call
         self.capacity = None if capacity is None else int(capacity)
         if self.capacity is not None and self.capacity <= 0:
             raise ValueError(f"FramePool: capacity {capacity} frames")
@@ -348,6 +354,40 @@ class FramePool:
                                         out, c0, c)(stream)
             return out
         self.be.u8_pool_gather(self.arena, h2d(idx, self.device), self.lut, self.fill, out, c0, c)(stream)
+        return out
+
+    def roi_gather(self, index_rows: torch.Tensor, box: torch.Tensor, size: int, out_dtype: torch.dtype = torch.float32,
+                   antialias: bool = True, crop: Optional[torch.Tensor] = None, padding: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(N, T) arena slots (or -1) and boxes (N, 4) = (x1, y1, x2, y2) -> the (N, T, c, size, size) clips ``RoiResize``
+        would write from the materialised frames (a -1 frame materialised as bytes of ``fill``), through ``byte_lut()``; crop
+        (N, 2) int32 (top, left): with RandomCrop(size, padding) after the resize (padding defaults to size // 10, as
+        RoiResize's).  The same liveness check of every index as ``gather``; ONE ``sfk_roi_resize_pool`` launch on the
+        current stream; the H2D of the index, box and crop tables only."""
+        idx = torch.as_tensor(index_rows, dtype=torch.int32).contiguous()
+        assert idx.dim() == 2 and idx.numel() > 0 and self.arena is not None
+        ok = torch.zeros(self.arena.shape[0] + 1, dtype=torch.bool)      # the last entry stands for -1
+        ok[-1] = True
+        for b, n in self.live.items():
+            ok[b:b + n] = True
+        if int(idx.min()) < -1 or int(idx.max()) >= self.arena.shape[0] or not bool(ok[idx.long()].all()):
+            raise ValueError("roi_gather: an index is neither -1 nor a slot of a video that is in the pool")
+        n, size = idx.shape[0], int(size)
+        box = torch.as_tensor(box).to(torch.int32).contiguous()
+        assert tuple(box.shape) == (n, 4), tuple(box.shape)
+        pad = 0
+        if crop is not None:
+            crop = torch.as_tensor(crop).to(torch.int32).contiguous()
+            assert tuple(crop.shape) == (n, 2), tuple(crop.shape)
+            pad = size // 10 if padding is None else int(padding)
+            crop = h2d(crop, self.device)
+        if self._byte_lut is None:
+            self._byte_lut = byte_lut().to(self.device)
+        if out is None:
+            out = torch.empty(n, idx.shape[1], self.arena.shape[3], size, size, dtype=out_dtype, device=self.device)
+        stream = stream_of(self.device)
+        self.be.roi_resize_pool(self.arena, h2d(idx, self.device), self._byte_lut, self.fill, h2d(box, self.device), out,
+                                bool(antialias), crop, pad)(stream)
         return out
 
 
@@ -592,9 +632,9 @@ class RoiResize:
 RESIDENT_METHODS = ("seq_len", "label", "video_item")
 
 
-def offers_resident(train_set) -> bool:
-    """does the dataset offer the three cheap methods ``ResidentTrainSet`` reads it through?"""
-    return all(callable(getattr(train_set, m, None)) for m in RESIDENT_METHODS)
+def offers_resident(train_set, methods=RESIDENT_METHODS) -> bool:
+    """does the dataset offer the cheap methods a resident set reads it through (default: ``ResidentTrainSet``'s three)?"""
+    return all(callable(getattr(train_set, m, None)) for m in methods)
 
 
 class _VideoRequests(torch.utils.data.Dataset):
@@ -612,52 +652,33 @@ class _VideoRequests(torch.utils.data.Dataset):
         return self.train_set.video_item(i) if indices is None else self.train_set.video_item(i, indices)
 
 
-class ResidentTrainSet:
-    """The train set of the v1 loader with its decoded frames kept on the device: one ``FramePool(capacity=)`` arena, a
-    deterministic sampling plan drawn here, in the main process, and a dataset that is consulted only for frames that are not
-    on the device yet.  The reference's train loop draws one random window per video per epoch (dataset/chalearn_dataset.py:
-    123-129) and decodes its frames again every time; here a video is decoded ONCE, when a clip first touches it, and every
-    batch after that is one ``sfk_u8_pool_gather_crop`` launch (include/sfk_resident.h) plus the H2D of two small tables.
+class _ResidentSet:
+    """What ``ResidentTrainSet`` (v1) and ``ResidentGestureSet`` (v2) share: one ``FramePool(capacity=)`` arena, a
+    deterministic sampling plan drawn here, in the main process, the residency and spill rules and the epoch loop.  A derived
+    class says what a clip's plan rows are beside its frame indices (``_clip_rows``), how a dataset item enters the pool
+    (``_upload``) and how a batch is gathered from the arena slots (``_batch``).
 
-    train_set offers ``seq_len(i)`` (frame names of video i, nothing read), ``label(i)`` (0-based) and ``video_item(i,
-    indices=None)`` (``make_pooled_item`` / ``make_raw_pooled_item`` over those frames, default all, 'windows' of shape
-    (1, len(indices))).
-
-    Arena: capacity_frames slots (default floor(MODEL.RESIDENT_GB * 2^30 / (S*S*21))); the last batch_size * CLIP_LEN of
-    them are the spill region, the rest the resident region.
     Plan: a function of (seed, epoch) only.  ``plan(e)`` = the batches of torch.randperm(len, manual_seed(seed + e)), each
-    (videos, indices (N, T), crop (N, 2), jitter (N, 8) | None); per clip a generator seeded from (seed, epoch, video) draws
-    the start (random_sampling: randint(0, max(0, seq_len - clip_len)), indices (start + k) % seq_len), then the crop
-    (``draw_crop_offsets``), then, under MODEL.COLOR_JITTER, the jitter row (``draw_color_jitter``).
+    (videos, indices (N, T), <the derived class's columns>, jitter (N, 8) | None); per clip a generator seeded from (seed,
+    epoch, video) draws the start (random_sampling: randint(0, max(0, seq_len - clip_len)), indices (start + k) % seq_len),
+    then the derived class's draws, then, under MODEL.COLOR_JITTER, the jitter row (``draw_color_jitter``).
     Residency: decided in plan order and never revoked.  A video met for the first time becomes resident if resident_used +
     seq_len(i) still fits the resident region: it is read whole, once, and kept for the life of this object.  One that does
     not fit is spilled: only its clip's distinct frames are read, into slots released right after the batch's gather is
     enqueued (stream order keeps them intact until that gather has run).  Within a batch the resident uploads precede the
     spilled ones, so the resident videos pack densely from slot 0 and the spills never fragment their region.
-    ``epoch(e)`` yields {'<key>': (N, T, 21, S, S) float32 on the device, 'label': (N,), optionally 'jitter': (N, 8)}: what
-    every model's prepare_data takes under the float key (like pooled eval, whatever MODEL.U8_STEM says).
     Counters: bytes_uploaded (the pool's), resident_videos, resident_frames (arena slots they hold), spilled_clips (of the
     epoch running or last run), spill_peak (most spill slots ever live at once)."""
+    methods = RESIDENT_METHODS                  # what the train set must offer
 
-    def __init__(self, train_set, cfg, device="cuda", backend=None, batch_size: int = 1, drop_last: bool = True, seed: int = 0,
-                 capacity_frames: Optional[int] = None, num_workers: int = 0, jitter=None):
-        if not offers_resident(train_set):
-            raise ValueError("ResidentTrainSet: the train set must offer seq_len(i), label(i) and video_item(i, indices=None)")
-        from .config import crop_resize_dict
-        self.train_set, self.cfg, self.device = train_set, cfg, torch.device(device)
-        self.key = cfg.MODEL.R3D_INPUT
-        self.size = int(crop_resize_dict[self.key])
+    def __init__(self, train_set, cfg, device, backend, batch_size, drop_last, seed, num_workers, jitter):
+        if not offers_resident(train_set, self.methods):
+            raise ValueError(f"{type(self).__name__}: the train set must offer " + ", ".join(
+                f"{m}(i, indices=None)" if m == "video_item" else f"{m}(i)" for m in self.methods))
+        self.train_set, self.cfg, self.device, self.backend = train_set, cfg, torch.device(device), backend
         self.clip_len = int(cfg.CHALEARN.CLIP_LEN)
         self.batch_size, self.drop_last, self.seed = int(batch_size), bool(drop_last), int(seed)
         self.num_workers, self.jitter = int(num_workers), (None if jitter is None else tuple(jitter))
-        if capacity_frames is None:
-            capacity_frames = int(float(cfg.MODEL.RESIDENT_GB) * 2 ** 30 // (self.size * self.size * 21))
-        self.capacity, self.spill_slots = int(capacity_frames), self.batch_size * self.clip_len
-        self.resident_slots = self.capacity - self.spill_slots
-        if self.resident_slots <= 0:
-            raise ValueError(f"ResidentTrainSet: {self.capacity} arena frames leave no resident slot beside the spill region of "
-                             f"batch_size * CLIP_LEN = {self.spill_slots}")
-        self.pool = FramePool(self.device, backend, capacity=self.capacity)
         self._seq_len = {}                      # video -> seq_len(i), asked once
         self._resident = {}                     # video -> True (resident) | False (spilled for good), in decision order
         self._rows = {}                         # loaded resident video -> (seq_len,) int32 arena slot of every frame, -1 missing
@@ -665,6 +686,15 @@ class ResidentTrainSet:
         self.resident_frames = 0
         self.spilled_clips = 0
         self.spill_peak = 0
+
+    def _make_pool(self, capacity_frames: int) -> None:
+        """the arena of capacity_frames slots: the last batch_size * CLIP_LEN of them are the spill region"""
+        self.capacity, self.spill_slots = int(capacity_frames), self.batch_size * self.clip_len
+        self.resident_slots = self.capacity - self.spill_slots
+        if self.resident_slots <= 0:
+            raise ValueError(f"{type(self).__name__}: {self.capacity} arena frames leave no resident slot beside the spill region "
+                             f"of batch_size * CLIP_LEN = {self.spill_slots}")
+        self.pool = FramePool(self.device, self.backend, capacity=self.capacity)
 
     # ---- counters
     @property
@@ -693,16 +723,17 @@ class ResidentTrainSet:
             videos = order[at:at + self.batch_size]
             if len(videos) < self.batch_size and self.drop_last:
                 break
-            indices, crop, jitter = [], [], []
+            indices, rows, jitter = [], [], []
             for v in videos:
                 g, length = self._clip_generator(epoch, v), self.seq_len(v)
                 start = int(torch.randint(0, max(0, length - self.clip_len) + 1, (1,), generator=g))
                 indices.append([(start + k) % length for k in range(self.clip_len)])
-                crop.append(draw_crop_offsets(1, self.size // 10, g)[0])
+                rows.append(self._clip_rows(g, v, indices[-1]))
                 if self.jitter is not None:
                     jitter.append(draw_color_jitter(1, *self.jitter, generator=g)[0])
-            batches.append((videos, torch.tensor(indices, dtype=torch.int32), torch.stack(crop),
-                            torch.stack(jitter) if jitter else None))
+            columns = tuple(None if col[0] is None else torch.stack(col) for col in zip(*rows))
+            batches.append((videos, torch.tensor(indices, dtype=torch.int32)) + columns
+                           + (torch.stack(jitter) if jitter else None,))
         return batches
 
     # ---- residency and loading
@@ -715,18 +746,15 @@ class ResidentTrainSet:
         return self._resident[video]
 
     def _add(self, item) -> tuple:
-        """(base, (L,) int32 arena slot of every requested frame, -1 for a missing one) of a pooled or raw pooled item"""
+        """(base, (L,) int32 arena slot of every requested frame, -1 for a missing one) of a dataset item"""
         windows = torch.as_tensor(item["windows"], dtype=torch.int32)
-        if rawpool_key(self.key) in item:
-            base = self.pool.add_raw(item[rawpool_key(self.key)], item["raw_hw"], self.size, windows)
-        else:
-            base = self.pool.add(item[pool_key(self.key)], windows)
+        base = self._upload(item, windows)
         return base, self.pool.rows(base, windows)[0]
 
     def epoch(self, epoch: int):
         plan = self.plan(epoch)
         requests, per_batch = [], []            # per batch: (videos that become resident now, [(clip n, distinct indices)])
-        for videos, indices, _, _ in plan:
+        for videos, indices, *_ in plan:
             new, spill = [], []
             for n, v in enumerate(videos):
                 if self._decide(v):
@@ -741,7 +769,8 @@ class ResidentTrainSet:
             items = iter(torch.utils.data.DataLoader(_VideoRequests(self.train_set, requests), batch_size=None, shuffle=False,
                                                      num_workers=self.num_workers))
         self.spilled_clips = 0
-        for (videos, indices, crop, jitter), (new, spill) in zip(plan, per_batch):
+        for entry, (new, spill) in zip(plan, per_batch):
+            videos, indices, jitter = entry[0], entry[1], entry[-1]
             for v in new:                       # the resident uploads first: no spill slot is live, they pack densely
                 base, rows = self._add(next(items))
                 assert rows.numel() == self.seq_len(v), (v, rows.numel(), self.seq_len(v))
@@ -759,10 +788,120 @@ class ResidentTrainSet:
                     table[n] = self._rows[v][indices[n].long()]
             self.spilled_clips += len(bases)
             self.spill_peak = max(self.spill_peak, sum(self.pool.live[b] for b in bases))
-            clip = self.pool.gather(table, torch.float32, 0, None, crop=crop)
+            batch = self._batch(table, entry)
             for b in bases:                     # free for the uploads queued behind that gather on the same stream
                 self.pool.release(b)
-            batch = {self.key: clip, "label": torch.tensor([int(self.train_set.label(v)) for v in videos], dtype=torch.int64)}
+            batch["label"] = torch.tensor([int(self.train_set.label(v)) for v in videos], dtype=torch.int64)
             if jitter is not None:
                 batch["jitter"] = jitter
             yield batch
+
+
+class ResidentTrainSet(_ResidentSet):
+    """The train set of the v1 loader with its decoded frames kept on the device (the machinery: ``_ResidentSet``).  The
+    reference's train loop draws one random window per video per epoch (dataset/chalearn_dataset.py:123-129) and decodes its
+    frames again every time; here a video is decoded ONCE, when a clip first touches it, and every batch after that is one
+    ``sfk_u8_pool_gather_crop`` launch (include/sfk_resident.h) plus the H2D of two small tables.
+
+    train_set offers ``seq_len(i)`` (frame names of video i, nothing read), ``label(i)`` (0-based) and ``video_item(i,
+    indices=None)`` (``make_pooled_item`` / ``make_raw_pooled_item`` over those frames, default all, 'windows' of shape
+    (1, len(indices))).
+
+    Arena: capacity_frames slots (default floor(MODEL.RESIDENT_GB * 2^30 / (S*S*21))); the last batch_size * CLIP_LEN of
+    them are the spill region, the rest the resident region.
+    Plan: ``plan(e)`` batches are (videos, indices (N, T), crop (N, 2), jitter (N, 8) | None); per clip the start, then the
+    crop (``draw_crop_offsets``), then the jitter row.
+    ``epoch(e)`` yields {'<key>': (N, T, 21, S, S) float32 on the device, 'label': (N,), optionally 'jitter': (N, 8)}: what
+    every model's prepare_data takes under the float key (like pooled eval, whatever MODEL.U8_STEM says)."""
+
+    def __init__(self, train_set, cfg, device="cuda", backend=None, batch_size: int = 1, drop_last: bool = True, seed: int = 0,
+                 capacity_frames: Optional[int] = None, num_workers: int = 0, jitter=None):
+        super().__init__(train_set, cfg, device, backend, batch_size, drop_last, seed, num_workers, jitter)
+        from .config import crop_resize_dict
+        self.key = cfg.MODEL.R3D_INPUT
+        self.size = int(crop_resize_dict[self.key])
+        if capacity_frames is None:
+            capacity_frames = int(float(cfg.MODEL.RESIDENT_GB) * 2 ** 30 // (self.size * self.size * 21))
+        self._make_pool(capacity_frames)
+
+    def _clip_rows(self, g, video, indices) -> tuple:
+        return (draw_crop_offsets(1, self.size // 10, g)[0],)
+
+    def _upload(self, item, windows) -> int:
+        if rawpool_key(self.key) in item:
+            return self.pool.add_raw(item[rawpool_key(self.key)], item["raw_hw"], self.size, windows)
+        return self.pool.add(item[pool_key(self.key)], windows)
+
+    def _batch(self, table, entry) -> dict:
+        return {self.key: self.pool.gather(table, torch.float32, 0, None, crop=entry[2])}
+
+
+GESTURE_METHODS = RESIDENT_METHODS + ("frame_boxes",)
+NO_BOX = (2 ** 31 - 1, 2 ** 31 - 1, -2 ** 31, -2 ** 31)   # frame_boxes' row of a frame without any of the parts: min/max ignore it
+
+
+class ResidentGestureSet(_ResidentSet):
+    """The train set of the v2 part-box loader (gesture_v2.py) with its decoded, UNCROPPED frames kept on the device (the
+    machinery: ``_ResidentSet``).  The reference decodes five videos per clip in every epoch (new_feature_test.py:590-606);
+    here a video is decoded once and every batch after that is one ``sfk_roi_resize_pool`` launch (include/sfk_roi_pool.h)
+    plus the H2D of its index, box and, when augmenting, crop tables.
+
+    train_set offers ``seq_len(i)``, ``label(i)`` (0-based), ``video_item(i, indices=None)`` = {'frames_pool': (L, H, W, 7)
+    uint8 [R, G, B, U, V, F0, F1] of those frames (default all), 'windows': (1, L)} and ``frame_boxes(i)`` = (seq_len, 4) int32,
+    a frame's union box over MODEL.PARTS, ``NO_BOX`` for a frame with none of them; frame_boxes is asked once per video.
+
+    Arena: frames of (H, W, 7), the shape of frame 0 of video 0, read once when this object is built; capacity_frames slots
+    (default floor(MODEL.RESIDENT_GB * 2^30 / (H*W*7))), the last batch_size * CLIP_LEN of them the spill region.
+    Plan: ``plan(e)`` batches are (videos, indices (N, T), box (N, 4), crop (N, 2) | None, jitter (N, 8) | None); per clip the
+    start exactly as v1 draws it, the crop row (``draw_crop_offsets``, padding S // 10) only with augment=True (the reference
+    trains with do_augment=False, new_feature_test.py:814), then the jitter row.  A clip's box is the min / max over the
+    frame_boxes rows of its indices, clamped as ``ChalearnGestureFrames.clip_box`` clamps it; an empty one is a ValueError
+    naming the video, raised by ``plan``.
+    ``epoch(e)`` yields {'clip_v2': (N, T, 7, S, S) on the device in MODEL.DTYPE, 'label': (N,), optionally 'jitter': (N, 8)},
+    S = MODEL.INPUT_SIZE, resized with MODEL.RESIZE_ANTIALIAS: what ``RoiResize`` writes from the same frames and boxes."""
+    methods = GESTURE_METHODS
+    key = "frames"                              # video_item's pool entry is pool_key(key)
+
+    def __init__(self, train_set, cfg, device="cuda", backend=None, batch_size: int = 1, drop_last: bool = False, seed: int = 0,
+                 capacity_frames: Optional[int] = None, num_workers: int = 0, jitter=None, augment: bool = False):
+        super().__init__(train_set, cfg, device, backend, batch_size, drop_last, seed, num_workers, jitter)
+        from .slowfast import _DTYPES
+        self.size, self.augment = int(cfg.MODEL.INPUT_SIZE), bool(augment)
+        self.out_dtype = _DTYPES[str(cfg.MODEL.get("DTYPE", "fp32")).lower()]
+        self.antialias = bool(cfg.MODEL.get("RESIZE_ANTIALIAS", True))
+        probe = train_set.video_item(0, [0])[pool_key(self.key)]
+        assert probe.dtype == torch.uint8 and probe.dim() == 4 and probe.shape[0] == 1, (probe.dtype, tuple(probe.shape))
+        self.frame_shape = tuple(int(v) for v in probe.shape[1:])
+        if capacity_frames is None:
+            h, w, p = self.frame_shape
+            capacity_frames = int(float(cfg.MODEL.RESIDENT_GB) * 2 ** 30 // (h * w * p))
+        self._make_pool(capacity_frames)
+        self._boxes = {}                        # video -> frame_boxes(i), asked once
+
+    def frame_boxes(self, i: int) -> torch.Tensor:
+        if i not in self._boxes:
+            b = torch.as_tensor(self.train_set.frame_boxes(i)).to(torch.int32)
+            assert tuple(b.shape) == (self.seq_len(i), 4), (i, tuple(b.shape), self.seq_len(i))
+            self._boxes[i] = b
+        return self._boxes[i]
+
+    def clip_box(self, video: int, indices) -> torch.Tensor:
+        """int32 (x1, y1, x2, y2): the union of the clip's frame boxes, clamped to the frame"""
+        b = self.frame_boxes(video)[torch.as_tensor(indices, dtype=torch.long)]
+        h, w = self.frame_shape[:2]
+        x1, y1, x2, y2 = int(b[:, 0].min()), int(b[:, 1].min()), int(b[:, 2].max()), int(b[:, 3].max())
+        if x1 > x2:                             # every row is NO_BOX
+            raise ValueError(f"video {video}: no part box in any frame of the clip {list(indices)}")
+        x1, y1, x2, y2 = max(0, x1), max(0, y1), min(x2, w), min(y2, h)
+        if x2 <= x1 or y2 <= y1:
+            raise ValueError(f"video {video}: empty part box {(x1, y1, x2, y2)} in a {w}x{h} frame")
+        return torch.tensor([x1, y1, x2, y2], dtype=torch.int32)
+
+    def _clip_rows(self, g, video, indices) -> tuple:
+        return (self.clip_box(video, indices), draw_crop_offsets(1, self.size // 10, g)[0] if self.augment else None)
+
+    def _upload(self, item, windows) -> int:
+        return self.pool.add(item[pool_key(self.key)], windows)
+
+    def _batch(self, table, entry) -> dict:
+        return {"clip_v2": self.pool.roi_gather(table, entry[2], self.size, self.out_dtype, self.antialias, crop=entry[3])}

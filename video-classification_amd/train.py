@@ -756,28 +756,34 @@ class Trainer:
                                f"importable here ({e}); pass train_set/test_set (e.g. SyntheticChalearn)") from e
         return ChalearnVideoDataset(self.cfg, 'train'), ChalearnVideoDataset(self.cfg, 'test')
 
-    resident_refused = None                              # a derived trainer that cannot train from a frame pool says why
+    # ---- MODEL.RESIDENT_TRAIN; a derived trainer (gesture_v2.Trainer) swaps the contract it asks for and the set it builds
+    resident_methods_missing = ("seq_len(i), label(i) and video_item(i, indices=None) "
+                                "(ChalearnVideoFramesU8 and SyntheticChalearn(as_uint8 / raw) do)")
+
+    def _offers_resident(self, train_set) -> bool:
+        from .input_pipeline import offers_resident
+        return offers_resident(train_set)
+
+    def _build_resident(self, train_set, backend):
+        from .input_pipeline import ResidentTrainSet
+        return ResidentTrainSet(train_set, self.cfg, self.device, backend, batch_size=self.batch_size,
+                                drop_last=self.train_drop_last, num_workers=self.num_workers, jitter=jitter_ranges(self.cfg))
 
     def _make_resident(self, train_set, backend):
-        """MODEL.RESIDENT_TRAIN: the ResidentTrainSet train_epoch iterates instead of the train loader"""
-        from .input_pipeline import ResidentTrainSet, offers_resident
+        """MODEL.RESIDENT_TRAIN: the resident set (v1: ResidentTrainSet) train_epoch iterates instead of the train loader"""
         why = None
-        if self.resident_refused:
-            why = self.resident_refused
-        elif train_set is None:
+        if train_set is None:
             why = ("it needs the train SET (train_set=), whose frames it keeps on the device; a ready-made train_loader= only "
                    "hands over finished batches")
-        elif not offers_resident(train_set):
-            why = (f"{type(train_set).__name__} does not offer seq_len(i), label(i) and video_item(i, indices=None) "
-                   "(ChalearnVideoFramesU8 and SyntheticChalearn(as_uint8 / raw) do)")
+        elif not self._offers_resident(train_set):
+            why = f"{type(train_set).__name__} does not offer {self.resident_methods_missing}"
         elif self.world > 1:
             why = "a per-rank partition of the resident set is not built yet: WORLD_SIZE must be 1"
         elif self.cfg.MODEL.NAME == "res2d" and self.mm._res2d_backend() == "torch":
             why = "MODEL.NAME res2d with the torch backend is host plumbing and has no device kernels; use RES2D_BACKEND = 'engine'"
         if why is not None:
             raise ValueError(f"MODEL.RESIDENT_TRAIN: {why}")
-        return ResidentTrainSet(train_set, self.cfg, self.device, backend, batch_size=self.batch_size,
-                                drop_last=self.train_drop_last, num_workers=self.num_workers, jitter=jitter_ranges(self.cfg))
+        return self._build_resident(train_set, backend)
 
     def _make_loaders(self, tr, te):
         """train.py:164,170: train = shuffle + drop_last, test = whole videos, identity collate.  world > 1: one shuffled
