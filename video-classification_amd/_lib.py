@@ -253,6 +253,17 @@ class _RoiPoolDesc(C.Structure):
                 ("dt", C.c_int64), ("dc", C.c_int64), ("dh", C.c_int64), ("c_off", C.c_int32)]
 
 
+class _RoiRaggedDesc(C.Structure):
+    """include/sfk_roi_ragged.h sfk_roi_ragged_desc: sfk_roi_desc with its source addressing replaced by a byte arena -- frame
+    t of clip n is hw[n] = (h_n, w_n) pixels of pixel_pitch packed bytes at arena + offset[n][t]"""
+    _fields_ = [("struct_size", C.c_uint32), ("antialias", C.c_int32), ("arena", C.c_void_p), ("arena_bytes", C.c_int64),
+                ("pixel_pitch", C.c_int32), ("c0", C.c_int32), ("c", C.c_int32), ("n", C.c_int32), ("t", C.c_int32),
+                ("max_h", C.c_int32), ("max_w", C.c_int32), ("offset", C.c_void_p), ("hw", C.c_void_p), ("lut", C.c_void_p),
+                ("box", C.c_void_p), ("crop", C.c_void_p), ("pad", C.c_int32), ("fill", C.c_int32), ("out_h", C.c_int32),
+                ("out_w", C.c_int32), ("dst_dtype", C.c_int32), ("dst", C.c_void_p), ("dn", C.c_int64), ("dt", C.c_int64),
+                ("dc", C.c_int64), ("dh", C.c_int64), ("c_off", C.c_int32)]
+
+
 class _ResizeDesc(C.Structure):
     """include/sfk_resize.h sfk_resize_desc: frame f is the contiguous HWC bytes src[offset[f] ...] of hw[f] = (h, w) pixels
     and c channels; its padded, cubic-resized (size, size, c) frame lands at out + f*out_frame_stride"""
@@ -410,6 +421,13 @@ SIGNATURES_ROI_POOL = {
     "sfk_roi_pool_abi_version": [],
     "sfk_roi_resize_pool": [C.POINTER(_RoiPoolDesc), _PV],
 }
+# include/sfk_roi_ragged.h: the v2 trainer's box-cropped resident train set (ROI crop-resize from a byte arena of ragged
+# frames), same library, its own header and version
+ROI_RAGGED_ABI_VERSION = 1   # include/sfk_roi_ragged.h SFK_ROI_RAGGED_ABI_VERSION
+SIGNATURES_ROI_RAGGED = {
+    "sfk_roi_ragged_abi_version": [],
+    "sfk_roi_resize_ragged": [C.POINTER(_RoiRaggedDesc), _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
@@ -469,6 +487,12 @@ def new_roi_pool_desc() -> "_RoiPoolDesc":
     return d
 
 
+def new_roi_ragged_desc() -> "_RoiRaggedDesc":
+    d = _RoiRaggedDesc()
+    d.struct_size = C.sizeof(_RoiRaggedDesc)
+    return d
+
+
 def new_resize_desc() -> "_ResizeDesc":
     d = _ResizeDesc()
     d.struct_size = C.sizeof(_ResizeDesc)
@@ -493,7 +517,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
                        "(there is no CPU or PyTorch fallback for the SlowFast path)")
     lib = C.CDLL(path)
     for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL,
-                  SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL):
+                  SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL, SIGNATURES_ROI_RAGGED):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -516,6 +540,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk resident ABI version mismatch: library {lib.sfk_resident_abi_version()}, binding {RESIDENT_ABI_VERSION}")
     if lib.sfk_roi_pool_abi_version() != ROI_POOL_ABI_VERSION:
         raise SfkError(f"libsfk roi_pool ABI version mismatch: library {lib.sfk_roi_pool_abi_version()}, binding {ROI_POOL_ABI_VERSION}")
+    if lib.sfk_roi_ragged_abi_version() != ROI_RAGGED_ABI_VERSION:
+        raise SfkError(f"libsfk roi_ragged ABI version mismatch: library {lib.sfk_roi_ragged_abi_version()}, binding {ROI_RAGGED_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -1068,6 +1094,35 @@ class HipBackend:
         d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
         d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
         return self._plain("sfk_roi_resize_pool", C.byref(d), keep=(d, pool, index, lut, box, out, crop))
+
+    def roi_resize_ragged(self, arena, offset, hw, lut, fill: int, box, out, antialias: bool, crop=None, pad: int = 0,
+                          pitch: int = 7, c0: int = 0, c: Optional[int] = None, c_off: int = 0, max_hw=None):
+        """sfk_roi_resize_ragged (include/sfk_roi_ragged.h): ``roi_resize`` whose clip (n, t) is the hw[n] = (h_n, w_n) pixels
+        of ``pitch`` packed bytes at arena[offset[n, t]:], channels c0 .. c0+c-1 -- or the constant image of byte fill when
+        that frame does not lie in the arena; arena 1-D uint8, 4-byte aligned, a multiple of 4 bytes; offset (N,T) int64, hw
+        (N,2) int32, box (N,4) int32 in the rectangle's coordinates and crop (N,2) int32 | None on the device, read when the
+        launch runs; max_hw = (max_h, max_w) bounds every hw row and sizes the tile (None: read from hw, which
+        synchronises); out (N,T,C',S,S') f32|bf16 with unit W stride, channels c_off .. c_off+c-1 written."""
+        c = pitch - c0 if c is None else c
+        assert arena.dtype == torch.uint8 and arena.dim() == 1 and arena.is_contiguous() and 0 <= c0 and 0 < c and c0 + c <= pitch
+        assert offset.dtype == torch.int64 and offset.dim() == 2 and offset.is_contiguous()
+        n, t = offset.shape
+        assert hw.dtype == torch.int32 and hw.is_contiguous() and tuple(hw.shape) == (n, 2)
+        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
+        assert box.dtype == torch.int32 and box.is_contiguous() and tuple(box.shape) == (n, 4)
+        assert out.dim() == 5 and out.stride(4) == 1 and out.shape[0] == n and out.shape[1] == t and c_off + c <= out.shape[2]
+        assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (n, 2))
+        if max_hw is None:
+            max_hw = tuple(max(int(v), 1) for v in hw.max(0).values.tolist())
+        d = new_roi_ragged_desc()
+        d.antialias, d.arena, d.arena_bytes, d.offset, d.hw = 1 if antialias else 0, arena.data_ptr(), arena.numel(), offset.data_ptr(), hw.data_ptr()
+        d.lut, d.box, d.crop = lut.data_ptr(), box.data_ptr(), _ptr(crop)
+        d.pixel_pitch, d.c0, d.c, d.n, d.t, d.pad, d.fill = int(pitch), c0, c, n, t, int(pad), int(fill)
+        d.max_h, d.max_w = int(max_hw[0]), int(max_hw[1])
+        d.out_h, d.out_w = out.shape[3], out.shape[4]
+        d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
+        d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
+        return self._plain("sfk_roi_resize_ragged", C.byref(d), keep=(d, arena, offset, hw, lut, box, out, crop))
 
     def u8_pad_resize_cubic(self, src, offset, hw, out, size: int, max_side: int, fill: int):
         """sfk_u8_pad_resize_cubic (include/sfk_resize.h): src 1-D uint8, the frames' HWC bytes; offset (F,) int64 and hw (F, 2)

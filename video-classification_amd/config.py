@@ -108,6 +108,7 @@ _C.MODEL.JITTER_SATURATION = 0.2
 _C.MODEL.JITTER_HUE = 0.1
 _C.MODEL.RESIDENT_TRAIN = False  # keep the decoded train frames on the device and gather the cropped clips there (input_pipeline.ResidentTrainSet)
 _C.MODEL.RESIDENT_GB = 32.0     # RESIDENT_TRAIN: the size of the frame arena, GiB (its last BATCH_SIZE * CLIP_LEN slots are the spill region)
+_C.MODEL.RESIDENT_STORE = 'frame'  # v2 RESIDENT_TRAIN: 'frame' keeps whole frames in a FramePool, 'box' only each video's part-box rectangle in a BoxArena of RESIDENT_GB bytes
 _C.DIST = CfgNode()
 _C.DIST.BUCKET_MB = 32         # gradient all-reduce bucket size
 

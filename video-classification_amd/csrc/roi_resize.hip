@@ -1,30 +1,38 @@
 // sfk_roi_resize (include/sfk_v2.h): part-box crop + uint8 table lookup + separable bilinear resize (F.interpolate,
 // align_corners=False, with or without antialiasing) + optional RandomCrop shift, one launch per batch -- and
-// sfk_roi_resize_pool (include/sfk_roi_pool.h): the same from frames that lie in a pool, picked by a table of frame indices.
-// The two entry points share one kernel and one launcher; the source addressing is a compile-time switch.
+// sfk_roi_resize_pool (include/sfk_roi_pool.h): the same from frames that lie in a pool, picked by a table of frame indices --
+// and sfk_roi_resize_ragged (include/sfk_roi_ragged.h): the same from frames stored cropped to their clip's own rectangle in a
+// byte arena, picked by a table of byte offsets.  The three entry points share one kernel and one launcher; the source
+// addressing is a compile-time switch.
 //
 // One workgroup owns a tile of B destination rows x TW destination columns of one (clip, frame), all channels:
 //   1. it reads the clip's box (and crop), builds the tap index / weight tables of its TW columns and B rows in LDS with
 //      torch's CPU arithmetic (upsample_bilinear2d's fused source index; _upsample_bilinear2d_aa's mixed float/double
 //      weights), and the byte table;
 //   2. it stages the source bytes its taps touch -- R rows x SP columns x c channels -- in LDS, as aligned dwords when the
-//      channels of a pixel are adjacent (HWC; a pool's frames always are), as bytes otherwise (planar); a pooled frame whose
-//      index is outside the pool is staged as bytes of `fill` and reads nothing;
+//      channels of a pixel are adjacent (HWC; a pool's and an arena's frames always are), as bytes otherwise (planar); a
+//      pooled frame whose index is outside the pool, or an arena frame that does not lie in the arena, is staged as bytes of
+//      `fill` and reads nothing;
 //   3. horizontal pass: R x c x TW fp32 band in LDS (taps in torch's order, no contraction);
 //   4. vertical pass: one coalesced row store per (channel, row), zeros where the crop shift leaves the resized image.
-// The host sizes B, TW, R and SP from the worst-case ratio frame / output, so every box fits its LDS; the kernel still
-// clamps every LDS index to what it staged, so a box the host did not foresee can neither write out of bounds nor read
-// unstaged memory.
+// The host sizes B, TW, R and SP from the worst-case ratio frame / output (of a ragged batch: its largest rectangle), so
+// every box fits its LDS; the kernel still clamps every LDS index to what it staged, so a box the host did not foresee can
+// neither write out of bounds nor read unstaged memory.
 #include <math.h>
 
 #include "sfk_common.h"
 #include "sfk_roi_pool.h"
+#include "sfk_roi_ragged.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxTaps = 2 * SFK_ROI_MAX_RATIO + 1;
 constexpr int kLdsBudget = 64 * 1024;
+// a ragged batch is sized from its own largest rectangle, which may admit a taller tile than the whole frame would; a tile
+// is taken only if three workgroups of it still share a CU's 160 KiB (10 x 20 clips of 240 x 320 to 192^2 with rectangles up
+// to 209 x 292: B 16 at 61 872 bytes, two workgroups a CU, ran 0.715 ms; B 8 at 38 992 bytes, four a CU, runs 0.454 ms)
+constexpr int kRaggedLdsBudget = 160 * 1024 / 3;
 
 struct RoiGeo {
   int B, TW, R, SP, KH, KW;
@@ -32,11 +40,18 @@ struct RoiGeo {
   int off_lut, off_xw, off_xi, off_yw, off_yi, off_sb, off_tmp, lds;
 };
 
-// what sfk_roi_resize_pool adds to the descriptor the kernel reads: there d.src = pool + c0, d.st = frame_stride, d.sh =
-// row_stride, d.sw = pixel_pitch, d.sc = 1 and d.sn is unused
-struct RoiPool {
+// where the kernel's source frames lie
+constexpr int kStacked = 0, kPool = 1, kRagged = 2;
+
+// what sfk_roi_resize_pool and sfk_roi_resize_ragged add to the descriptor the kernel reads.  Pool: d.src = pool + c0, d.st =
+// frame_stride, d.sh = row_stride, d.sw = pixel_pitch, d.sc = 1 and d.sn is unused.  Ragged: d.src = arena + c0, (d.h, d.w) =
+// (max_h, max_w), d.sw = pixel_pitch, d.sc = 1 and d.sn, d.st, d.sh are unused (a row is w_n * pixel_pitch bytes)
+struct RoiSrc {
   const int32_t* index;
   int frames, fill;
+  const int64_t* offset;
+  const int32_t* hw;
+  int64_t arena_bytes;
 };
 
 inline int align16(int v) { return (v + 15) & ~15; }
@@ -119,8 +134,8 @@ __device__ void roi_taps(int i, int in, int out, int aa, int K, int* idx, float*
   for (int k = 0; k < K; ++k) idx[k] = min(max(idx[k], 0), in - 1);
 }
 
-template <typename D, bool POOL>
-__global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, RoiGeo g, RoiPool p) {
+template <typename D, int SRC>
+__global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, RoiGeo g, RoiSrc p) {
   extern __shared__ __align__(16) unsigned char smem[];
   float* lut = reinterpret_cast<float*>(smem + g.off_lut);
   float* xw = reinterpret_cast<float*>(smem + g.off_xw);
@@ -137,10 +152,27 @@ __global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, Ro
   const int Bv = min(g.B, d.out_h - Y0), TWv = min(g.TW, d.out_w - X0);
   const int C = d.c, KH = g.KH, KW = g.KW;
 
+  // the frame extent and row stride: the descriptor's, or the clip's own rectangle; its table rows are read once per
+  // workgroup and are block-uniform.  A frame is missing unless it lies in the arena whole: no product here can overflow
+  // (h_n * w_n < 2^62, and the bytes left after o are divided, not the rectangle multiplied)
+  int H = d.h, W = d.w;
+  int64_t rstride = d.sh;
+  int64_t foff = 0;                                       // the frame's byte offset in the arena
+  bool miss = false;
+  if (SRC == kRagged) {
+    const int hn = p.hw[2 * (int64_t)n], wn = p.hw[2 * (int64_t)n + 1];
+    const int64_t o = p.offset[(int64_t)n * d.t + t];
+    H = min(max(hn, 1), d.h);
+    W = min(max(wn, 1), d.w);
+    miss = o < 0 || hn != H || wn != W || o > p.arena_bytes || (int64_t)hn * wn > (p.arena_bytes - o) / d.sw;
+    rstride = (int64_t)W * d.sw;
+    foff = miss ? 0 : o;                                  // 64-bit: an arena may exceed 2^31 bytes
+  }
+
   // the box, clamped the way a Python slice clamps it
   const int32_t* bx = d.box + 4 * (int64_t)n;
-  const int x1 = min(max(bx[0], 0), d.w - 1), y1 = min(max(bx[1], 0), d.h - 1);
-  const int x2 = min(max(bx[2], x1 + 1), d.w), y2 = min(max(bx[3], y1 + 1), d.h);
+  const int x1 = min(max(bx[0], 0), W - 1), y1 = min(max(bx[1], 0), H - 1);
+  const int x2 = min(max(bx[2], x1 + 1), W), y2 = min(max(bx[3], y1 + 1), H);
   const int bw = x2 - x1, bh = y2 - y1;
   int dy = 0, dx = 0;
   if (d.crop) {
@@ -172,27 +204,28 @@ __global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, Ro
   const int ncol = min(xhi - xlo + 1, g.SP), nrow = min(yhi - ylo + 1, g.R);
 
   // 2. stage the window's bytes: sb[(row * SP + col) * C + ch]
-  const uint8_t* base = d.src + (int64_t)(y1 + ylo) * d.sh + (int64_t)(x1 + xlo) * d.sw;
-  bool miss = false;
-  if (POOL) {
+  const uint8_t* base = d.src + (int64_t)(y1 + ylo) * rstride + (int64_t)(x1 + xlo) * d.sw;
+  if (SRC == kPool) {
     const int f = p.index[(int64_t)n * d.t + t];          // read once per workgroup; block-uniform
     miss = f < 0 || f >= p.frames;
     base += (int64_t)(miss ? 0 : f) * d.st;               // 64-bit: a pool may exceed 2^31 bytes
+  } else if (SRC == kRagged) {
+    base += foff;
   } else {
     base += n * d.sn + t * d.st;
   }
-  if (POOL && miss) {
+  if (SRC != kStacked && miss) {
     // a missing frame: the window's rows as dwords of the fill byte (sb is 16-byte aligned and nrow <= R), no global load
     const uint32_t v = 0x01010101u * (uint32_t)p.fill;
     const int nd = (nrow * g.SP * C + 3) >> 2;
     for (int q = tid; q < nd; q += kThreads) reinterpret_cast<uint32_t*>(sb)[q] = v;
-  } else if (POOL || (d.sc == 1 && d.sw >= C)) {
+  } else if (SRC != kStacked || (d.sc == 1 && d.sw >= C)) {
     // one aligned dword per lane over each row's bytes [first pixel, last pixel's channel C-1]: every dword holds at
     // least one byte of an in-frame pixel of the window
     const int pitch = (int)d.sw;
     const int rbytes = (ncol - 1) * pitch + C;
     for (int r = 0; r < nrow; ++r) {
-      const uint8_t* rp = base + (int64_t)r * d.sh;
+      const uint8_t* rp = base + (int64_t)r * rstride;
       const uintptr_t a0 = (uintptr_t)rp & ~(uintptr_t)3;
       const int nd = (int)(((uintptr_t)rp + rbytes + 3 - a0) >> 2);
       for (int q = tid; q < nd; q += kThreads) {
@@ -256,9 +289,9 @@ __global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, Ro
   }
 }
 
-// every host-side check the two entry points share (each checks its own struct_size and its own source first), then the
-// launch: p == nullptr is sfk_roi_resize's strided source, otherwise the pool's
-int roi_resize(const sfk_roi_desc* d, const RoiPool* p, sfk_stream_t stream) {
+// every host-side check the three entry points share (each checks its own struct_size and its own source first), then the
+// launch: p == nullptr is sfk_roi_resize's strided source, otherwise the pool's or the arena's
+int roi_resize(const sfk_roi_desc* d, int src, const RoiSrc* p, sfk_stream_t stream) {
   if (!d->src || !d->lut || !d->box || !d->dst) return SFK_ERR_INVALID;
   if (d->n <= 0 || d->t <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->out_h <= 0 || d->out_w <= 0) return SFK_ERR_INVALID;
   if (d->sn < 0 || d->st < 0 || d->sh < 0 || d->sw < 0 || d->sc < 0 || d->dn < 0 || d->dt < 0 || d->dc < 0 || d->dh < 0)
@@ -274,10 +307,13 @@ int roi_resize(const sfk_roi_desc* d, const RoiPool* p, sfk_stream_t stream) {
   const double spans_h = sh > 1.0 ? sh : 1.0, spans_w = sw > 1.0 ? sw : 1.0;
   RoiGeo g{};
   bool ok = false;
-  for (int TW : {64, 32, 16}) {
-    for (int B : {16, 8, 4, 2, 1}) {
-      g = roi_layout(B, TW, d->c, KH, KW, spans_h, spans_w, d->out_h, d->out_w);
-      if (g.lds <= kLdsBudget) { ok = true; break; }
+  for (int budget : {src == kRagged ? kRaggedLdsBudget : kLdsBudget, kLdsBudget}) {
+    for (int TW : {64, 32, 16}) {
+      for (int B : {16, 8, 4, 2, 1}) {
+        g = roi_layout(B, TW, d->c, KH, KW, spans_h, spans_w, d->out_h, d->out_w);
+        if (g.lds <= budget) { ok = true; break; }
+      }
+      if (ok) break;
     }
     if (ok) break;
   }
@@ -287,9 +323,10 @@ int roi_resize(const sfk_roi_desc* d, const RoiPool* p, sfk_stream_t stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)tiles, (unsigned)d->t, (unsigned)d->n);
   const bool bf = d->dst_dtype == SFK_BF16;
-  const auto kernel = p ? (bf ? roi_resize_kernel<bf16_t, true> : roi_resize_kernel<float, true>)
-                        : (bf ? roi_resize_kernel<bf16_t, false> : roi_resize_kernel<float, false>);
-  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), g.lds, s, *d, g, p ? *p : RoiPool{});
+  const auto kernel = src == kRagged ? (bf ? roi_resize_kernel<bf16_t, kRagged> : roi_resize_kernel<float, kRagged>)
+                      : src == kPool ? (bf ? roi_resize_kernel<bf16_t, kPool> : roi_resize_kernel<float, kPool>)
+                                     : (bf ? roi_resize_kernel<bf16_t, kStacked> : roi_resize_kernel<float, kStacked>);
+  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), g.lds, s, *d, g, p ? *p : RoiSrc{});
   SFK_CHECK_LAUNCH();
   return SFK_OK;
 }
@@ -298,7 +335,7 @@ int roi_resize(const sfk_roi_desc* d, const RoiPool* p, sfk_stream_t stream) {
 
 extern "C" int sfk_roi_resize(const sfk_roi_desc* d, sfk_stream_t stream) {
   if (!d || d->struct_size != sizeof(sfk_roi_desc)) return SFK_ERR_INVALID;
-  return roi_resize(d, nullptr, stream);
+  return roi_resize(d, kStacked, nullptr, stream);
 }
 
 extern "C" int sfk_roi_resize_pool(const sfk_roi_pool_desc* d, sfk_stream_t stream) {
@@ -317,9 +354,30 @@ extern "C" int sfk_roi_resize_pool(const sfk_roi_pool_desc* d, sfk_stream_t stre
   r.lut = d->lut, r.box = d->box, r.crop = d->crop, r.pad = d->pad;
   r.dst_dtype = d->dst_dtype, r.dst = d->dst;
   r.dn = d->dn, r.dt = d->dt, r.dc = d->dc, r.dh = d->dh, r.c_off = d->c_off;
-  const RoiPool p{d->index, d->frames, d->fill};
-  return roi_resize(&r, &p, stream);
+  const RoiSrc p{d->index, d->frames, d->fill, nullptr, nullptr, 0};
+  return roi_resize(&r, kPool, &p, stream);
+}
+
+extern "C" int sfk_roi_resize_ragged(const sfk_roi_ragged_desc* d, sfk_stream_t stream) {
+  if (!d || d->struct_size != sizeof(sfk_roi_ragged_desc)) return SFK_ERR_INVALID;
+  if (!d->arena || !d->offset || !d->hw || d->max_h <= 0 || d->max_w <= 0) return SFK_ERR_INVALID;
+  if (d->arena_bytes <= 0 || (d->arena_bytes & 3) || ((uintptr_t)d->arena & 3) || d->c0 < 0) return SFK_ERR_INVALID;
+  if ((int64_t)d->pixel_pitch < (int64_t)d->c0 + d->c) return SFK_ERR_INVALID;
+  if (d->fill < 0 || d->fill > 255) return SFK_ERR_INVALID;
+  sfk_roi_desc r{};
+  r.struct_size = sizeof(sfk_roi_desc);
+  r.antialias = d->antialias;
+  r.src = d->arena + d->c0;
+  r.sn = 0, r.st = 0, r.sh = 0, r.sw = d->pixel_pitch, r.sc = 1;
+  r.n = d->n, r.t = d->t, r.h = d->max_h, r.w = d->max_w, r.c = d->c;
+  r.out_h = d->out_h, r.out_w = d->out_w;
+  r.lut = d->lut, r.box = d->box, r.crop = d->crop, r.pad = d->pad;
+  r.dst_dtype = d->dst_dtype, r.dst = d->dst;
+  r.dn = d->dn, r.dt = d->dt, r.dc = d->dc, r.dh = d->dh, r.c_off = d->c_off;
+  const RoiSrc p{nullptr, 0, d->fill, d->offset, d->hw, d->arena_bytes};
+  return roi_resize(&r, kRagged, &p, stream);
 }
 
 extern "C" int sfk_roi_pool_abi_version(void) { return SFK_ROI_POOL_ABI_VERSION; }
+extern "C" int sfk_roi_ragged_abi_version(void) { return SFK_ROI_RAGGED_ABI_VERSION; }
 extern "C" int sfk_v2_abi_version(void) { return SFK_V2_ABI_VERSION; }

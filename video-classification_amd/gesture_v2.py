@@ -376,11 +376,13 @@ class Trainer(_train.Trainer):
         return offers_resident(train_set, GESTURE_METHODS)
 
     def _build_resident(self, train_set, backend):
-        """MODEL.RESIDENT_TRAIN: the uncropped frames stay on the device, a batch is one sfk_roi_resize_pool launch"""
+        """MODEL.RESIDENT_TRAIN: the frames stay on the device, whole (a batch is one sfk_roi_resize_pool launch) or, with
+        MODEL.RESIDENT_STORE: box, cropped to what their video's clips can read (one sfk_roi_resize_ragged launch)"""
         from .input_pipeline import ResidentGestureSet
         return ResidentGestureSet(train_set, self.cfg, self.device, backend, batch_size=self.batch_size,
                                   drop_last=self.train_drop_last, num_workers=self.num_workers,
-                                  jitter=_train.jitter_ranges(self.cfg))
+                                  jitter=_train.jitter_ranges(self.cfg),
+                                  store=str(self.cfg.MODEL.get("RESIDENT_STORE", "frame")))
 
     def _reference_datasets(self):
         try:

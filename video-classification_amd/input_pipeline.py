@@ -26,6 +26,8 @@ numerically this step is "parity unpinned" against torchvision itself (tests/tes
 """
 from __future__ import annotations
 
+import bisect
+
 from dataclasses import dataclass
 from typing import Optional
 
@@ -391,6 +393,132 @@ class FramePool:
         return out
 
 
+class BoxArena:
+    """A byte arena next to ``FramePool`` for frames that differ in shape from video to video: ONE uint8 tensor of
+    capacity_bytes (rounded down to a multiple of 16), allocated at the first ``add`` and never grown or moved.
+
+    ``add`` uploads the (L, h, w, P) frames of one block ONCE, through pinned memory, to the first free run of bytes that
+    starts at a multiple of 16 (first fit over the gaps between the live blocks) and returns that byte offset (its base);
+    ``offsets`` turns the block's window table into the byte offset of every frame; ``roi_gather`` builds the
+    (N, T, P, size, size) clips ``RoiResize`` would write from the frames behind any mix of offsets, each clip with its own
+    stored rectangle, by ONE ``sfk_roi_resize_ragged`` launch (include/sfk_roi_ragged.h); ``release`` returns a block's bytes.
+    Every copy and launch goes on the current stream, so a byte is never overwritten before the gather that read it has run.
+    ``bytes_uploaded`` counts the frame bytes sent host to device.  ``ResidentGestureSet(store='box')`` uses it."""
+    ALIGN = 16
+
+    def __init__(self, capacity_bytes: int, device="cuda", backend=None, fill: int = MISSING_BYTE):
+        self.be, self.device, self.fill = hip_backend(backend), torch.device(device), int(fill)
+        self.capacity = int(capacity_bytes) // self.ALIGN * self.ALIGN
+        if self.capacity <= 0:
+            raise ValueError(f"BoxArena: capacity {capacity_bytes} bytes")
+        self.arena: Optional[torch.Tensor] = None
+        self.live = {}                          # base -> (L, h, w, P) of that block
+        self.pitch: Optional[int] = None        # P: that of the first block, and of every block after it
+        self.bytes_uploaded = 0
+        self._byte_lut = None                   # roi_gather's table, made at its first call
+
+    @classmethod
+    def _span(cls, shape) -> int:
+        """the bytes a block of that shape holds in the arena: its own, rounded up to the alignment"""
+        l, h, w, p = shape
+        return -(-(l * h * w * p) // cls.ALIGN) * cls.ALIGN
+
+    def _place(self, nbytes: int) -> Optional[int]:
+        at = 0
+        for base in sorted(self.live):
+            if base - at >= nbytes:
+                return at
+            at = base + self._span(self.live[base])
+        return at if self.capacity - at >= nbytes else None
+
+    def fits(self, nbytes: int) -> bool:
+        """would ``add`` of a block of nbytes find room?"""
+        return int(nbytes) > 0 and self._place(-(-int(nbytes) // self.ALIGN) * self.ALIGN) is not None
+
+    def add(self, frames: torch.Tensor) -> int:
+        """upload (L, h, w, P) uint8 frames; the byte offset of the first"""
+        assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.numel() > 0, (frames.dtype, tuple(frames.shape))
+        shape = tuple(int(v) for v in frames.shape)
+        if self.pitch is not None and shape[3] != self.pitch:
+            raise ValueError(f"BoxArena: frames of {shape[3]} bytes a pixel in an arena of {self.pitch}")
+        base = self._place(self._span(shape))
+        if base is None:
+            raise RuntimeError(f"BoxArena: no room for {frames.numel()} more bytes in its fixed capacity of {self.capacity} "
+                               f"({sum(self._span(v) for v in self.live.values())} in use)")
+        if self.arena is None:
+            self.arena = torch.empty(self.capacity, dtype=torch.uint8, device=self.device)
+        src = frames.contiguous().view(-1)
+        if src.device.type == "cpu" and self.device.type == "cuda" and not src.is_pinned():
+            src = src.pin_memory()
+        self.arena[base:base + src.numel()].copy_(src, non_blocking=True)
+        self.live[base], self.pitch = shape, shape[3]
+        self.bytes_uploaded += src.numel()
+        return base
+
+    def offsets(self, base: int, windows: torch.Tensor) -> torch.Tensor:
+        """(K, T) int64 byte offsets of a block's windows (-1 stays -1)"""
+        l, h, w, p = self.live[base]
+        FramePool.check_windows(windows, l)
+        win = torch.as_tensor(windows, dtype=torch.int64)
+        return torch.where(win < 0, win, base + win * (h * w * p))
+
+    def release(self, base: int) -> None:
+        del self.live[base]
+
+    def _check_table(self, off: torch.Tensor, hw: torch.Tensor, box: torch.Tensor) -> None:
+        """every offset is -1 or the start of a frame of a live block whose (h, w) is its clip's hw row; every box lies in
+        its clip's rectangle (one that does not would silently differ from whole-frame storage)"""
+        bases = sorted(self.live)
+        for n in range(off.shape[0]):
+            h, w = (int(v) for v in hw[n])
+            x1, y1, x2, y2 = (int(v) for v in box[n])
+            if not (0 <= x1 < x2 <= w and 0 <= y1 < y2 <= h):
+                raise ValueError(f"roi_gather: box {(x1, y1, x2, y2)} of clip {n} is not inside its {w}x{h} rectangle")
+            for o in set(off[n].tolist()):
+                if o == -1:
+                    continue
+                k = bisect.bisect_right(bases, o) - 1
+                ok = k >= 0
+                if ok:
+                    l, bh, bw, p = self.live[bases[k]]
+                    rel, fb = o - bases[k], bh * bw * p
+                    ok = (bh, bw) == (h, w) and rel % fb == 0 and rel // fb < l
+                if not ok:
+                    raise ValueError(f"roi_gather: offset {o} of clip {n} is neither -1 nor the start of a {w}x{h} frame of a "
+                                     "block that is in the arena")
+
+    def roi_gather(self, offset_rows: torch.Tensor, hw: torch.Tensor, box: torch.Tensor, size: int,
+                   out_dtype: torch.dtype = torch.float32, antialias: bool = True, crop: Optional[torch.Tensor] = None,
+                   padding: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(N, T) byte offsets (or -1), the clips' stored rectangles hw (N, 2) = (h_n, w_n) and their boxes (N, 4) =
+        (x1, y1, x2, y2) IN those rectangles -> the (N, T, P, size, size) clips ``RoiResize`` would write from those frames (a
+        -1 frame as bytes of ``fill``), through ``byte_lut()``; crop and padding as ``FramePool.roi_gather``'s.  The host
+        checks of ``_check_table`` first; then ONE ``sfk_roi_resize_ragged`` launch on the current stream, its tile sized from
+        the largest rectangle of THIS batch, and the H2D of the offset, hw, box and crop tables only."""
+        off = torch.as_tensor(offset_rows, dtype=torch.int64).contiguous()
+        assert off.dim() == 2 and off.numel() > 0 and self.arena is not None
+        n, size = off.shape[0], int(size)
+        hw = torch.as_tensor(hw).to(torch.int32).contiguous()
+        box = torch.as_tensor(box).to(torch.int32).contiguous()
+        assert tuple(hw.shape) == (n, 2) and tuple(box.shape) == (n, 4), (tuple(hw.shape), tuple(box.shape))
+        self._check_table(off, hw, box)
+        pitch, pad = self.pitch, 0
+        if crop is not None:
+            crop = torch.as_tensor(crop).to(torch.int32).contiguous()
+            assert tuple(crop.shape) == (n, 2), tuple(crop.shape)
+            pad = size // 10 if padding is None else int(padding)
+            crop = h2d(crop, self.device)
+        if self._byte_lut is None:
+            self._byte_lut = byte_lut().to(self.device)
+        if out is None:
+            out = torch.empty(n, off.shape[1], pitch, size, size, dtype=out_dtype, device=self.device)
+        stream = stream_of(self.device)
+        self.be.roi_resize_ragged(self.arena, h2d(off, self.device), h2d(hw, self.device), self._byte_lut, self.fill,
+                                  h2d(box, self.device), out, bool(antialias), crop, pad, pitch=pitch,
+                                  max_hw=(int(hw[:, 0].max()), int(hw[:, 1].max())))(stream)
+        return out
+
+
 def raw_key(key: str) -> str:
     return key + "_raw"
 
@@ -638,18 +766,25 @@ def offers_resident(train_set, methods=RESIDENT_METHODS) -> bool:
 
 
 class _VideoRequests(torch.utils.data.Dataset):
-    """the reads an epoch of ``ResidentTrainSet`` still needs, in plan order: (video, None) = the whole video, (video,
-    indices) = those frames only; a DataLoader over it lets workers decode ahead of the step that consumes them"""
+    """the reads an epoch of a resident set still needs, in plan order: (video, None, rect) = the whole video, (video,
+    indices, rect) = those frames only; rect = (x1, y1, x2, y2) keeps only that rectangle of the frames under crop_key (a
+    slice made here, in the loader worker), None keeps them whole.  A DataLoader over it lets workers decode ahead of the
+    step that consumes them"""
 
-    def __init__(self, train_set, requests):
-        self.train_set, self.requests = train_set, requests
+    def __init__(self, train_set, requests, crop_key: Optional[str] = None):
+        self.train_set, self.requests, self.crop_key = train_set, requests, crop_key
 
     def __len__(self):
         return len(self.requests)
 
     def __getitem__(self, k):
-        i, indices = self.requests[k]
-        return self.train_set.video_item(i) if indices is None else self.train_set.video_item(i, indices)
+        i, indices, rect = self.requests[k]
+        item = self.train_set.video_item(i) if indices is None else self.train_set.video_item(i, indices)
+        if rect is not None:
+            x1, y1, x2, y2 = rect
+            item = dict(item)
+            item[self.crop_key] = item[self.crop_key][:, y1:y2, x1:x2].contiguous()
+        return item
 
 
 class _ResidentSet:
@@ -668,8 +803,13 @@ class _ResidentSet:
     enqueued (stream order keeps them intact until that gather has run).  Within a batch the resident uploads precede the
     spilled ones, so the resident videos pack densely from slot 0 and the spills never fragment their region.
     Counters: bytes_uploaded (the pool's), resident_videos, resident_frames (arena slots they hold), spilled_clips (of the
-    epoch running or last run), spill_peak (most spill slots ever live at once)."""
+    epoch running or last run), spill_peak (most spill slots ever live at once).
+    The residency rule is written over a per-video COST in the arena's own unit (``_cost``: seq_len slots here; a derived
+    class whose arena is measured in bytes says so), a request may name the rectangle of the frames it needs (``_request``)
+    and the table a batch is gathered from holds whatever ``_add`` returns per frame (slots here)."""
     methods = RESIDENT_METHODS                  # what the train set must offer
+    table_dtype = torch.int32                   # of the per-frame arena rows _add returns
+    crop_key = None                             # the item entry a request's rectangle crops
 
     def __init__(self, train_set, cfg, device, backend, batch_size, drop_last, seed, num_workers, jitter):
         if not offers_resident(train_set, self.methods):
@@ -682,7 +822,7 @@ class _ResidentSet:
         self._seq_len = {}                      # video -> seq_len(i), asked once
         self._resident = {}                     # video -> True (resident) | False (spilled for good), in decision order
         self._rows = {}                         # loaded resident video -> (seq_len,) int32 arena slot of every frame, -1 missing
-        self.resident_used = 0                  # sum of seq_len over the videos decided resident
+        self.resident_used = 0                  # sum of _cost over the videos decided resident
         self.resident_frames = 0
         self.spilled_clips = 0
         self.spill_peak = 0
@@ -737,12 +877,24 @@ class _ResidentSet:
         return batches
 
     # ---- residency and loading
+    def _cost(self, video: int) -> Optional[int]:
+        """what the video would hold of the resident region, in the arena's unit; None: it can only be spilled"""
+        return self.seq_len(video)
+
+    def _request(self, entry, n: int, indices) -> tuple:
+        """the read of clip n of a plan entry: its whole video (indices None) or those frames only"""
+        return (entry[0][n], indices, None)
+
+    def _live_frames(self, base: int) -> int:
+        return self.pool.live[base]
+
     def _decide(self, video: int) -> bool:
         if video not in self._resident:
-            fits = self.resident_used + self.seq_len(video) <= self.resident_slots
+            cost = self._cost(video)
+            fits = cost is not None and self.resident_used + cost <= self.resident_slots
             self._resident[video] = fits
             if fits:
-                self.resident_used += self.seq_len(video)
+                self.resident_used += cost
         return self._resident[video]
 
     def _add(self, item) -> tuple:
@@ -754,20 +906,21 @@ class _ResidentSet:
     def epoch(self, epoch: int):
         plan = self.plan(epoch)
         requests, per_batch = [], []            # per batch: (videos that become resident now, [(clip n, distinct indices)])
-        for videos, indices, *_ in plan:
+        for entry in plan:
+            videos, indices = entry[0], entry[1]
             new, spill = [], []
             for n, v in enumerate(videos):
                 if self._decide(v):
                     if v not in self._rows:     # (a video occurs once an epoch: the order is a permutation)
-                        new.append(v)
+                        new.append(n)
                 else:
                     spill.append((n, sorted(set(indices[n].tolist()))))
-            requests += [(v, None) for v in new] + [(videos[n], ind) for n, ind in spill]
-            per_batch.append((new, spill))
+            requests += [self._request(entry, n, None) for n in new] + [self._request(entry, n, ind) for n, ind in spill]
+            per_batch.append(([videos[n] for n in new], spill))
         items = None
         if requests:                            # an epoch with nothing to read builds no loader
-            items = iter(torch.utils.data.DataLoader(_VideoRequests(self.train_set, requests), batch_size=None, shuffle=False,
-                                                     num_workers=self.num_workers))
+            items = iter(torch.utils.data.DataLoader(_VideoRequests(self.train_set, requests, self.crop_key), batch_size=None,
+                                                     shuffle=False, num_workers=self.num_workers))
         self.spilled_clips = 0
         for entry, (new, spill) in zip(plan, per_batch):
             videos, indices, jitter = entry[0], entry[1], entry[-1]
@@ -775,19 +928,19 @@ class _ResidentSet:
                 base, rows = self._add(next(items))
                 assert rows.numel() == self.seq_len(v), (v, rows.numel(), self.seq_len(v))
                 self._rows[v] = rows
-                self.resident_frames += self.pool.live[base]
-            table, bases = torch.empty_like(indices), []
+                self.resident_frames += self._live_frames(base)
+            table, bases = torch.empty(indices.shape, dtype=self.table_dtype), []
             spilled = dict(spill)
             for n, v in enumerate(videos):
                 if n in spilled:
                     base, rows = self._add(next(items))
                     bases.append(base)
                     slot = dict(zip(spilled[n], rows.tolist()))
-                    table[n] = torch.tensor([slot[k] for k in indices[n].tolist()], dtype=torch.int32)
+                    table[n] = torch.tensor([slot[k] for k in indices[n].tolist()], dtype=self.table_dtype)
                 else:
                     table[n] = self._rows[v][indices[n].long()]
             self.spilled_clips += len(bases)
-            self.spill_peak = max(self.spill_peak, sum(self.pool.live[b] for b in bases))
+            self.spill_peak = max(self.spill_peak, sum(self._live_frames(b) for b in bases))
             batch = self._batch(table, entry)
             for b in bases:                     # free for the uploads queued behind that gather on the same stream
                 self.pool.release(b)
@@ -858,13 +1011,29 @@ class ResidentGestureSet(_ResidentSet):
     frame_boxes rows of its indices, clamped as ``ChalearnGestureFrames.clip_box`` clamps it; an empty one is a ValueError
     naming the video, raised by ``plan``.
     ``epoch(e)`` yields {'clip_v2': (N, T, 7, S, S) on the device in MODEL.DTYPE, 'label': (N,), optionally 'jitter': (N, 8)},
-    S = MODEL.INPUT_SIZE, resized with MODEL.RESIZE_ANTIALIAS: what ``RoiResize`` writes from the same frames and boxes."""
+    S = MODEL.INPUT_SIZE, resized with MODEL.RESIZE_ANTIALIAS: what ``RoiResize`` writes from the same frames and boxes.
+
+    store='box' (MODEL.RESIDENT_STORE) keeps of every video only what its clips can read: the rectangle R_v = the union of
+    frame_boxes(v), clamped as ``clip_box`` clamps.  The arena is then a ``BoxArena`` of capacity_bytes (default
+    floor(MODEL.RESIDENT_GB * 2^30); capacity_frames, when given instead, counts whole frames), its last batch_size *
+    (CLIP_LEN * H*W*7 + 16) bytes the spill region; a video costs seq_len * h_R * w_R * 7 bytes rounded up to 16, decided in
+    plan order as above; a spilled clip uploads its distinct frames cropped to the clip's OWN box.  The crop is a slice in
+    the loader worker; a batch is one ``sfk_roi_resize_ragged`` launch (include/sfk_roi_ragged.h) with each clip's box
+    translated by its rectangle's origin.  Same plan, same batches bit for bit: a resize reads nothing outside its box.  A
+    video without any part box can only be spilled (and ``plan`` raises for its clips).  ``resident_bytes_used``: the arena
+    bytes the resident videos hold, under either store."""
     methods = GESTURE_METHODS
     key = "frames"                              # video_item's pool entry is pool_key(key)
 
     def __init__(self, train_set, cfg, device="cuda", backend=None, batch_size: int = 1, drop_last: bool = False, seed: int = 0,
-                 capacity_frames: Optional[int] = None, num_workers: int = 0, jitter=None, augment: bool = False):
+                 capacity_frames: Optional[int] = None, num_workers: int = 0, jitter=None, augment: bool = False,
+                 store: Optional[str] = None, capacity_bytes: Optional[int] = None):
         super().__init__(train_set, cfg, device, backend, batch_size, drop_last, seed, num_workers, jitter)
+        self.store = str(cfg.MODEL.get("RESIDENT_STORE", "frame") if store is None else store)
+        if self.store not in ("frame", "box"):
+            raise ValueError(f"ResidentGestureSet: store {self.store!r} is neither 'frame' nor 'box'")
+        if capacity_bytes is not None and self.store != "box":
+            raise ValueError("ResidentGestureSet: capacity_bytes is the 'box' store's; the 'frame' store counts capacity_frames")
         from .slowfast import _DTYPES
         self.size, self.augment = int(cfg.MODEL.INPUT_SIZE), bool(augment)
         self.out_dtype = _DTYPES[str(cfg.MODEL.get("DTYPE", "fp32")).lower()]
@@ -872,11 +1041,77 @@ class ResidentGestureSet(_ResidentSet):
         probe = train_set.video_item(0, [0])[pool_key(self.key)]
         assert probe.dtype == torch.uint8 and probe.dim() == 4 and probe.shape[0] == 1, (probe.dtype, tuple(probe.shape))
         self.frame_shape = tuple(int(v) for v in probe.shape[1:])
+        h, w, p = self.frame_shape
+        self._boxes = {}                        # video -> frame_boxes(i), asked once
+        if self.store == "box":
+            if capacity_bytes is None:
+                capacity_bytes = (int(float(cfg.MODEL.RESIDENT_GB) * 2 ** 30) if capacity_frames is None
+                                  else int(capacity_frames) * h * w * p)
+            self._make_arena(capacity_bytes)
+            return
         if capacity_frames is None:
-            h, w, p = self.frame_shape
             capacity_frames = int(float(cfg.MODEL.RESIDENT_GB) * 2 ** 30 // (h * w * p))
         self._make_pool(capacity_frames)
-        self._boxes = {}                        # video -> frame_boxes(i), asked once
+
+    # ---- store='box': the arena in bytes, a video's rectangle, its cost, its requests
+    def _make_arena(self, capacity_bytes: int) -> None:
+        """the arena of capacity_bytes: its last batch_size * (CLIP_LEN * H*W*P + 16) bytes, the worst case of whole frames,
+        are the spill region (``capacity``, ``spill_slots`` and ``resident_slots`` count bytes under this store)"""
+        h, w, p = self.frame_shape
+        self.capacity = int(capacity_bytes) // BoxArena.ALIGN * BoxArena.ALIGN
+        self.spill_slots = self.batch_size * (self.clip_len * h * w * p + BoxArena.ALIGN)
+        self.resident_slots = self.capacity - self.spill_slots
+        if self.resident_slots <= 0:
+            raise ValueError(f"ResidentGestureSet: {capacity_bytes} arena bytes leave no resident byte beside the spill region of "
+                             f"batch_size * (CLIP_LEN * H*W*{p} + {BoxArena.ALIGN}) = {self.spill_slots}")
+        self.pool = BoxArena(self.capacity, self.device, self.backend)
+        self.table_dtype, self.crop_key = torch.int64, pool_key(self.key)
+        self._rects = {}                        # video -> R_v (x1, y1, x2, y2) | None
+
+    @property
+    def resident_bytes_used(self) -> int:
+        """the arena bytes the loaded resident videos hold"""
+        h, w, p = self.frame_shape
+        if self.store != "box":
+            return self.resident_frames * h * w * p
+        return sum(self.seq_len(v) * (r[3] - r[1]) * (r[2] - r[0]) * p for v in self._rows for r in [self.video_rect(v)])
+
+    def video_rect(self, video: int) -> Optional[tuple]:
+        """R_v = (x1, y1, x2, y2): the union of the video's frame boxes, clamped to the frame as ``clip_box`` clamps; None
+        when it is empty (no frame has a part, or the union misses the frame)"""
+        if video not in self._rects:
+            b = self.frame_boxes(video)
+            h, w = self.frame_shape[:2]
+            x1, y1 = max(0, int(b[:, 0].min())), max(0, int(b[:, 1].min()))
+            x2, y2 = min(int(b[:, 2].max()), w), min(int(b[:, 3].max()), h)
+            self._rects[video] = None if x2 <= x1 or y2 <= y1 else (x1, y1, x2, y2)
+        return self._rects[video]
+
+    def _cost(self, video: int) -> Optional[int]:
+        if self.store != "box":
+            return super()._cost(video)
+        r = self.video_rect(video)
+        if r is None:
+            return None
+        nbytes = self.seq_len(video) * (r[3] - r[1]) * (r[2] - r[0]) * self.frame_shape[2]
+        return -(-nbytes // BoxArena.ALIGN) * BoxArena.ALIGN
+
+    def _request(self, entry, n: int, indices) -> tuple:
+        if self.store != "box":
+            return super()._request(entry, n, indices)
+        return (entry[0][n], indices, self.video_rect(entry[0][n]) if indices is None else tuple(entry[2][n].tolist()))
+
+    def _live_frames(self, base: int) -> int:
+        return self.pool.live[base][0] if self.store == "box" else super()._live_frames(base)
+
+    def _add(self, item) -> tuple:
+        if self.store != "box":
+            return super()._add(item)
+        windows = torch.as_tensor(item["windows"], dtype=torch.int32)
+        frames = item[pool_key(self.key)]
+        FramePool.check_windows(windows, int(frames.shape[0]))
+        base = self.pool.add(frames)
+        return base, self.pool.offsets(base, windows)[0]
 
     def frame_boxes(self, i: int) -> torch.Tensor:
         if i not in self._boxes:
@@ -904,4 +1139,11 @@ class ResidentGestureSet(_ResidentSet):
         return self.pool.add(item[pool_key(self.key)], windows)
 
     def _batch(self, table, entry) -> dict:
+        if self.store == "box":
+            # a resident video's frames lie in R_v, a spilled clip's in its own box: translate each box by that origin
+            rect = torch.tensor([self.video_rect(v) if self._resident[v] else entry[2][n].tolist() for n, v in enumerate(entry[0])],
+                                dtype=torch.int32)
+            hw = torch.stack([rect[:, 3] - rect[:, 1], rect[:, 2] - rect[:, 0]], 1)
+            box = entry[2] - torch.cat([rect[:, :2], rect[:, :2]], 1)
+            return {"clip_v2": self.pool.roi_gather(table, hw, box, self.size, self.out_dtype, self.antialias, crop=entry[3])}
         return {"clip_v2": self.pool.roi_gather(table, entry[2], self.size, self.out_dtype, self.antialias, crop=entry[3])}
