@@ -133,7 +133,8 @@ class WgradPass:
 
 @dataclass
 class StemSrc:
-    src: torch.Tensor        # any strided view indexed (n, c, t, h, w), f32 or bf16, read in place
+    src: torch.Tensor        # any strided view indexed (n, c, t, h, w), f32 or bf16, read in place (or an input_pipeline
+                             # U8Clip / PoolClip: the u8stem* / u8pstem* entry points)
     t_index: Optional[torch.Tensor]   # int32 frame indices (PackPathway) or None
     kt: int
 
@@ -202,6 +203,16 @@ class _U8Clip(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("pad", C.c_int32), ("src", C.c_void_p), ("sn", C.c_int64), ("st", C.c_int64),
                 ("sh", C.c_int64), ("sw", C.c_int64), ("c0", C.c_int32), ("c", C.c_int32), ("n", C.c_int32),
                 ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("lut", C.c_void_p), ("crop", C.c_void_p)]
+
+
+class _U8PoolClip(C.Structure):
+    """include/sfk_u8stem_pool.h sfk_u8_pool_clip: sfk_u8_clip with its frames in a frame pool -- byte (f, y, x, ch) at
+    pool[f*frame_stride + y*row_stride + x*pixel_pitch + ch], frame t of clip n is pool frame index[n][t] (outside [0, frames):
+    the constant image of byte fill); the stem reads channels c0 .. c0 + c - 1 through lut, shifted by the per-clip crop"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_int32), ("pool", C.c_void_p), ("frame_stride", C.c_int64),
+                ("row_stride", C.c_int64), ("pixel_pitch", C.c_int32), ("frames", C.c_int32), ("c0", C.c_int32), ("c", C.c_int32),
+                ("n", C.c_int32), ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("index", C.c_void_p),
+                ("lut", C.c_void_p), ("crop", C.c_void_p), ("pad", C.c_int32), ("fill", C.c_int32)]
 
 
 class _RoiDesc(C.Structure):
@@ -428,6 +439,16 @@ SIGNATURES_ROI_RAGGED = {
     "sfk_roi_ragged_abi_version": [],
     "sfk_roi_resize_ragged": [C.POINTER(_RoiRaggedDesc), _PV],
 }
+# include/sfk_u8stem_pool.h: the uint8 stems reading the frame pool through its index table (MODEL.POOL_STEM), same library, its
+# own header and version
+U8STEM_POOL_ABI_VERSION = 1   # include/sfk_u8stem_pool.h SFK_U8STEM_POOL_ABI_VERSION
+SIGNATURES_U8STEM_POOL = {
+    "sfk_u8stem_pool_abi_version": [],
+    "sfk_u8pstem_conv_fwd": [C.POINTER(_U8PoolClip), _PV, _I32, _I32, _PV, _P_FMAP, _PF, _PV],
+    "sfk_u8pstem_conv_wgrad": [C.POINTER(_U8PoolClip), _PV, _I32, _I32, _P_FMAP, _PF, _PV],
+    "sfk_u8pstem2d_fwd": [C.POINTER(_U8PoolClip), _PV, _P_FMAP, _PF, _PV],
+    "sfk_u8pstem2d_wgrad": [C.POINTER(_U8PoolClip), _P_FMAP, _PF, _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
@@ -454,6 +475,12 @@ def new_stem2d_src() -> "_Stem2dSrc":
 def new_u8_clip() -> "_U8Clip":
     d = _U8Clip()
     d.struct_size = C.sizeof(_U8Clip)
+    return d
+
+
+def new_u8_pool_clip() -> "_U8PoolClip":
+    d = _U8PoolClip()
+    d.struct_size = C.sizeof(_U8PoolClip)
     return d
 
 
@@ -517,7 +544,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
                        "(there is no CPU or PyTorch fallback for the SlowFast path)")
     lib = C.CDLL(path)
     for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL,
-                  SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL, SIGNATURES_ROI_RAGGED):
+                  SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL, SIGNATURES_ROI_RAGGED, SIGNATURES_U8STEM_POOL):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -542,6 +569,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk roi_pool ABI version mismatch: library {lib.sfk_roi_pool_abi_version()}, binding {ROI_POOL_ABI_VERSION}")
     if lib.sfk_roi_ragged_abi_version() != ROI_RAGGED_ABI_VERSION:
         raise SfkError(f"libsfk roi_ragged ABI version mismatch: library {lib.sfk_roi_ragged_abi_version()}, binding {ROI_RAGGED_ABI_VERSION}")
+    if lib.sfk_u8stem_pool_abi_version() != U8STEM_POOL_ABI_VERSION:
+        raise SfkError(f"libsfk u8stem_pool ABI version mismatch: library {lib.sfk_u8stem_pool_abi_version()}, binding {U8STEM_POOL_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -775,8 +804,8 @@ class HipBackend:
         return d
 
     def u8stem_tiles(self, p: StemSrc, y: FMap) -> int:
-        """the BatchNorm partial-sum rows of either u8 stem: sfk_stem_conv_tiles' count, which depends on the output map only
-        (for the one-frame output of the 2-D stem it equals sfk_stem2d_tiles')"""
+        """the BatchNorm partial-sum rows of either u8 stem, over a U8Clip or a PoolClip alike: sfk_stem_conv_tiles' count,
+        which depends on the output map only (for the one-frame output of the 2-D stem it equals sfk_stem2d_tiles')"""
         d, fy = _StemSrc(), _c_fmap(y)
         r = self.lib.sfk_stem_conv_tiles(C.byref(d), C.byref(fy))
         if r < 0:
@@ -802,6 +831,42 @@ class HipBackend:
         assert p.t_index is None
         d, fy = self._c_u8clip(p), _c_fmap(dy)
         return self._plain("sfk_u8stem2d_wgrad", C.byref(d), C.byref(fy), _ptr(dw), keep=(d, fy, p, dy, dw))
+
+    # -- the uint8 stems reading the frame pool (include/sfk_u8stem_pool.h); `src` of the StemSrc is an input_pipeline.PoolClip
+    #    (the BatchNorm partial-sum rows: u8stem_tiles, which reads the output map only)
+    @staticmethod
+    def _c_u8poolclip(p: StemSrc) -> _U8PoolClip:
+        x = p.src
+        a, idx = x.arena, x.index
+        assert a.dtype == torch.uint8 and a.dim() == 4 and a.stride(3) == 1
+        assert idx.dtype == torch.int32 and idx.dim() == 2 and idx.is_contiguous()
+        d = new_u8_pool_clip()
+        d.pool, d.index, d.lut, d.crop = a.data_ptr(), idx.data_ptr(), x.lut.data_ptr(), _ptr(x.crop)
+        d.frame_stride, d.row_stride, d.pixel_pitch = a.stride()[:3]
+        d.frames, d.h, d.w = a.shape[:3]
+        d.n, d.t = idx.shape
+        d.c0, d.c, d.pad, d.fill = x.c0, x.c, x.pad, x.fill
+        return d
+
+    def u8pstem_conv_fwd(self, p: StemSrc, w: torch.Tensor, y: FMap, stats: Optional[torch.Tensor]):
+        d, fy = self._c_u8poolclip(p), _c_fmap(y)
+        return self._plain("sfk_u8pstem_conv_fwd", C.byref(d), _ptr(p.t_index), p.t_len, p.kt, _ptr(w), C.byref(fy),
+                           _ptr(stats), keep=(d, fy, p, w, y, stats))
+
+    def u8pstem_conv_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
+        d, fy = self._c_u8poolclip(p), _c_fmap(dy)
+        return self._plain("sfk_u8pstem_conv_wgrad", C.byref(d), _ptr(p.t_index), p.t_len, p.kt, C.byref(fy), _ptr(dw),
+                           keep=(d, fy, p, dy, dw))
+
+    def u8pstem2d_fwd(self, p: StemSrc, w: torch.Tensor, y: FMap, stats: Optional[torch.Tensor]):
+        assert p.t_index is None
+        d, fy = self._c_u8poolclip(p), _c_fmap(y)
+        return self._plain("sfk_u8pstem2d_fwd", C.byref(d), _ptr(w), C.byref(fy), _ptr(stats), keep=(d, fy, p, w, y, stats))
+
+    def u8pstem2d_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
+        assert p.t_index is None
+        d, fy = self._c_u8poolclip(p), _c_fmap(dy)
+        return self._plain("sfk_u8pstem2d_wgrad", C.byref(d), C.byref(fy), _ptr(dw), keep=(d, fy, p, dy, dw))
 
     # -- generic plain-argument entry points
     def _plain(self, name, *args, keep=()):

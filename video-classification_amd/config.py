@@ -100,6 +100,7 @@ _C.MODEL.DEPTH = 50            # the reference hard-codes 50 (model/my_slowfast.
 _C.MODEL.RES2D_BACKEND = 'torch'  # MODEL.NAME res2d: 'torch' (res2d.py, PyTorch kernels, fp32) | 'engine' (libsfk, MODEL.DTYPE)
 _C.MODEL.PARTS = 'lHandArmTorso'  # gesture_v2 (new_feature_test.py:812): the PartCompose composition whose box each clip crops
 _C.MODEL.RESIZE_ANTIALIAS = True  # gesture_v2: antialiased resize of the crop (torchvision >= 0.17 tensor Resize) or not (older)
+_C.MODEL.POOL_STEM = False     # pooled routes (RESIDENT_TRAIN batches, pooled run_eval): the uint8 stems read the frame pool through its index table (True, include/sfk_u8stem_pool.h) or the gather writes the float clip first (False); it acts only on pooled routes that are in use -- without RESIDENT_TRAIN and without pooled test items it changes nothing
 _C.MODEL.U8_STEM = False       # uint8 batches (<R3D_INPUT>_u8): the engine's stems read the frames (True) or DevicePreprocess writes the float clip first (False)
 _C.MODEL.COLOR_JITTER = False  # train items carry the draws of torchvision's ColorJitter; applied on the device (include/sfk_aug.h)
 _C.MODEL.JITTER_BRIGHTNESS = 0.5   # dataset/chalearn_dataset.py:49: ColorJitter(brightness=0.5, hue=0.1, contrast=0.3, saturation=0.2)

@@ -5,6 +5,7 @@
 
 #include "sfk.h"
 #include "sfk_u8stem.h"
+#include "sfk_u8stem_pool.h"
 
 // the process-wide tuning table of sfk_init (optim_misc.hip); read-only after the first launch
 __attribute__((visibility("hidden"))) const sfk_tuning& sfk_tune();
@@ -117,9 +118,30 @@ template <> inline constexpr bool sfk_is_u8<U8Lut> = true;
 template <int CIN> inline constexpr bool sfk_is_u8<U8Pix<CIN>> = true;
 template <typename S> inline constexpr int sfk_u8_pix = 0;
 template <int CIN> inline constexpr int sfk_u8_pix<U8Pix<CIN>> = CIN;
+// The same two sources with their frames in a frame pool (include/sfk_u8stem_pool.h): frame t of clip n is pool frame
+// index[n][t], or the constant image of byte fill when that index is outside the pool.  The pool is a compile-time property
+// of the tag, so the stacked-frame and float instantiations carry none of it.
+struct U8PoolLut {};
+template <int CIN> struct U8PoolPix {};
+template <> inline constexpr bool sfk_is_u8<U8PoolLut> = true;
+template <int CIN> inline constexpr bool sfk_is_u8<U8PoolPix<CIN>> = true;
+template <int CIN> inline constexpr int sfk_u8_pix<U8PoolPix<CIN>> = CIN;
+template <typename S> inline constexpr bool sfk_is_pool = false;
+template <> inline constexpr bool sfk_is_pool<U8PoolLut> = true;
+template <int CIN> inline constexpr bool sfk_is_pool<U8PoolPix<CIN>> = true;
+// plane_base's two negative states: a plane that is padding (all zeros), and a plane of a MISSING pool frame (lut[fill]
+// wherever the slot is inside the conv input and inside the crop)
+constexpr int64_t SFK_PLANE_PAD = -1;
+constexpr int64_t SFK_PLANE_MISSING = -2;
 // the host checks shared by the 3-D and 2-D uint8 stem entry points (SFK_ERR_INVALID when false)
 static inline bool sfk_u8_clip_ok(const sfk_u8_clip* x) {
   return x && x->struct_size == sizeof(sfk_u8_clip) && x->src && x->lut && x->pad >= 0 && x->c0 >= 0 && x->c > 0 &&
          x->n > 0 && x->t > 0 && x->h > 0 && x->w > 0 && x->sn >= 0 && x->st >= 0 && x->sh >= 0 &&
          (int64_t)x->c0 + x->c <= x->sw;
+}
+// ... and by the pooled ones (include/sfk_u8stem_pool.h): sfk_u8_clip_ok's and sfk_u8_pool_gather_crop's, together
+static inline bool sfk_u8_pool_clip_ok(const sfk_u8_pool_clip* x) {
+  return x && x->struct_size == sizeof(sfk_u8_pool_clip) && x->pool && x->index && x->lut && x->pad >= 0 && x->c0 >= 0 &&
+         x->c > 0 && x->n > 0 && x->t > 0 && x->h > 0 && x->w > 0 && x->frames > 0 && x->frame_stride >= 0 &&
+         x->row_stride >= 0 && (int64_t)x->c0 + x->c <= x->pixel_pitch && x->fill >= 0 && x->fill <= 255;
 }

@@ -47,6 +47,9 @@ struct S2K {
   const float* lut;               // S = U8Lut: value of each source byte (sc = 1: channel c at byte c)
   const int32_t* crop;            // S = U8Lut: [n][2] (top, left) or null; the frame pixel of (hi, wi) is (hi + top - pad, wi + left - pad)
   int pad;
+  const int32_t* pindex;          // pooled S (include/sfk_u8stem_pool.h): [n][t] pool frame of (clip, frame); src is the pool, sn = 0
+  int pframes;                    // pooled S: frames in the pool; an index outside [0, pframes) names a missing frame
+  int pfill;                      // pooled S: the byte every pixel of a missing frame has
 };
 
 template <typename S> __device__ __forceinline__ float ldsrc(const void* p, int64_t off);
@@ -86,12 +89,21 @@ struct PatchSlots {
   }
 };
 
-// source offset of input plane pl = t*C + c of clip n; -1 past the last plane
+// source offset of input plane pl = t*C + c of clip n; SFK_PLANE_PAD (-1) past the last plane.  Pooled S: frame t goes
+// through the pool's index table (one lookup per plane, wave-uniform), and a frame that is not in the pool is the third
+// state, SFK_PLANE_MISSING.
+template <typename S = float>
 __device__ __forceinline__ int64_t plane_base(const S2K& k, int pl, int n) {
-  if (pl >= k.planes) return -1;
+  if (pl >= k.planes) return SFK_PLANE_PAD;
   uint32_t t, c;
   k.dc.divmod((uint32_t)pl, t, c);
-  return (int64_t)n * k.sn + (int64_t)t * k.st + (int64_t)c * k.sc;
+  if constexpr (sfk_is_pool<S>) {
+    const int slot = k.pindex[(int64_t)n * k.t + (int)t];
+    if ((unsigned)slot >= (unsigned)k.pframes) return SFK_PLANE_MISSING;
+    return (int64_t)slot * k.st + (int64_t)c * k.sc;
+  } else {
+    return (int64_t)n * k.sn + (int64_t)t * k.st + (int64_t)c * k.sc;
+  }
 }
 
 // lut: S = U8Lut, the block's LDS copy of the table (one gather per element from LDS instead of a second global round trip)
@@ -100,12 +112,19 @@ __device__ __forceinline__ void plane_fetch(const S2K& k, const PatchSlots& ps, 
                                             const float* lut = nullptr) {
   const bool bok = base >= 0;              // branch-free: padding slots read the plane's first element, zeroed by a select
   const int64_t b = bok ? base : 0;
+  // pooled S: a missing frame's slots load a byte of pool frame 0 like padding does, and a select puts the fill byte in its
+  // place in front of the table lookup -- lut[fill] wherever the slot is inside the conv input and the crop
+  const bool miss = sfk_is_pool<S> && base == SFK_PLANE_MISSING;
+  const bool live = sfk_is_pool<S> ? (bok || miss) : bok;
 #pragma unroll
   for (int i = 0; i < NSLOT; ++i) {
     float x;
-    if constexpr (sfk_is_u8<S>) x = lut[static_cast<const uint8_t*>(k.src)[b + ps.off[i]]];   // the table's f32, as the float clip holds it
+    if constexpr (sfk_is_pool<S>) {
+      const uint32_t u = static_cast<const uint8_t*>(k.src)[b + ps.off[i]];
+      x = lut[miss ? (uint32_t)k.pfill : u];
+    } else if constexpr (sfk_is_u8<S>) x = lut[static_cast<const uint8_t*>(k.src)[b + ps.off[i]]];   // the table's f32, as the float clip holds it
     else x = ldsrc<S>(k.src, b + ps.off[i]);
-    v[i] = (bok && ps.ok[i]) ? x : 0.f;
+    v[i] = (live && ps.ok[i]) ? x : 0.f;
   }
 }
 
@@ -201,7 +220,7 @@ __global__ __launch_bounds__(256) void stem2d_fwd_kernel(const S2K k) {
   auto fetch = [&](int c) {
     int64_t base[CP];
 #pragma unroll
-    for (int q = 0; q < CP; ++q) base[q] = plane_base(k, c * CP + q, n);
+    for (int q = 0; q < CP; ++q) base[q] = plane_base<S>(k, c * CP + q, n);
 #pragma unroll
     for (int q = 0; q < CP; ++q) plane_fetch<S>(k, ps, base[q], pv[q], lut);
 #pragma unroll
@@ -338,7 +357,7 @@ __global__ __launch_bounds__(256) void stem2d_wgrad_kernel(const S2K k) {
     tile_coords(k, tile, n, ho0, wo0);
     ps.set_tile<S>(k, n, ho0, wo0);
     float v[NSLOT];
-    plane_fetch<S>(k, ps, plane_base(k, pl, n), v, lut);
+    plane_fetch<S>(k, ps, plane_base<S>(k, pl, n), v, lut);
     // dY of pixel tid of the tile (zero outside the map and for co >= cout)
     const int ho = ho0 + (tid >> 4), wo = wo0 + (tid & 15);
     const bool pok = ho < k.ho && wo < k.wo;
@@ -433,6 +452,22 @@ int fill_u8(const sfk_u8_clip* x, const sfk_fmap* y, S2K& k) {
   return SFK_OK;
 }
 
+// ... and of an sfk_u8_pool_clip: the pool is the source, the clip stride is unused (plane_base goes through the index table)
+int fill_u8p(const sfk_u8_pool_clip* x, const sfk_fmap* y, S2K& k) {
+  if (!sfk_u8_pool_clip_ok(x)) return SFK_ERR_INVALID;
+  sfk_stem2d_src s{};
+  s.struct_size = sizeof(sfk_stem2d_src);
+  s.src_dtype = SFK_F32;          // (fill's element-type check only, as in fill_u8)
+  s.src = x->pool + x->c0;
+  s.sn = 0; s.st = x->frame_stride; s.sc = 1; s.sh = x->row_stride; s.sw = x->pixel_pitch;
+  s.n = x->n; s.t = x->t; s.c = x->c; s.h_in = x->h; s.w_in = x->w;
+  const int st = fill(&s, y, k);
+  if (st != SFK_OK) return st;
+  k.lut = x->lut; k.crop = x->crop; k.pad = x->pad;
+  k.pindex = x->index; k.pframes = x->frames; k.pfill = x->fill;
+  return SFK_OK;
+}
+
 template <typename S>
 int launch_fwd(const S2K& k, const sfk_fmap* y, hipStream_t hs) {
   const dim3 grid((unsigned)k.ntiles), block(256);
@@ -516,4 +551,25 @@ extern "C" int sfk_u8stem2d_wgrad(const sfk_u8_clip* x, const sfk_fmap* dy, floa
   if (!dw) return SFK_ERR_INVALID;
   k.dw = dw;
   return launch_wgrad<U8Lut>(k, dy, static_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------------------------------------------ uint8 frames in a frame pool (sfk_u8stem_pool.h)
+extern "C" int sfk_u8pstem2d_fwd(const sfk_u8_pool_clip* x, const void* w, const sfk_fmap* y, float* stats, sfk_stream_t stream) {
+  S2K k;
+  const int st = fill_u8p(x, y, k);
+  if (st != SFK_OK) return st;
+  if (!w) return SFK_ERR_INVALID;
+  if ((((uintptr_t)w) & 15) != 0) return SFK_ERR_UNSUPPORTED;
+  k.w = w;
+  k.stats = stats;
+  return launch_fwd<U8PoolLut>(k, y, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int sfk_u8pstem2d_wgrad(const sfk_u8_pool_clip* x, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
+  S2K k;
+  const int st = fill_u8p(x, dy, k);
+  if (st != SFK_OK) return st;
+  if (!dw) return SFK_ERR_INVALID;
+  k.dw = dw;
+  return launch_wgrad<U8PoolLut>(k, dy, static_cast<hipStream_t>(stream));
 }

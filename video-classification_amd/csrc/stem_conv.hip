@@ -43,6 +43,9 @@ struct StemK {
   const float* lut;               // S = U8Lut: value of each source byte (sc = 1: channel c at byte c)
   const int32_t* crop;            // S = U8Lut: [n][2] (top, left) or null; the frame pixel of (hi, wi) is (hi + top - pad, wi + left - pad)
   int pad;
+  const int32_t* pindex;          // pooled S (include/sfk_u8stem_pool.h): [n][t_in] pool frame of (clip, frame); src is the pool, sn = 0
+  int pframes;                    // pooled S: frames in the pool; an index outside [0, pframes) names a missing frame
+  int pfill;                      // pooled S: the byte every pixel of a missing frame has
 };
 
 template <typename S> __device__ __forceinline__ float ldsrc(const void* p, int64_t off);
@@ -87,15 +90,24 @@ struct PatchSlots {
   }
 };
 
-// source base offset of plane pl for output frame `to` of clip n; <0 when the frame is temporal padding
+// source base offset of plane pl for output frame `to` of clip n; SFK_PLANE_PAD (-1) when the frame is temporal padding.
+// Pooled S: the selected frame goes through the pool's index table (one lookup per plane, wave-uniform), and a frame
+// that is not in the pool is the third state, SFK_PLANE_MISSING.
+template <typename S = float>
 __device__ __forceinline__ int64_t plane_base(const StemK& k, int pl, int n, int to) {
   uint32_t f, ci;
   k.dcin.divmod((uint32_t)pl, f, ci);
   const int tt = to + (int)f - k.pt;
   int frame = -1;
   if (tt >= 0 && tt < k.t_log) frame = k.t_index ? k.t_index[tt] : tt;
-  if (frame < 0 || frame >= k.t_in) return -1;
-  return (int64_t)n * k.sn + (int64_t)ci * k.sc + (int64_t)frame * k.st;
+  if (frame < 0 || frame >= k.t_in) return SFK_PLANE_PAD;
+  if constexpr (sfk_is_pool<S>) {
+    const int slot = k.pindex[(int64_t)n * k.t_in + frame];
+    if ((unsigned)slot >= (unsigned)k.pframes) return SFK_PLANE_MISSING;
+    return (int64_t)ci * k.sc + (int64_t)slot * k.st;
+  } else {
+    return (int64_t)n * k.sn + (int64_t)ci * k.sc + (int64_t)frame * k.st;
+  }
 }
 
 // lut: S = U8Lut, the block's LDS copy of the table (one gather per element from LDS instead of a second global round trip)
@@ -106,13 +118,20 @@ __device__ __forceinline__ void plane_fetch(const StemK& k, const PatchSlots& ps
   // hipcc drain vmcnt behind it -- NSLOT serial round trips per plane instead of one)
   const bool bok = base >= 0;
   const int64_t b = bok ? base : 0;
+  // pooled S: a missing frame's slots load a byte of pool frame 0 like padding does, and a select puts the fill byte in its
+  // place in front of the table lookup -- lut[fill] wherever the slot is inside the conv input and the crop
+  const bool miss = sfk_is_pool<S> && base == SFK_PLANE_MISSING;
+  const bool live = sfk_is_pool<S> ? (bok || miss) : bok;
 #pragma unroll
   for (int i = 0; i < NSLOT; ++i) {
     const int64_t o = b + (ps.ok[i] ? ps.off[i] : 0);
     float x;
-    if constexpr (sfk_is_u8<S>) x = lut[static_cast<const uint8_t*>(k.src)[o]];   // the table's f32, as the float clip holds it
+    if constexpr (sfk_is_pool<S>) {
+      const uint32_t u = static_cast<const uint8_t*>(k.src)[o];
+      x = lut[miss ? (uint32_t)k.pfill : u];
+    } else if constexpr (sfk_is_u8<S>) x = lut[static_cast<const uint8_t*>(k.src)[o]];   // the table's f32, as the float clip holds it
     else x = ldsrc<S>(k.src, o);
-    v[i] = (bok && ps.ok[i]) ? x : 0.f;
+    v[i] = (live && ps.ok[i]) ? x : 0.f;
   }
 }
 
@@ -130,14 +149,17 @@ __device__ __forceinline__ void plane_store(T* patch, const float (&v)[NSLOT]) {
 // the same lines again; instead each lane loads the aligned dwords that hold its pixel's CIN bytes once per frame tap and
 // spreads them over the CIN planes (v_alignbyte per 4 channels, the table lookup in LDS).  Masked slots read the pixel at the
 // plane's origin; an aligned dword that holds a byte of the frames never leaves their allocation's pages.
-template <typename T, int CIN>
+template <typename T, typename S>
 __device__ __forceinline__ void stage_u8_pixels(const StemK& k, const PatchSlots& ps, int n, int to, T* patch,
                                                 const float* lut) {
+  constexpr int CIN = sfk_u8_pix<S>;
   constexpr int NQ = (CIN + 3) / 4, NW = NQ + 1;
   const uint8_t* src = static_cast<const uint8_t*>(k.src);
   for (int f = 0; f < k.kt; ++f) {
-    const int64_t base = plane_base(k, f * CIN, n, to);        // channel 0 of frame tap f; < 0: temporal padding
+    const int64_t base = plane_base<S>(k, f * CIN, n, to);     // channel 0 of frame tap f; < 0: temporal padding / missing
     const bool bok = base >= 0;
+    const bool miss = sfk_is_pool<S> && base == SFK_PLANE_MISSING;   // (see plane_fetch)
+    const bool live = sfk_is_pool<S> ? (bok || miss) : bok;
     uint32_t w[NSLOT][NW], sh[NSLOT];
 #pragma unroll
     for (int i = 0; i < NSLOT; ++i) {                            // all loads first (branch-free, see plane_fetch)
@@ -152,10 +174,11 @@ __device__ __forceinline__ void stage_u8_pixels(const StemK& k, const PatchSlots
     for (int i = 0; i < NSLOT; ++i) {
       const int e = threadIdx.x + 256 * i;
       if (e >= PR * PC) continue;
-      const bool ok = bok && ps.ok[i];
+      const bool ok = live && ps.ok[i];
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
-        const uint32_t v = __builtin_amdgcn_alignbyte(w[i][q + 1], w[i][q], sh[i]);   // bytes 4q .. 4q+3 of the pixel
+        uint32_t v = __builtin_amdgcn_alignbyte(w[i][q + 1], w[i][q], sh[i]);   // bytes 4q .. 4q+3 of the pixel
+        if constexpr (sfk_is_pool<S>) v = miss ? (uint32_t)k.pfill * 0x01010101u : v;
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
           if (4 * q + b < CIN) patch[(f * CIN + 4 * q + b) * PR * PC + e] = (T)(ok ? lut[(v >> (8 * b)) & 255u] : 0.f);
@@ -250,13 +273,13 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemK k) {
     __syncthreads();                                          // previous tile's patch / red reads are done
     int pl = 0;
     if constexpr (sfk_u8_pix<S> > 0) {
-      stage_u8_pixels<T, sfk_u8_pix<S>>(k, ps, n, to, patch, lut);
+      stage_u8_pixels<T, S>(k, ps, n, to, patch, lut);
       pl = k.planes;
     }
     for (; pl + 3 <= k.planes; pl += 3) {                     // 18 loads in flight per thread
       float v0[NSLOT], v1[NSLOT], v2[NSLOT];
       // the three frame lookups first (one wait), then all 18 element loads back to back
-      const int64_t b0 = plane_base(k, pl, n, to), b1 = plane_base(k, pl + 1, n, to), b2 = plane_base(k, pl + 2, n, to);
+      const int64_t b0 = plane_base<S>(k, pl, n, to), b1 = plane_base<S>(k, pl + 1, n, to), b2 = plane_base<S>(k, pl + 2, n, to);
       plane_fetch<S>(k, ps, b0, v0, lut);
       plane_fetch<S>(k, ps, b1, v1, lut);
       plane_fetch<S>(k, ps, b2, v2, lut);
@@ -266,7 +289,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const StemK k) {
     }
     for (; pl < k.planes; ++pl) {
       float v0[NSLOT];
-      plane_fetch<S>(k, ps, plane_base(k, pl, n, to), v0, lut);
+      plane_fetch<S>(k, ps, plane_base<S>(k, pl, n, to), v0, lut);
       plane_store<T>(patch + pl * PR * PC, v0);
     }
     __syncthreads();
@@ -393,7 +416,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemK k) {
     int n, to, ho0, wo0;
     tile_coords(k, tile, n, to, ho0, wo0);
     ps.set_tile<S>(k, n, ho0, wo0);
-    plane_fetch<S>(k, ps, plane_base(k, pl, n, to), pv, lut);
+    plane_fetch<S>(k, ps, plane_base<S>(k, pl, n, to), pv, lut);
 #pragma unroll
     for (int i = 0; i < NDL; ++i) {
       const int e = tid + 256 * i;
@@ -1301,6 +1324,7 @@ int fill(const sfk_stem_src* s, int cout, int t_out, int ho, int wo, StemK& k) {
   k.tiles_h = (ho + TS - 1) / TS; k.tiles_w = (wo + TS - 1) / TS;
   k.dtw.set(k.tiles_w); k.dth.set(k.tiles_h); k.dt.set(t_out); k.d7.set(KH); k.dcin.set(s->cin); k.dpc.set(PC);
   k.lut = nullptr; k.crop = nullptr; k.pad = 0;
+  k.pindex = nullptr; k.pframes = 0; k.pfill = 0;
   return SFK_OK;
 }
 
@@ -1317,6 +1341,23 @@ int fill_u8(const sfk_u8_clip* x, const int32_t* t_index, int32_t t_len, int32_t
   const int st = fill(&s, cout, t_out, ho, wo, k);
   if (st != SFK_OK) return st;
   k.lut = x->lut; k.crop = x->crop; k.pad = x->pad;
+  return SFK_OK;
+}
+
+// ... and of an sfk_u8_pool_clip: the pool is the source, the clip stride is unused (plane_base goes through the index table)
+int fill_u8p(const sfk_u8_pool_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt, int n, int cout, int t_out, int ho,
+             int wo, StemK& k) {
+  if (!sfk_u8_pool_clip_ok(x) || x->n != n) return SFK_ERR_INVALID;
+  sfk_stem_src s{};
+  s.src = x->pool + x->c0;
+  s.src_dtype = SFK_F32;          // (fill's element-type check only, as in fill_u8)
+  s.sn = 0; s.sc = 1; s.st = x->frame_stride; s.sh = x->row_stride; s.sw = x->pixel_pitch;
+  s.cin = x->c; s.t_in = x->t; s.h_in = x->h; s.w_in = x->w;
+  s.t_index = t_index; s.t_len = t_len; s.kt = kt;
+  const int st = fill(&s, cout, t_out, ho, wo, k);
+  if (st != SFK_OK) return st;
+  k.lut = x->lut; k.crop = x->crop; k.pad = x->pad;
+  k.pindex = x->index; k.pframes = x->frames; k.pfill = x->fill;
   return SFK_OK;
 }
 
@@ -1507,4 +1548,34 @@ extern "C" int sfk_u8stem_conv_wgrad(const sfk_u8_clip* x, const int32_t* t_inde
   k.w = nullptr; k.y = dy->ptr; k.yld = dy->ld; k.yoff = dy->c_off; k.stats = nullptr; k.dw = dw;
   k.ntiles = dy->n * dy->t * k.tiles_h * k.tiles_w;
   return stem_wgrad_generic<U8Lut>(k, dy, static_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------------------------------------------ uint8 frames in a frame pool (sfk_u8stem_pool.h)
+extern "C" int sfk_u8stem_pool_abi_version(void) { return SFK_U8STEM_POOL_ABI_VERSION; }
+
+extern "C" int sfk_u8pstem_conv_fwd(const sfk_u8_pool_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt, const void* w,
+                                    const sfk_fmap* y, float* stats, sfk_stream_t stream) {
+  if (!w || !sfk_fmap_ok(y)) return SFK_ERR_INVALID;
+  StemK k;
+  const int st = fill_u8p(x, t_index, t_len, kt, y->n, y->c, y->t, y->h, y->w, k);
+  if (st != SFK_OK) return st;
+  if ((y->ld % 4) || (y->c_off % 4) || (((uintptr_t)y->ptr) & 15) || (((uintptr_t)w) & 15)) return SFK_ERR_UNSUPPORTED;
+  k.w = w; k.y = y->ptr; k.yld = y->ld; k.yoff = y->c_off; k.stats = stats; k.dw = nullptr;
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  // whole pixels for the reference geometries' channel counts, as sfk_u8stem_conv_fwd
+  if (x->c == 5) return stem_fwd_generic<U8PoolPix<5>>(k, y, hs);
+  if (x->c == 15) return stem_fwd_generic<U8PoolPix<15>>(k, y, hs);
+  return stem_fwd_generic<U8PoolLut>(k, y, hs);
+}
+
+extern "C" int sfk_u8pstem_conv_wgrad(const sfk_u8_pool_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt,
+                                      const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
+  if (!dw || !sfk_fmap_ok(dy)) return SFK_ERR_INVALID;
+  StemK k;
+  const int st = fill_u8p(x, t_index, t_len, kt, dy->n, dy->c, dy->t, dy->h, dy->w, k);
+  if (st != SFK_OK) return st;
+  if (!sfk_fmap_vec_ok(dy)) return SFK_ERR_UNSUPPORTED;
+  k.w = nullptr; k.y = dy->ptr; k.yld = dy->ld; k.yoff = dy->c_off; k.stats = nullptr; k.dw = dw;
+  k.ntiles = dy->n * dy->t * k.tiles_h * k.tiles_w;
+  return stem_wgrad_generic<U8PoolLut>(k, dy, static_cast<hipStream_t>(stream));
 }

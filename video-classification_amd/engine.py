@@ -23,7 +23,7 @@ import torch
 
 from . import arch
 from ._lib import BN_FOLD_ROWS, BnBwdFuse, ConvEpilogue, ConvPass, FMap, StemSrc, WgradPass, stem_kp
-from .input_pipeline import U8Clip
+from .input_pipeline import STEM_CLIPS, PoolClip, U8Clip
 from .plan import ConvGeom, dgrad_passes, fwd_pass, round_up, wgrad_taps
 
 Run = Callable[[int], None]
@@ -629,8 +629,10 @@ class Engine:
         esz = 2 if self.dtype == torch.bfloat16 else 4
         flops = 2.0 * st["y"].pixels * L.c * L.cb.geom.cin * L.cb.geom.wtaps
         f2d = self.spec.frames_as_channels               # res2d: Conv2d over the T*C stacked planes (include/sfk_stem2d.h)
-        u8 = isinstance(x5, U8Clip)                      # the stem reads the uint8 frames itself (include/sfk_u8stem.h)
-        if u8:
+        if isinstance(x5, PoolClip):                     # the stem reads the frame pool through its index table (include/sfk_u8stem_pool.h)
+            fwd_fn, wgrad_fn = ((self.be.u8pstem2d_fwd, self.be.u8pstem2d_wgrad) if f2d else
+                                (self.be.u8pstem_conv_fwd, self.be.u8pstem_conv_wgrad))
+        elif isinstance(x5, U8Clip):                     # the stem reads the uint8 frames itself (include/sfk_u8stem.h)
             fwd_fn, wgrad_fn = ((self.be.u8stem2d_fwd, self.be.u8stem2d_wgrad) if f2d else
                                 (self.be.u8stem_conv_fwd, self.be.u8stem_conv_wgrad))
         else:
@@ -677,7 +679,7 @@ class Engine:
         pl.stem_state[p] = st
         rec = None
         if train:
-            if isinstance(x5, U8Clip):
+            if isinstance(x5, STEM_CLIPS):
                 tiles = self.be.u8stem_tiles
             else:
                 tiles = self.be.stem2d_tiles if self.spec.frames_as_channels else self.be.stem_conv_tiles
@@ -1197,14 +1199,16 @@ class Engine:
         """Plans are keyed on geometry (shapes, strides, dtypes); only the two im2col ops hold the input
         addresses, so a new batch tensor re-binds those two ops instead of rebuilding ~1000 descriptors.
         A U8Clip (the stems read uint8 frames) is keyed on its frames' geometry, its channel range and whether it has a
-        crop, so it never shares a plan with a float clip; its frames, crop and table are the addresses bound."""
+        crop, so it never shares a plan with a float clip; its frames, crop and table are the addresses bound.  A PoolClip
+        likewise (arena geometry, table shape, channel range, crop or not): its arena and its two tables are bound, and those
+        stay where they are from batch to batch of a fixed-capacity pool, so nothing is re-bound."""
         def geo(t):
-            if isinstance(t, U8Clip):
+            if isinstance(t, STEM_CLIPS):
                 return t.geometry_key()
             return None if t is None else (tuple(t.shape), tuple(t.stride()), t.dtype)
 
         def ptrs():
-            return tuple(None if t is None else (t.bound_ptrs() if isinstance(t, U8Clip) else t.data_ptr())
+            return tuple(None if t is None else (t.bound_ptrs() if isinstance(t, STEM_CLIPS) else t.data_ptr())
                          for t in (x_slow, x_fast, slow_t_index))
         key = (geo(x_slow), geo(x_fast), geo(slow_t_index), train)
         pl = self._plans.get(key)
@@ -1276,8 +1280,8 @@ class Engine:
     def input_view(self, x: torch.Tensor) -> torch.Tensor:
         """The frames-as-channels stem (res2d) reads its clip as an (N, C, T, H, W) view; this makes that view, without a
         copy, from the reference's (N, T*C, H, W) tensor (channel t*C + c, any strides) or the loader's (N, T, >=C, H, W)
-        memory.  Every other network, and a U8Clip (already the logical (N, C, T, H, W) clip): x as it is."""
-        if not self.spec.frames_as_channels or isinstance(x, U8Clip):
+        memory.  Every other network, and a U8Clip or PoolClip (already the logical (N, C, T, H, W) clip): x as it is."""
+        if not self.spec.frames_as_channels or isinstance(x, STEM_CLIPS):
             return x
         c, t = self.spec.input_channels[0], self.spec.stem_kernels[0][0]
         if x.dim() == 4:
@@ -1291,7 +1295,7 @@ class Engine:
 
     def forward(self, x_slow: torch.Tensor, x_fast: torch.Tensor, train: bool, slow_t_index=None) -> Plan:
         """x_*: (N, C, T, H, W) views with ANY strides (the dataset's N,T,C,H,W memory is read in place), or U8Clips
-        (the stems read the uint8 frames, input_pipeline.U8Clip).  If slow_t_index is given, the slow pathway reads frames x_slow[:, :, slow_t_index] (PackPathway)."""
+        (the stems read the uint8 frames, input_pipeline.U8Clip / PoolClip).  If slow_t_index is given, the slow pathway reads frames x_slow[:, :, slow_t_index] (PackPathway)."""
         assert x_slow.dim() == 5 and x_slow.shape[1] == self.spec.input_channels[0]
         if self.spec.pathways == 2:
             assert x_fast.dim() == 5 and x_slow.shape[0] == x_fast.shape[0]

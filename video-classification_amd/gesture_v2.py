@@ -360,6 +360,8 @@ class Trainer(_train.Trainer):
     last smaller batch, uniform non-overlapping test windows; checkpoints, eval and the multi-process path as train.Trainer."""
     train_drop_last = False                              # :815
     momentum = 0.9                                       # :832
+    pool_stem_unsupported = ("the v2 part-box route resizes the box crop BEFORE the stem, so its stems read that resized float "
+                             "clip and not the pool's frames")
     resident_methods_missing = ("seq_len(i), label(i), video_item(i, indices=None) and frame_boxes(i), which ResidentGestureSet "
                                 "needs to gather RoiResize's uncropped 240 x 320 x 7 frames and their boxes from a frame pool "
                                 "(ChalearnGestureFrames and SyntheticGesture(videos=True) do)")

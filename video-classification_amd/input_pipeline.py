@@ -228,6 +228,7 @@ class FramePool:
         self.bytes_uploaded = 0
         self._resize = {}                       # (size, channels) -> the PadResize of add_raw
         self._byte_lut = None                   # roi_gather's table, made at its first call
+        self._tables = {}                       # clip's persistent device tables: 'index' / 'crop' -> flat int32 buffer
         self.capacity = None if capacity is None else int(capacity)
         if self.capacity is not None and self.capacity <= 0:
             raise ValueError(f"FramePool: capacity {capacity} frames")
@@ -331,11 +332,9 @@ class FramePool:
     def release(self, base: int) -> None:
         del self.live[base]
 
-    def gather(self, index_rows: torch.Tensor, out_dtype: torch.dtype = torch.float32, c0: int = 0,
-               c: Optional[int] = None, crop: Optional[torch.Tensor] = None, padding: Optional[int] = None) -> torch.Tensor:
-        """(N, T) arena slots (or -1) -> the (N, T, c, S, S) clips DevicePreprocess would write from the materialised frames;
-        crop (N, 2) int32 (top, left): with that RandomCrop (padding defaults to S // 10, as DevicePreprocess's), by ONE
-        ``sfk_u8_pool_gather_crop`` launch instead of the ``sfk_u8_pool_gather`` one"""
+    def _checked_rows(self, index_rows: torch.Tensor, who: str = "gather") -> torch.Tensor:
+        """the (N, T) int32 table of ``gather`` / ``clip`` (who: the caller the ValueError names): every entry -1 or a slot of a
+        video that is in the pool"""
         idx = torch.as_tensor(index_rows, dtype=torch.int32).contiguous()
         assert idx.dim() == 2 and idx.numel() > 0 and self.arena is not None
         ok = torch.zeros(self.arena.shape[0] + 1, dtype=torch.bool)      # the last entry stands for -1
@@ -343,7 +342,45 @@ class FramePool:
         for b, n in self.live.items():
             ok[b:b + n] = True
         if int(idx.min()) < -1 or int(idx.max()) >= self.arena.shape[0] or not bool(ok[idx.long()].all()):
-            raise ValueError("gather: an index is neither -1 nor a slot of a video that is in the pool")
+            raise ValueError(f"{who}: an index is neither -1 nor a slot of a video that is in the pool")
+        return idx
+
+    def _table(self, name: str, host: torch.Tensor) -> torch.Tensor:
+        """host int32 table -> its view of the pool's persistent device buffer `name`, written on the current stream.  The
+        buffer is sized at first use and grows to the largest table seen, so equal-shaped batches get the SAME address (a
+        smaller one the same base); the copy is ordered behind every launch already enqueued that reads the old contents."""
+        buf = self._tables.get(name)
+        if buf is None or buf.numel() < host.numel():
+            buf = self._tables[name] = torch.empty(host.numel(), dtype=torch.int32, device=self.device)
+        view = buf[:host.numel()].view(host.shape)
+        src = host
+        if src.device.type == "cpu" and self.device.type == "cuda" and not src.is_pinned():
+            src = src.pin_memory()
+        view.copy_(src, non_blocking=True)
+        return view
+
+    def clip(self, index_rows: torch.Tensor, channels, crop: Optional[torch.Tensor] = None,
+             padding: Optional[int] = None) -> list:
+        """(N, T) arena slots (or -1) -> one ``PoolClip`` per (c0, c) range of channels: the clips ``gather`` would write,
+        handed to the stems as the arena and the two tables instead (include/sfk_u8stem_pool.h, MODEL.POOL_STEM).  The table
+        is checked as ``gather`` checks it; nothing is launched.  The slots must stay live until the launches that read the
+        clips have been enqueued on this stream, and the next ``clip`` call overwrites the tables these clips hold."""
+        idx = self._checked_rows(index_rows, "clip")
+        h = self.arena.shape[1]
+        if crop is not None:
+            crop = torch.as_tensor(crop).to(torch.int32).contiguous()
+            assert tuple(crop.shape) == (idx.shape[0], 2), tuple(crop.shape)
+            crop = self._table("crop", crop)
+        padding = h // 10 if padding is None else int(padding)
+        index = self._table("index", idx)
+        return [PoolClip(self.arena, index, int(c0), int(c), crop, padding, self.lut, self.fill) for c0, c in channels]
+
+    def gather(self, index_rows: torch.Tensor, out_dtype: torch.dtype = torch.float32, c0: int = 0,
+               c: Optional[int] = None, crop: Optional[torch.Tensor] = None, padding: Optional[int] = None) -> torch.Tensor:
+        """(N, T) arena slots (or -1) -> the (N, T, c, S, S) clips DevicePreprocess would write from the materialised frames;
+        crop (N, 2) int32 (top, left): with that RandomCrop (padding defaults to S // 10, as DevicePreprocess's), by ONE
+        ``sfk_u8_pool_gather_crop`` launch instead of the ``sfk_u8_pool_gather`` one"""
+        idx = self._checked_rows(index_rows)
         _, h, w, p = self.arena.shape
         c = p - c0 if c is None else c
         out = torch.empty(idx.shape[0], idx.shape[1], c, h, w, dtype=out_dtype, device=self.device)
@@ -713,6 +750,80 @@ class U8Clip:
         return (self.frames.data_ptr(), None if self.crop is None else self.crop.data_ptr(), self.lut.data_ptr())
 
 
+@dataclass(eq=False)
+class PoolClip:
+    """``U8Clip``'s sibling for frames that lie in a ``FramePool``: one pathway's view of (arena, index table, crop table), read
+    by the stem kernels themselves (include/sfk_u8stem_pool.h, MODEL.POOL_STEM), so the float clip ``FramePool.gather`` would
+    write is never materialised.  Logical element (n, ci, t, h, w) is ``lut[arena[index[n, t], h + top - pad, w + left - pad,
+    c0 + ci]]`` -- zero outside the frame, no shift without a crop, ``lut[fill]`` in place of the arena byte when index[n, t]
+    is outside [0, F): the clip ``gather`` produces, sliced to channels c0 .. c0 + c - 1 and permuted to (N, c, T, H, W).
+
+    arena: (F, H, W, P) uint8 with channel stride 1; index: (N, T) int32 and crop: (N, 2) int32 (top, left) or None, both on
+    the arena's device.  Their CONTENTS are read when the stems run, so a captured graph follows new tables written into the
+    same tensors, and a fixed-capacity arena hands every batch of an epoch the same addresses."""
+    arena: torch.Tensor
+    index: torch.Tensor
+    c0: int
+    c: int
+    crop: Optional[torch.Tensor]
+    pad: int
+    lut: torch.Tensor
+    fill: int
+
+    def __post_init__(self):
+        a, idx = self.arena, self.index
+        assert a.dtype == torch.uint8 and a.dim() == 4 and a.stride(3) == 1, "arena: (F, H, W, P) uint8, channels contiguous"
+        assert 0 <= self.c0 and 0 < self.c and self.c0 + self.c <= a.shape[3] <= a.stride(2), (self.c0, self.c, a.shape)
+        assert idx.dtype == torch.int32 and idx.dim() == 2 and idx.is_contiguous() and idx.device == a.device
+        assert self.lut.dtype == torch.float32 and self.lut.numel() == 256 and self.lut.device == a.device
+        assert 0 <= int(self.fill) <= 255 and self.pad >= 0
+        if self.crop is not None:
+            assert self.crop.dtype == torch.int32 and tuple(self.crop.shape) == (idx.shape[0], 2) and self.crop.is_contiguous()
+            assert self.crop.device == a.device
+
+    # the logical (N, c, T, H, W) geometry, as the engine's plan code reads a float clip's
+    @property
+    def shape(self) -> torch.Size:
+        (n, t), (_, h, w, _) = self.index.shape, self.arena.shape
+        return torch.Size((n, self.c, t, h, w))
+
+    @property
+    def device(self) -> torch.device:
+        return self.arena.device
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return torch.uint8
+
+    def dim(self) -> int:
+        return 5
+
+    def numel(self) -> int:
+        return self.shape.numel()
+
+    def element_size(self) -> int:
+        return 1
+
+    def geometry_key(self) -> tuple:
+        """what a plan built for this clip depends on (never equal to a float tensor's or a U8Clip's key)"""
+        a = self.arena
+        return ("u8pool", tuple(a.shape), tuple(a.stride()), tuple(self.index.shape), self.c0, self.c, self.crop is not None,
+                self.pad, self.fill)
+
+    def bound_ptrs(self) -> tuple:
+        """the device addresses the stem ops hold"""
+        return (self.arena.data_ptr(), self.index.data_ptr(), None if self.crop is None else self.crop.data_ptr(),
+                self.lut.data_ptr())
+
+
+STEM_CLIPS = (U8Clip, PoolClip)                 # what a stem reads in place of a float tensor
+
+
+def is_pool_clips(x) -> bool:
+    """a batch entry that ``FramePool.clip`` made: a list of PoolClips, one per pathway"""
+    return isinstance(x, (list, tuple)) and len(x) > 0 and all(isinstance(c, PoolClip) for c in x)
+
+
 def u8_pathways(frames: torch.Tensor, crop: Optional[torch.Tensor], lut: torch.Tensor, channels) -> list:
     """U8Clips over the same device frames and crop, one per (c0, c) range; pad = S // 10 (RandomCrop's padding)."""
     pad = frames.shape[2] // 10
@@ -808,6 +919,7 @@ class _ResidentSet:
     class whose arena is measured in bytes says so), a request may name the rectangle of the frames it needs (``_request``)
     and the table a batch is gathered from holds whatever ``_add`` returns per frame (slots here)."""
     methods = RESIDENT_METHODS                  # what the train set must offer
+    lazy_batch = False                          # the batch reads the arena when the STEP runs (MODEL.POOL_STEM), not in _batch
     table_dtype = torch.int32                   # of the per-frame arena rows _add returns
     crop_key = None                             # the item entry a request's rectangle crops
 
@@ -897,6 +1009,11 @@ class _ResidentSet:
                 self.resident_used += cost
         return self._resident[video]
 
+    def _drain(self) -> None:
+        """wait for everything enqueued on the device (every stream: the stems may run on the engine's side streams)"""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+
     def _add(self, item) -> tuple:
         """(base, (L,) int32 arena slot of every requested frame, -1 for a missing one) of a dataset item"""
         windows = torch.as_tensor(item["windows"], dtype=torch.int32)
@@ -942,12 +1059,29 @@ class _ResidentSet:
             self.spilled_clips += len(bases)
             self.spill_peak = max(self.spill_peak, sum(self._live_frames(b) for b in bases))
             batch = self._batch(table, entry)
-            for b in bases:                     # free for the uploads queued behind that gather on the same stream
-                self.pool.release(b)
+            if not self.lazy_batch:
+                for b in bases:                 # free for the uploads queued behind that gather on the same stream
+                    self.pool.release(b)
             batch["label"] = torch.tensor([int(self.train_set.label(v)) for v in videos], dtype=torch.int64)
             if jitter is not None:
                 batch["jitter"] = jitter
-            yield batch
+            if not self.lazy_batch:
+                yield batch
+                continue
+            # the batch reads the arena when its step runs, so the slots go back only when the consumer leaves this yield.  It
+            # comes back for the next batch: the step that reads these slots (and the tables) has been enqueued, the next
+            # uploads queue behind it.  It stops here instead -- a break, an exception, the generator dropped: the release
+            # still happens (the bookkeeping is that of the gathered route), but what was enqueued is not known to be on the
+            # stream later uploads take, so the device is drained first.  A batch not yet stepped is void from then on.
+            resumed = False
+            try:
+                yield batch
+                resumed = True
+            finally:
+                if not resumed:
+                    self._drain()
+                for b in bases:
+                    self.pool.release(b)
 
 
 class ResidentTrainSet(_ResidentSet):
@@ -965,13 +1099,19 @@ class ResidentTrainSet(_ResidentSet):
     Plan: ``plan(e)`` batches are (videos, indices (N, T), crop (N, 2), jitter (N, 8) | None); per clip the start, then the
     crop (``draw_crop_offsets``), then the jitter row.
     ``epoch(e)`` yields {'<key>': (N, T, 21, S, S) float32 on the device, 'label': (N,), optionally 'jitter': (N, 8)}: what
-    every model's prepare_data takes under the float key (like pooled eval, whatever MODEL.U8_STEM says)."""
+    every model's prepare_data takes under the float key (like pooled eval, whatever MODEL.U8_STEM says).
+    stem_channels (MODEL.POOL_STEM): the (c0, c) channel range of every pathway's stem.  '<key>' is then the list of
+    ``PoolClip``s ``FramePool.clip`` makes -- no launch, no float clip; the stems read the arena when the step runs, so a
+    spilled clip's slots are released when the consumer comes back for the next batch, after it has enqueued that step."""
 
     def __init__(self, train_set, cfg, device="cuda", backend=None, batch_size: int = 1, drop_last: bool = True, seed: int = 0,
-                 capacity_frames: Optional[int] = None, num_workers: int = 0, jitter=None):
+                 capacity_frames: Optional[int] = None, num_workers: int = 0, jitter=None, stem_channels=None):
         super().__init__(train_set, cfg, device, backend, batch_size, drop_last, seed, num_workers, jitter)
         from .config import crop_resize_dict
         self.key = cfg.MODEL.R3D_INPUT
+        # MODEL.POOL_STEM: the (c0, c) range each pathway's stem reads; the batch is then those PoolClips, not the float clip
+        self.stem_channels = None if stem_channels is None else [(int(c0), int(c)) for c0, c in stem_channels]
+        self.lazy_batch = self.stem_channels is not None
         self.size = int(crop_resize_dict[self.key])
         if capacity_frames is None:
             capacity_frames = int(float(cfg.MODEL.RESIDENT_GB) * 2 ** 30 // (self.size * self.size * 21))
@@ -986,6 +1126,8 @@ class ResidentTrainSet(_ResidentSet):
         return self.pool.add(item[pool_key(self.key)], windows)
 
     def _batch(self, table, entry) -> dict:
+        if self.stem_channels is not None:
+            return {self.key: self.pool.clip(table, self.stem_channels, crop=entry[2])}
         return {self.key: self.pool.gather(table, torch.float32, 0, None, crop=entry[2])}
 
 

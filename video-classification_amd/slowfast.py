@@ -14,7 +14,7 @@ import torch
 
 from . import arch
 from .engine import Engine
-from .input_pipeline import U8Clip
+from .input_pipeline import STEM_CLIPS
 
 _DTYPES = {"fp32": torch.float32, "f32": torch.float32, "float32": torch.float32, "bf16": torch.bfloat16,
            "bfloat16": torch.bfloat16}
@@ -49,9 +49,10 @@ class SlowFast(torch.nn.Module):
     def forward(self, x, slow_t_index: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x: [x_slow, x_fast] (SlowFast) or one (N,C,T,H,W) tensor (the single-pathway res3d network); res2d: the
         reference's (N, T*5, H, W) tensor or the loader's (N, T, >=5, H, W) memory (read in place, Engine.input_view).
-        Any pathway may be an input_pipeline.U8Clip: its stem then reads the uint8 frames (MODEL.U8_STEM)."""
+        Any pathway may be an input_pipeline.U8Clip: its stem then reads the uint8 frames (MODEL.U8_STEM), or a PoolClip
+        (MODEL.POOL_STEM: out of the frame pool)."""
         if self.spec.pathways == 1:
-            x_slow, x_fast = self.engine.input_view(x if isinstance(x, (torch.Tensor, U8Clip)) else x[0]), None
+            x_slow, x_fast = self.engine.input_view(x if isinstance(x, (torch.Tensor,) + STEM_CLIPS) else x[0]), None
         else:
             x_slow, x_fast = x[0], x[1]
         if slow_t_index is None:

@@ -30,7 +30,7 @@ from torch.utils.data.dataloader import default_collate
 from . import dist as sdist
 from .config import crop_resize_dict
 from .engine import Engine
-from .input_pipeline import U8Clip, h2d
+from .input_pipeline import STEM_CLIPS, h2d, is_pool_clips
 from .slowfast import init_my_slowfast
 
 
@@ -249,6 +249,30 @@ class ModelManager:
     def _u8_stem(self) -> bool:
         return bool(self.cfg.MODEL.get("U8_STEM", False))
 
+    # ---- MODEL.POOL_STEM: on the pooled routes (ResidentTrainSet batches, pooled run_eval) the batch carries, under the float
+    #      key, the PoolClips FramePool.clip made for stem_channels(): the stems read the arena through its index table
+    def _pool_stem(self) -> bool:
+        return bool(self.cfg.MODEL.get("POOL_STEM", False))
+
+    def stem_channels(self) -> list:
+        """the (c0, c) range of the 21 loader channels each pathway's stem reads: BGR+UV, or BGR+UV and the 15 flow channels"""
+        if self.arch == "canonical8x8":
+            raise ValueError("MODEL.POOL_STEM: the canonical8x8 stems read the float clip's three BGR planes through their "
+                             "production kernels, which have no uint8 source")
+        return [(0, 5), (5, 15)] if "slowfast" in self.cfg.MODEL.NAME else [(0, 5)]
+
+    def _pool_clips(self, batch):
+        """the batch's PoolClips (None: not such a batch), refusing a 'jitter' entry as _u8_clips does"""
+        x = batch.get(self.cfg.MODEL.R3D_INPUT)
+        if not is_pool_clips(x):
+            return None
+        if "jitter" in batch:
+            raise ValueError(self._NO_FLOAT_CLIP.format("POOL_STEM"))
+        return list(x)
+
+    _NO_FLOAT_CLIP = ("MODEL.{0}: true reads the uint8 frames in the stems, so there is no float clip for the "
+                      "batch's 'jitter' entry to work on; turn {0} or MODEL.COLOR_JITTER off")
+
     def _u8_float(self, batch) -> torch.Tensor:
         """DevicePreprocess: (N,T,S,S,P) uint8 -> (N,T,P,S,S) float32 on the device (then the batch's 'jitter', if any)"""
         if self._pre is None:
@@ -290,8 +314,7 @@ class ModelManager:
         """U8Clips over the pinned-H2D frames and crop, one per (c0, c) channel range"""
         from .input_pipeline import normalize_lut, u8_pathways
         if "jitter" in batch:
-            raise ValueError("MODEL.U8_STEM: true reads the uint8 frames in the stems, so there is no float clip for the "
-                             "batch's 'jitter' entry to work on; turn U8_STEM or MODEL.COLOR_JITTER off")
+            raise ValueError(self._NO_FLOAT_CLIP.format("U8_STEM"))
         if self._lut is None:
             self._lut = normalize_lut().to(self.device)
         frames = self._h2d(batch[self._u8_key(batch)])
@@ -326,6 +349,9 @@ class ModelManager:
         stem reads frame t, channel c as input channel t*5 + c (Engine.input_view)."""
         batch = self._resized(batch)
         if self._res2d_backend() == "engine":
+            clips = self._pool_clips(batch)              # MODEL.POOL_STEM on a pooled route
+            if clips is not None:
+                return clips[0], self._h2d(batch['label'])
             if self._u8_key(batch):                      # the uint8 transport
                 if self._u8_stem():
                     return self._u8_clips(batch, [(0, 5)])[0], self._h2d(batch['label'])
@@ -393,6 +419,9 @@ class ModelManager:
         """(N,T,21,S,S) -> BGR+UV (N,5,T,S,S) strided view (train.py:85-89; 5 channels as train.py:72 / the 5-channel
         stem of :81).  A uint8 batch: DevicePreprocess's float clip, or (MODEL.U8_STEM) a U8Clip over channels 0:5."""
         batch = self._resized(batch)
+        clips = self._pool_clips(batch)                  # MODEL.POOL_STEM on a pooled route
+        if clips is not None:
+            return clips[0], self._h2d(batch['label'])
         if self._u8_key(batch):
             if self._u8_stem():
                 return self._u8_clips(batch, [(0, 5)])[0], self._h2d(batch['label'])
@@ -410,6 +439,9 @@ class ModelManager:
         MODEL.U8_STEM, inside the two stems, which read the frames as U8Clips over channels 0:5 and 5:20.
         An optional ``jitter`` (N,8) entry applies ColorJitter to the B, G, R planes of the float clip (_jitter_v1)."""
         batch = self._resized(batch)
+        clips = self._pool_clips(batch)                  # MODEL.POOL_STEM on a pooled route: PoolClips over channels 0:5 and 5:20
+        if clips is not None:
+            return clips, self._h2d(batch['label'])
         if self._u8_key(batch):
             if self._u8_stem():
                 return self._u8_clips(batch, [(0, 5), (5, 15)]), self._h2d(batch['label'])
@@ -722,6 +754,7 @@ class Trainer:
             train_loader, test_loader = self._make_loaders(train_set, test_set)
         self.train_loader, self.test_loader = train_loader, test_loader
         self.mm = self._model_manager(cfg, device, backend)
+        self.pool_stem = self._check_pool_stem()
         if bool(cfg.MODEL.get("RESIDENT_TRAIN", False)):
             self.resident = self._make_resident(train_set, backend)
         self.model = self.mm.init_model()
@@ -760,6 +793,22 @@ class Trainer:
     resident_methods_missing = ("seq_len(i), label(i) and video_item(i, indices=None) "
                                 "(ChalearnVideoFramesU8 and SyntheticChalearn(as_uint8 / raw) do)")
 
+    # ---- MODEL.POOL_STEM: the pooled routes hand the stems PoolClips instead of the gathered float clip
+    pool_stem_unsupported = None                         # a derived trainer's reason why it cannot (gesture_v2.Trainer)
+
+    def _check_pool_stem(self) -> bool:
+        if not bool(self.cfg.MODEL.get("POOL_STEM", False)):
+            return False
+        why = self.pool_stem_unsupported
+        if why is None and self.world > 1:
+            why = "the resident set it feeds from has no per-rank partition yet: WORLD_SIZE must be 1"
+        elif why is None and self.cfg.MODEL.NAME == "res2d" and self.mm._res2d_backend() == "torch":
+            why = "MODEL.NAME res2d with the torch backend is host plumbing and has no stem kernels; use RES2D_BACKEND = 'engine'"
+        if why is not None:
+            raise ValueError(f"MODEL.POOL_STEM: {why}")
+        self.mm.stem_channels()                          # (raises for an architecture without uint8 stems)
+        return True
+
     def _offers_resident(self, train_set) -> bool:
         from .input_pipeline import offers_resident
         return offers_resident(train_set)
@@ -767,7 +816,8 @@ class Trainer:
     def _build_resident(self, train_set, backend):
         from .input_pipeline import ResidentTrainSet
         return ResidentTrainSet(train_set, self.cfg, self.device, backend, batch_size=self.batch_size,
-                                drop_last=self.train_drop_last, num_workers=self.num_workers, jitter=jitter_ranges(self.cfg))
+                                drop_last=self.train_drop_last, num_workers=self.num_workers, jitter=jitter_ranges(self.cfg),
+                                stem_channels=self.mm.stem_channels() if self.pool_stem else None)
 
     def _make_resident(self, train_set, backend):
         """MODEL.RESIDENT_TRAIN: the resident set (v1: ResidentTrainSet) train_epoch iterates instead of the train loader"""
@@ -842,7 +892,7 @@ class Trainer:
         resident = getattr(self, "resident", None)       # MODEL.RESIDENT_TRAIN: clips gathered from the frames on the device
         for batch in (self.train_loader if resident is None else resident.epoch(self.epoch)):
             x, y_true = self.mm.prepare_data(batch)
-            if isinstance(x, (torch.Tensor, U8Clip)):    # res3d / res2d: one input tensor (or uint8 clip)
+            if isinstance(x, (torch.Tensor,) + STEM_CLIPS):    # res3d / res2d: one input tensor (or uint8 clip)
                 self.step(x, None, y_true)
             else:
                 self.step(x[0], x[1], y_true, slow_t_index=self.model.slow_t_index)
@@ -886,7 +936,8 @@ class Trainer:
         A loader element that is a pooled item (a dict with '<R3D_INPUT>_pool' and 'windows', input_pipeline.py) is one
         video whose frames are uploaded once into ``self.frame_pool``; its windows join the batches as (video, row)
         references, and a batch of them is ONE ``sfk_u8_pool_gather`` launch that writes the float clip, handed to
-        prepare_data under the float key (whatever MODEL.U8_STEM says).  ``frame_pool.bytes_uploaded`` counts this call's.
+        prepare_data under the float key (whatever MODEL.U8_STEM says) -- or, under MODEL.POOL_STEM, no launch at all: the
+        batch is the ``PoolClip``s of ``FramePool.clip`` and the stems read the pool (include/sfk_u8stem_pool.h).  ``frame_pool.bytes_uploaded`` counts this call's.
         A raw pooled item ('<R3D_INPUT>_rawpool' + 'raw_hw': the frames at their native sizes) differs only in how its arena
         slots are filled: ``FramePool.add_raw`` uploads the raw bytes and ``sfk_u8_pad_resize_cubic`` writes the frames."""
         loader = self.test_loader if dataset_loader is None else dataset_loader
@@ -908,20 +959,31 @@ class Trainer:
                      "left": int(b["windows"].shape[0])}
             return [(video, r) for r in range(video["left"])]
 
+        pool_stem = getattr(self, "pool_stem", False)          # MODEL.POOL_STEM: the stems read the pool, nothing is gathered
+        read_out = []                                          # ... so a video's slots are free only once the forward that
+                                                               # reads its last window has been enqueued (test_batch)
+
         def collate(items):
             if not isinstance(items[0], tuple):
                 return default_collate(items)
-            clip = self.frame_pool.gather(torch.stack([v["rows"][r] for v, r in items]))
+            rows = torch.stack([v["rows"][r] for v, r in items])
+            clip = self.frame_pool.clip(rows, self.mm.stem_channels()) if pool_stem else self.frame_pool.gather(rows)
             for v, _ in items:
                 v["left"] -= 1
-                if v["left"] == 0:                             # its last window is in this gather: the slots are free
+                if v["left"] == 0 and pool_stem:
+                    read_out.append(v["base"])
+                elif v["left"] == 0:                           # its last window is in this gather: the slots are free
                     self.frame_pool.release(v["base"])         # for uploads queued behind it on the same stream
             return {key: clip, "label": torch.tensor([v["label"] for v, _ in items])}
 
         def test_batch(collect):
-            x, y_true = self.mm.prepare_data(collect)
-            with torch.no_grad():
-                y_pred = self.model(x)
+            try:
+                x, y_true = self.mm.prepare_data(collect)
+                with torch.no_grad():
+                    y_pred = self.model(x)
+            finally:                                           # that forward is enqueued (or failed before it read anything):
+                while read_out:                                # uploads queue behind it
+                    self.frame_pool.release(read_out.pop(0))
             logit_list.append(y_pred.float().clone())      # the engine reuses its logits buffer
             true_list.append(y_true.clone())
 
