@@ -235,6 +235,13 @@ class _JitterDesc(C.Structure):
                 ("workspace", C.c_void_p)]
 
 
+class _OptimHp(C.Structure):
+    """include/sfk_optim.h sfk_optim_hp: the device learning-rate table, weight decay and clipping coefficient shared by
+    sfk_adam_hp and sfk_sgd_hp"""
+    _fields_ = [("struct_size", C.c_uint32), ("decay_mode", C.c_int32), ("lr_table", C.c_void_p), ("lr_len", C.c_int64),
+                ("decay_count", C.c_int64), ("clip_coef", C.c_void_p), ("weight_decay", C.c_float), ("reserved0", C.c_int32)]
+
+
 class _PoolDesc(C.Structure):
     """include/sfk_pool.h sfk_pool_desc: byte (f, y, x, ch) of the frame pool at
     pool[f*frame_stride + y*row_stride + x*pixel_pitch + c0 + ch]; clip n, time t of out is frame index[n][t] through lut"""
@@ -449,6 +456,18 @@ SIGNATURES_U8STEM_POOL = {
     "sfk_u8pstem2d_fwd": [C.POINTER(_U8PoolClip), _PV, _P_FMAP, _PF, _PV],
     "sfk_u8pstem2d_wgrad": [C.POINTER(_U8PoolClip), _P_FMAP, _PF, _PV],
 }
+# include/sfk_optim.h: the optimizer step with a device learning-rate table, weight decay and gradient clipping, same library,
+# its own header and version
+OPTIM_ABI_VERSION = 1      # include/sfk_optim.h SFK_OPTIM_ABI_VERSION
+DECAY_MODES = {"none": 0, "l2": 1, "decoupled": 2}   # include/sfk_optim.h SFK_DECAY_*
+GRAD_NORM_MAX_PARTS = 2048   # include/sfk_optim.h SFK_GRAD_NORM_MAX_PARTS
+SIGNATURES_OPTIM = {
+    "sfk_optim_abi_version": [],
+    "sfk_adam_hp": [_PF, _PF, _PF, _PF, _I64, C.POINTER(_OptimHp), _F, _F, _F, _F, _PV, _PV, _I32, _PV],
+    "sfk_sgd_hp": [_PF, _PF, _PF, _I64, C.POINTER(_OptimHp), _F, _F, _I32, _F, _PV, _PV, _I32, _PV],
+    "sfk_grad_norm_parts": [_I64],
+    "sfk_grad_norm": [_PF, _I64, _F, _F, _PV, _PF, _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
@@ -520,6 +539,12 @@ def new_roi_ragged_desc() -> "_RoiRaggedDesc":
     return d
 
 
+def new_optim_hp() -> "_OptimHp":
+    d = _OptimHp()
+    d.struct_size = C.sizeof(_OptimHp)
+    return d
+
+
 def new_resize_desc() -> "_ResizeDesc":
     d = _ResizeDesc()
     d.struct_size = C.sizeof(_ResizeDesc)
@@ -544,7 +569,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
                        "(there is no CPU or PyTorch fallback for the SlowFast path)")
     lib = C.CDLL(path)
     for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL,
-                  SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL, SIGNATURES_ROI_RAGGED, SIGNATURES_U8STEM_POOL):
+                  SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL, SIGNATURES_ROI_RAGGED, SIGNATURES_U8STEM_POOL,
+                  SIGNATURES_OPTIM):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -571,6 +597,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk roi_ragged ABI version mismatch: library {lib.sfk_roi_ragged_abi_version()}, binding {ROI_RAGGED_ABI_VERSION}")
     if lib.sfk_u8stem_pool_abi_version() != U8STEM_POOL_ABI_VERSION:
         raise SfkError(f"libsfk u8stem_pool ABI version mismatch: library {lib.sfk_u8stem_pool_abi_version()}, binding {U8STEM_POOL_ABI_VERSION}")
+    if lib.sfk_optim_abi_version() != OPTIM_ABI_VERSION:
+        raise SfkError(f"libsfk optim ABI version mismatch: library {lib.sfk_optim_abi_version()}, binding {OPTIM_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -1063,6 +1091,50 @@ class HipBackend:
         sd = _DT[shadow.dtype] if shadow is not None else SFK_F32
         return self._plain("sfk_sgd", _ptr(p), _ptr(g), _ptr(buf), count, lr, momentum, dampening, 1 if nesterov else 0,
                            gscale, _ptr(step), _ptr(shadow), sd, keep=(p, g, buf, step, shadow))
+
+    @staticmethod
+    def _optim_hp(lr_table, weight_decay, decay_mode, decay_count, clip_coef):
+        assert lr_table.dtype == torch.float32 and lr_table.is_contiguous() and lr_table.dim() == 1
+        assert clip_coef is None or clip_coef.dtype == torch.float32
+        d = new_optim_hp()
+        d.decay_mode = DECAY_MODES[decay_mode] if isinstance(decay_mode, str) else int(decay_mode)
+        d.lr_table, d.lr_len, d.decay_count = lr_table.data_ptr(), lr_table.numel(), int(decay_count)
+        d.clip_coef, d.weight_decay = _ptr(clip_coef), float(weight_decay)
+        return d
+
+    def adam_hp(self, p, g, m, v, count, lr_table, b1, b2, eps, gscale, step, shadow=None, weight_decay: float = 0.0,
+                decay_mode="none", decay_count: int = 0, clip_coef=None):
+        """sfk_adam_hp (include/sfk_optim.h): sfk_adam with the rate of step s read from lr_table[min(s, len) - 1] on the
+        device, weight decay ('none' | 'l2' | 'decoupled') over elements [0, decay_count) and an optional clipping
+        coefficient (device float[1])"""
+        sd = _DT[shadow.dtype] if shadow is not None else SFK_F32
+        d = self._optim_hp(lr_table, weight_decay, decay_mode, decay_count, clip_coef)
+        return self._plain("sfk_adam_hp", _ptr(p), _ptr(g), _ptr(m), _ptr(v), count, C.byref(d), b1, b2, eps, gscale,
+                           _ptr(step), _ptr(shadow), sd, keep=(d, p, g, m, v, step, shadow, lr_table, clip_coef))
+
+    def sgd_hp(self, p, g, buf, count, lr_table, momentum, dampening, nesterov, gscale, step, shadow=None,
+               weight_decay: float = 0.0, decay_mode="none", decay_count: int = 0, clip_coef=None):
+        """sfk_sgd_hp (include/sfk_optim.h): sfk_sgd with the device rate table, L2 weight decay and clipping"""
+        sd = _DT[shadow.dtype] if shadow is not None else SFK_F32
+        d = self._optim_hp(lr_table, weight_decay, decay_mode, decay_count, clip_coef)
+        return self._plain("sfk_sgd_hp", _ptr(p), _ptr(g), _ptr(buf), count, C.byref(d), momentum, dampening,
+                           1 if nesterov else 0, gscale, _ptr(step), _ptr(shadow), sd,
+                           keep=(d, p, g, buf, step, shadow, lr_table, clip_coef))
+
+    def grad_norm_parts(self, count: int) -> int:
+        """rows of float64 partial sums sfk_grad_norm needs for `count` gradients (a function of count alone)"""
+        r = int(self.lib.sfk_grad_norm_parts(count))
+        if r < 0:
+            _check(r, "sfk_grad_norm_parts")
+        return r
+
+    def grad_norm(self, g, count, gscale, max_norm, partials, out):
+        """sfk_grad_norm (include/sfk_optim.h): out[0] = ||g * gscale||_2, out[1] = min(1, max_norm / (out[0] + 1e-6));
+        partials: float64[grad_norm_parts(count)], out: float32[2]"""
+        assert partials.dtype == torch.float64 and partials.numel() >= self.grad_norm_parts(count)
+        assert out.dtype == torch.float32 and out.numel() >= 2
+        return self._plain("sfk_grad_norm", _ptr(g), count, gscale, max_norm, _ptr(partials), _ptr(out),
+                           keep=(g, partials, out))
 
     def roi_resize(self, src, lut, box, out, antialias: bool, crop=None, pad: int = 0, c_off: int = 0):
         """sfk_roi_resize (include/sfk_v2.h): src (N,T,H,W,C) uint8, any byte strides (HWC or a permuted planar view);

@@ -110,6 +110,16 @@ _C.MODEL.JITTER_HUE = 0.1
 _C.MODEL.RESIDENT_TRAIN = False  # keep the decoded train frames on the device and gather the cropped clips there (input_pipeline.ResidentTrainSet)
 _C.MODEL.RESIDENT_GB = 32.0     # RESIDENT_TRAIN: the size of the frame arena, GiB (its last BATCH_SIZE * CLIP_LEN slots are the spill region)
 _C.MODEL.RESIDENT_STORE = 'frame'  # v2 RESIDENT_TRAIN: 'frame' keeps whole frames in a FramePool, 'box' only each video's part-box rectangle in a BoxArena of RESIDENT_GB bytes
+# ---- the scheduled optimizer step (include/sfk_optim.h, schedule.py); every default keeps the plain sfk_adam / sfk_sgd launch
+_C.MODEL.LR_SCHEDULE = 'constant'   # 'constant' | 'cosine' (linear warm-up, then cosine annealing to LR_MIN) | 'multistep'
+_C.MODEL.LR_WARMUP_STEPS = 0        # cosine: optimizer steps of linear warm-up from LR / steps to LR
+_C.MODEL.LR_MIN = 0.0               # cosine: the rate the annealing ends at
+_C.MODEL.LR_MILESTONES = []         # multistep: the epochs at which the rate is multiplied by LR_GAMMA
+_C.MODEL.LR_GAMMA = 0.1
+_C.MODEL.WEIGHT_DECAY = 0.0
+_C.MODEL.WEIGHT_DECAY_MODE = 'decoupled'   # 'decoupled' (AdamW; Adam only) | 'l2' (torch's Adam / SGD weight_decay)
+_C.MODEL.WEIGHT_DECAY_SCOPE = 'weights'    # 'weights' (conv filters and the FC weight) | 'all' (biases and BatchNorm too)
+_C.MODEL.CLIP_GRAD_NORM = 0.0       # clip_grad_norm_(max_norm) before the optimizer launch; 0 = off
 _C.DIST = CfgNode()
 _C.DIST.BUCKET_MB = 32         # gradient all-reduce bucket size
 

@@ -283,6 +283,8 @@ class Engine:
         self.adam_step = None
         self.sgd_buf = None
         self.sgd_step = None
+        self.grad_norm = None          # (norm, clipping coefficient) of the last clipped step: grad_norm_ops
+        self.grad_norm_parts = None
         # compute-precision copies of the filters: S = [cout][tap][cin] (forward, filter-gradient layout),
         # St = [cin][tap][cout] (data-gradient pass)
         self.S = self.P.data if self.dtype == torch.float32 else self._new(self.conv_total, dtype=self.dtype)
@@ -1356,4 +1358,61 @@ class Engine:
                             betas[1], eps, grad_scale, self.adam_step, None)
         tail = self.be.adam(self.P.data[:cut], self.G[:cut], self.adam_m[:cut], self.adam_v[:cut], cut, lr, betas[0],
                             betas[1], eps, grad_scale, self.adam_step_tail, None)
+        return main, tail
+
+    # ---- the scheduled optimizer step (include/sfk_optim.h): the rate of step s read from a device table, weight decay and
+    #      gradient clipping.  adam_ops / sgd_ops / adam_split_ops above stay the default route and are not touched by these.
+    def decay_count(self, scope: str) -> int:
+        """arena elements [0, decay_count) decay: 'weights' = the conv filters and the FC weight (the arena is conv filters |
+        FC weight | FC bias | BN gamma/beta, _build_params), 'all' = every parameter"""
+        if scope not in ("weights", "all"):
+            raise ValueError(f"decay_scope={scope!r}: 'weights' or 'all'")
+        return self.fc_b_off if scope == "weights" else self.arena_numel
+
+    def lr_table(self, rates) -> torch.Tensor:
+        """the per-step rates as the device float32 table the hp launches index with their step counter"""
+        t = torch.as_tensor(rates, dtype=torch.float32).reshape(-1)
+        if t.numel() < 1:
+            raise ValueError("lr_table: at least one rate")
+        return t.to(self.device).contiguous()
+
+    def grad_norm_ops(self, max_norm: float, grad_scale: float = 1.0) -> Run:
+        """sfk_grad_norm over the whole gradient arena: self.grad_norm = (||G * grad_scale||_2, min(1, max_norm / (norm + 1e-6)))
+        on the device, float32[2]; the partial rows are allocated on first use"""
+        if self.grad_norm is None:
+            self.grad_norm = self._new(2)
+            self.grad_norm_parts = self._new(self.be.grad_norm_parts(self.arena_numel), dtype=torch.float64)
+        return self.be.grad_norm(self.G, self.arena_numel, grad_scale, max_norm, self.grad_norm_parts, self.grad_norm)
+
+    def adam_hp_ops(self, lr_table: torch.Tensor, betas=(0.9, 0.999), eps: float = 1e-8, grad_scale: float = 1.0,
+                    weight_decay: float = 0.0, decay_mode: str = "none", decay_scope: str = "weights", clip_coef=None) -> Run:
+        self._adam_state()
+        return self.be.adam_hp(self.P.data, self.G, self.adam_m, self.adam_v, self.arena_numel, lr_table, betas[0], betas[1],
+                               eps, grad_scale, self.adam_step, None, weight_decay=weight_decay, decay_mode=decay_mode,
+                               decay_count=self.decay_count(decay_scope), clip_coef=clip_coef)
+
+    def sgd_hp_ops(self, lr_table: torch.Tensor, momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False,
+                   grad_scale: float = 1.0, weight_decay: float = 0.0, decay_mode: str = "none",
+                   decay_scope: str = "weights", clip_coef=None) -> Run:
+        if self.sgd_step is None:
+            self.sgd_buf = self._new(self.arena_numel)
+            self.sgd_step = self._new(1, dtype=torch.int64)
+        return self.be.sgd_hp(self.P.data, self.G, self.sgd_buf, self.arena_numel, lr_table, momentum, dampening, nesterov,
+                              grad_scale, self.sgd_step, None, weight_decay=weight_decay, decay_mode=decay_mode,
+                              decay_count=self.decay_count(decay_scope), clip_coef=clip_coef)
+
+    def adam_hp_split_ops(self, cut: int, lr_table: torch.Tensor, betas=(0.9, 0.999), eps: float = 1e-8,
+                          grad_scale: float = 1.0, weight_decay: float = 0.0, decay_mode: str = "none",
+                          decay_scope: str = "weights"):
+        """(main, tail) as adam_split_ops: arena [cut:] through adam_step, [:cut] through adam_step_tail (both read the same
+        table entry, TrainStep sets the tail counter to step - 1 first), each with its slice-relative decay_count.  No
+        clipping here: the coefficient needs the last filter gradient, which the main launch does not wait for."""
+        self._adam_state()
+        n, dc = self.arena_numel, self.decay_count(decay_scope)
+        kw = dict(weight_decay=weight_decay, decay_mode=decay_mode, clip_coef=None)
+        main = self.be.adam_hp(self.P.data[cut:], self.G[cut:], self.adam_m[cut:], self.adam_v[cut:], n - cut, lr_table,
+                               betas[0], betas[1], eps, grad_scale, self.adam_step, None,
+                               decay_count=min(max(dc - cut, 0), n - cut), **kw)
+        tail = self.be.adam_hp(self.P.data[:cut], self.G[:cut], self.adam_m[:cut], self.adam_v[:cut], cut, lr_table,
+                               betas[0], betas[1], eps, grad_scale, self.adam_step_tail, None, decay_count=min(dc, cut), **kw)
         return main, tail

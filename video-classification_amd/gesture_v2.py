@@ -370,8 +370,12 @@ class Trainer(_train.Trainer):
         return ModelManager(cfg, device=device, backend=backend)
 
     def _make_step(self, eng, use_graph, reducer):
+        kw = self._optim_kwargs()
+        if kw.get("decay_mode") == "decoupled":
+            raise ValueError("MODEL.WEIGHT_DECAY_MODE: decoupled needs Adam; the v2 trainer runs SGD (torch has no decoupled "
+                             "SGD): set WEIGHT_DECAY_MODE: l2")
         return _train.TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer, optimizer="sgd",
-                                momentum=self.momentum)
+                                momentum=self.momentum, **kw)
 
     def _offers_resident(self, train_set) -> bool:
         from .input_pipeline import GESTURE_METHODS, offers_resident

@@ -44,11 +44,38 @@ class TrainStep:
 
     def __init__(self, engine: Engine, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, use_graph: bool = False,
                  reducer: Optional[sdist.GradReducer] = None, overlap_segments: int = 6, optimizer: str = "adam",
-                 momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False):
+                 momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False, lr_table=None,
+                 weight_decay: float = 0.0, decay_mode: str = "none", decay_scope: str = "weights",
+                 clip_grad_norm: float = 0.0):
         """optimizer 'adam' (train.py:182: lr, betas, eps) or 'sgd' (the v2 trainer, new_feature_test.py:832: lr, momentum,
-        dampening, nesterov; one sfk_sgd launch over the arena, never split beside the last kernel)."""
+        dampening, nesterov; one sfk_sgd launch over the arena, never split beside the last kernel).
+
+        lr_table, weight_decay, decay_mode, decay_scope, clip_grad_norm: at their defaults the step issues exactly the
+        launches above (sfk_adam / sfk_sgd with `lr` by value).  Otherwise the optimizer launch is sfk_adam_hp / sfk_sgd_hp
+        (include/sfk_optim.h): lr_table (a sequence of per-step rates, see lr_schedule; None = `lr` at every step) goes to
+        the device once and step s of THIS optimizer reads entry min(s, len) - 1 with the counter the launch keeps on the
+        device, so a replayed graph follows the schedule; decay_mode 'none' | 'l2' (torch's Adam / SGD weight_decay) |
+        'decoupled' (AdamW; Adam only) over decay_scope 'weights' (conv filters and the FC weight) | 'all'; clip_grad_norm
+        > 0 runs sfk_grad_norm over the finished (reduced) gradients before one optimizer launch -- clip_grad_norm_(max_norm)
+        -- and leaves (norm, coefficient) in self.grad_norm.  The optimizer state and the step count are not checkpointed
+        (as in the reference), so a resumed run starts the table again."""
         if optimizer not in ("adam", "sgd"):
             raise ValueError(f"optimizer={optimizer!r}: 'adam' or 'sgd'")
+        if decay_mode not in ("none", "l2", "decoupled"):
+            raise ValueError(f"decay_mode={decay_mode!r}: 'none', 'l2' or 'decoupled'")
+        if decay_scope not in ("weights", "all"):
+            raise ValueError(f"decay_scope={decay_scope!r}: 'weights' or 'all'")
+        if weight_decay < 0 or clip_grad_norm < 0:
+            raise ValueError("weight_decay and clip_grad_norm must not be negative")
+        if weight_decay == 0 or decay_mode == "none":
+            weight_decay, decay_mode = 0.0, "none"
+        if optimizer == "sgd" and decay_mode == "decoupled":
+            raise ValueError("decay_mode='decoupled' needs optimizer='adam': torch has no decoupled SGD")
+        self.weight_decay, self.decay_mode, self.decay_scope = float(weight_decay), decay_mode, decay_scope
+        self.clip_grad_norm = float(clip_grad_norm)
+        self.hp = lr_table is not None or decay_mode != "none" or self.clip_grad_norm > 0     # the sfk_optim.h route
+        self.lr_table = engine.lr_table([lr] if lr_table is None else lr_table) if self.hp else None
+        self.grad_norm = None                             # device float32[2] (norm, coefficient) of the last step, with clipping
         self.eng, self.lr, self.betas, self.eps = engine, lr, betas, eps
         self.optimizer, self.momentum, self.dampening, self.nesterov = optimizer, momentum, dampening, nesterov
         self.reducer = reducer
@@ -82,6 +109,8 @@ class TrainStep:
     def _build(self, pl, labels):
         eng = self.eng
         gscale = self.reducer.grad_scale if self.reducer is not None else 1.0
+        if self.hp:
+            return self._build_hp(pl, labels, gscale)
         if self.optimizer == "sgd":
             opt = eng.sgd_ops(self.lr, self.momentum, self.dampening, self.nesterov, gscale)
         else:
@@ -97,6 +126,44 @@ class TrainStep:
                 and eng.options.split_adam):
             ops["adam_main"], ops["adam_tail"] = eng.adam_split_ops(pl.tail_cut[1], self.lr, self.betas, self.eps)
         return ops
+
+    def _split_ok(self, pl) -> bool:
+        eng = self.eng
+        return (self.optimizer == "adam" and pl.tail_cut is not None and not self.segmented and not self.use_graph
+                and eng.two_streams and eng.device.type == "cuda" and eng.options.split_adam)
+
+    def _build_hp(self, pl, labels, gscale):
+        """the ops of _build with the optimizer launch of include/sfk_optim.h; `grad_norm` (clipping on) runs after the whole
+        backward, so the split update is used only without it"""
+        eng = self.eng
+        decay = dict(weight_decay=self.weight_decay, decay_mode=self.decay_mode, decay_scope=self.decay_scope)
+        ops = dict(
+            loss=eng.loss_ops(pl, labels, self.loss, self.loss_sum, self.correct),
+            zero_loss=eng.be.fill_zero(self.loss),
+            zero_grad=eng.be.fill_zero(eng.G),
+        )
+        coef = None
+        if self.clip_grad_norm > 0:
+            ops["grad_norm"] = eng.grad_norm_ops(self.clip_grad_norm, gscale)
+            self.grad_norm = eng.grad_norm
+            coef = eng.grad_norm[1:2]
+        if self.optimizer == "sgd":
+            ops["adam"] = eng.sgd_hp_ops(self.lr_table, self.momentum, self.dampening, self.nesterov, gscale, clip_coef=coef, **decay)
+        else:
+            ops["adam"] = eng.adam_hp_ops(self.lr_table, self.betas, self.eps, gscale, clip_coef=coef, **decay)
+        if coef is None and self._split_ok(pl):
+            ops["adam_main"], ops["adam_tail"] = eng.adam_hp_split_ops(pl.tail_cut[1], self.lr_table, self.betas, self.eps, gscale, **decay)
+        return ops
+
+    def last_lr(self) -> float:
+        """the rate the last optimizer step used (one device read: the step counter; the table is kept on the host side too)"""
+        eng = self.eng
+        if not self.hp:
+            return float(self.lr)
+        step = eng.sgd_step if self.optimizer == "sgd" else eng.adam_step
+        s = int(step[0]) if step is not None else 0
+        n = self.lr_table.numel()
+        return float(self.lr_table[min(max(s, 1), n) - 1])
 
     def _eager(self, pl, ops):
         eng = self.eng
@@ -131,6 +198,8 @@ class TrainStep:
                 eng._run_lanes(pl.bwd, a, b)          # the pathway lanes and the filter-gradient lane, as the single-rank step
                 self.reducer.reduce(ranges, lanes, issue_on=issue)
             self.reducer.finish()
+        if "grad_norm" in ops:
+            ops["grad_norm"](st)
         ops["adam"](st)
 
     def __call__(self, x_slow, x_fast, labels, slow_t_index=None) -> torch.Tensor:
@@ -767,6 +836,9 @@ class Trainer:
         if eng is None:                                  # res2d: a plain torch module, the reference's own five lines
             from .res2d import TorchStep
             assert self.world == 1, "res2d is single-process host plumbing"
+            if self._optim_kwargs():
+                raise ValueError("MODEL.LR_SCHEDULE / WEIGHT_DECAY / CLIP_GRAD_NORM need the engine's optimizer launch: MODEL.NAME "
+                                 "res2d with the torch backend is host plumbing (torch.optim.Adam); use RES2D_BACKEND = 'engine'")
             self.step = TorchStep(self.model, lr=cfg.MODEL.LR)
         else:
             reducer = sdist.GradReducer(eng.G, bucket_mb=cfg.DIST.BUCKET_MB) if self.world > 1 else None
@@ -778,8 +850,22 @@ class Trainer:
     def _model_manager(self, cfg, device, backend):
         return ModelManager(cfg, device=device, backend=backend)
 
+    def steps_per_epoch(self) -> int:
+        """optimizer steps of one train_epoch: the resident plan's batches, else len(train_loader)"""
+        resident = getattr(self, "resident", None)
+        if resident is not None:
+            n, bs = len(resident.train_set), int(resident.batch_size)
+            return max(n // bs if resident.drop_last else -(-n // bs), 1)
+        return max(len(self.train_loader), 1)
+
+    def _optim_kwargs(self) -> dict:
+        """MODEL.LR_SCHEDULE, WEIGHT_DECAY*, CLIP_GRAD_NORM as TrainStep keywords ({} at the defaults); the table spans
+        MAX_EPOCH * steps_per_epoch() steps and is indexed by the optimizer's own step count (schedule.py)"""
+        from .schedule import optim_kwargs
+        return optim_kwargs(self.cfg, self.steps_per_epoch)
+
     def _make_step(self, eng, use_graph, reducer):
-        return TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer)
+        return TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer, **self._optim_kwargs())
 
     def _reference_datasets(self):
         try:
@@ -909,6 +995,9 @@ class Trainer:
             correct, seen = sum(p[1] for p in parts), sum(p[2] for p in parts)
         print(f'loss_avg: {round(loss_avg, 3)}')
         print(f'Train Accuracy: {round(correct / max(seen, 1), 3)}. ({correct} / {seen})')
+        if getattr(self.step, "hp", False):              # the scheduled step: its last rate and gradient norm, read once an epoch
+            gn = self.step.grad_norm
+            print(f'lr: {self.step.last_lr():.6g}' + ('' if gn is None else f', grad_norm: {float(gn[0]):.4g}'))
         return loss_avg, correct / max(seen, 1)
 
     def train(self):
