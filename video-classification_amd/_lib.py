@@ -242,6 +242,19 @@ class _OptimHp(C.Structure):
                 ("decay_count", C.c_int64), ("clip_coef", C.c_void_p), ("weight_decay", C.c_float), ("reserved0", C.c_int32)]
 
 
+class _GroupSeg(C.Structure):
+    """include/sfk_groups.h sfk_group_seg: arena elements [begin, end) of one parameter group"""
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("tile0", C.c_int64), ("group", C.c_int32), ("decay", C.c_int32)]
+
+
+class _GroupsHp(C.Structure):
+    """include/sfk_groups.h sfk_groups_hp: the segment table (device copy and host mirror), the per-group rate rows and
+    weight decays, the launch's decay mode and clipping coefficient"""
+    _fields_ = [("struct_size", C.c_uint32), ("decay_mode", C.c_int32), ("segs", C.c_void_p), ("segs_host", C.c_void_p),
+                ("nsegs", C.c_int32), ("ngroups", C.c_int32), ("lr_rows", C.c_void_p), ("lr_len", C.c_int64),
+                ("weight_decay", C.c_void_p), ("clip_coef", C.c_void_p)]
+
+
 class _PoolDesc(C.Structure):
     """include/sfk_pool.h sfk_pool_desc: byte (f, y, x, ch) of the frame pool at
     pool[f*frame_stride + y*row_stride + x*pixel_pitch + c0 + ch]; clip n, time t of out is frame index[n][t] through lut"""
@@ -468,7 +481,17 @@ SIGNATURES_OPTIM = {
     "sfk_grad_norm_parts": [_I64],
     "sfk_grad_norm": [_PF, _I64, _F, _F, _PV, _PF, _PV],
 }
-_RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
+# include/sfk_groups.h: the optimizer step and the gradient norm over parameter groups and frozen ranges
+GROUPS_ABI_VERSION = 1     # include/sfk_groups.h SFK_GROUPS_ABI_VERSION
+GROUPS_MAX_SEGS, GROUPS_MAX_GROUPS = 2048, 64   # include/sfk_groups.h SFK_GROUPS_MAX_*
+SIGNATURES_GROUPS = {
+    "sfk_groups_abi_version": [],
+    "sfk_groups_prepare": [_PV, _I32, _I64, _I32],
+    "sfk_adam_groups": [_PF, _PF, _PF, _PF, _I64, C.POINTER(_GroupsHp), _F, _F, _F, _F, _PV, _PV, _I32, _PV],
+    "sfk_sgd_groups": [_PF, _PF, _PF, _I64, C.POINTER(_GroupsHp), _F, _F, _I32, _F, _PV, _PV, _I32, _PV],
+    "sfk_grad_norm_groups": [_PF, _I64, _PV, _PV, _I32, _F, _F, _PV, _PF, _PV],
+}
+_RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_groups_prepare": C.c_int64, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
 
@@ -545,6 +568,19 @@ def new_optim_hp() -> "_OptimHp":
     return d
 
 
+class GroupTable:
+    """A segment table of include/sfk_groups.h, ready to launch: the host mirror (a ctypes array with tile0 filled by
+    sfk_groups_prepare), its device copy, and the per-group weight decays on the device.  Built once (HipBackend.group_table)
+    and shared by the update and the norm launch that use it."""
+
+    def __init__(self, segments, host, dev, wds, ngroups, count):
+        self.segments, self.host, self.dev, self.wds, self.ngroups, self.count = segments, host, dev, wds, ngroups, count
+
+    @property
+    def nsegs(self) -> int:
+        return len(self.segments)
+
+
 def new_resize_desc() -> "_ResizeDesc":
     d = _ResizeDesc()
     d.struct_size = C.sizeof(_ResizeDesc)
@@ -570,7 +606,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib = C.CDLL(path)
     for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL,
                   SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL, SIGNATURES_ROI_RAGGED, SIGNATURES_U8STEM_POOL,
-                  SIGNATURES_OPTIM):
+                  SIGNATURES_OPTIM, SIGNATURES_GROUPS):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -599,6 +635,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk u8stem_pool ABI version mismatch: library {lib.sfk_u8stem_pool_abi_version()}, binding {U8STEM_POOL_ABI_VERSION}")
     if lib.sfk_optim_abi_version() != OPTIM_ABI_VERSION:
         raise SfkError(f"libsfk optim ABI version mismatch: library {lib.sfk_optim_abi_version()}, binding {OPTIM_ABI_VERSION}")
+    if lib.sfk_groups_abi_version() != GROUPS_ABI_VERSION:
+        raise SfkError(f"libsfk groups ABI version mismatch: library {lib.sfk_groups_abi_version()}, binding {GROUPS_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -1135,6 +1173,68 @@ class HipBackend:
         assert out.dtype == torch.float32 and out.numel() >= 2
         return self._plain("sfk_grad_norm", _ptr(g), count, gscale, max_norm, _ptr(partials), _ptr(out),
                            keep=(g, partials, out))
+
+    def group_table(self, segments, weight_decays, count: int, device) -> GroupTable:
+        """segments: sorted, disjoint (begin, end, group, decay) over [0, count); weight_decays: one per group (already
+        wd * wd_mult).  Validates on the host (sfk_groups_prepare), fills tile0 and uploads the table once."""
+        segments = [tuple(int(x) for x in s) for s in segments]
+        n, ng = len(segments), len(weight_decays)
+        host = (_GroupSeg * max(n, 1))()
+        for k, (b, e, grp, dec) in enumerate(segments):
+            host[k] = _GroupSeg(b, e, 0, grp, 1 if dec else 0)
+        if n > GROUPS_MAX_SEGS:
+            raise SfkError(f"sfk_groups_prepare: {n} segments, the cap is {GROUPS_MAX_SEGS}")
+        tiles = int(self.lib.sfk_groups_prepare(C.addressof(host), n, count, ng))
+        if tiles < 0:
+            _check(tiles, "sfk_groups_prepare")
+        raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8)[:n * C.sizeof(_GroupSeg)]
+        dev = raw.to(device) if n else None
+        wds = torch.tensor([float(w) for w in weight_decays], dtype=torch.float32).to(device)
+        return GroupTable(segments, host, dev, wds, ng, count)
+
+    @staticmethod
+    def _groups_hp(table: GroupTable, lr_rows, decay_mode, clip_coef):
+        assert lr_rows.dtype == torch.float32 and lr_rows.is_contiguous() and lr_rows.dim() == 2
+        assert lr_rows.shape[0] == table.ngroups
+        assert clip_coef is None or clip_coef.dtype == torch.float32
+        d = _GroupsHp()
+        d.struct_size = C.sizeof(_GroupsHp)
+        d.decay_mode = DECAY_MODES[decay_mode] if isinstance(decay_mode, str) else int(decay_mode)
+        d.segs, d.segs_host = _ptr(table.dev), (C.addressof(table.host) if table.nsegs else None)
+        d.nsegs, d.ngroups = table.nsegs, table.ngroups
+        d.lr_rows, d.lr_len = lr_rows.data_ptr(), lr_rows.shape[1]
+        d.weight_decay, d.clip_coef = table.wds.data_ptr(), _ptr(clip_coef)
+        return d
+
+    def adam_groups(self, p, g, m, v, count, table: GroupTable, lr_rows, b1, b2, eps, gscale, step, shadow=None,
+                    decay_mode="none", clip_coef=None):
+        """sfk_adam_groups (include/sfk_groups.h): per segment [b, e) of group j the bits of adam_hp on that slice with
+        lr_table = lr_rows[j], weight_decay = table's j-th, decay_count = decay ? e - b : 0; uncovered elements are frozen"""
+        assert table.count == count
+        sd = _DT[shadow.dtype] if shadow is not None else SFK_F32
+        d = self._groups_hp(table, lr_rows, decay_mode, clip_coef)
+        return self._plain("sfk_adam_groups", _ptr(p), _ptr(g), _ptr(m), _ptr(v), count, C.byref(d), b1, b2, eps, gscale,
+                           _ptr(step), _ptr(shadow), sd, keep=(d, table, p, g, m, v, step, shadow, lr_rows, clip_coef))
+
+    def sgd_groups(self, p, g, buf, count, table: GroupTable, lr_rows, momentum, dampening, nesterov, gscale, step,
+                   shadow=None, decay_mode="none", clip_coef=None):
+        """sfk_sgd_groups (include/sfk_groups.h): sgd_hp per segment, as adam_groups"""
+        assert table.count == count
+        sd = _DT[shadow.dtype] if shadow is not None else SFK_F32
+        d = self._groups_hp(table, lr_rows, decay_mode, clip_coef)
+        return self._plain("sfk_sgd_groups", _ptr(p), _ptr(g), _ptr(buf), count, C.byref(d), momentum, dampening,
+                           1 if nesterov else 0, gscale, _ptr(step), _ptr(shadow), sd,
+                           keep=(d, table, p, g, buf, step, shadow, lr_rows, clip_coef))
+
+    def grad_norm_groups(self, g, count, table: GroupTable, gscale, max_norm, partials, out):
+        """sfk_grad_norm_groups (include/sfk_groups.h): grad_norm over the covered elements only, the bits of grad_norm on a
+        copy of g with the uncovered elements zeroed"""
+        assert table.count == count
+        assert partials.dtype == torch.float64 and partials.numel() >= self.grad_norm_parts(count)
+        assert out.dtype == torch.float32 and out.numel() >= 2
+        return self._plain("sfk_grad_norm_groups", _ptr(g), count, _ptr(table.dev),
+                           C.addressof(table.host) if table.nsegs else None, table.nsegs, gscale, max_norm, _ptr(partials),
+                           _ptr(out), keep=(table, g, partials, out))
 
     def roi_resize(self, src, lut, box, out, antialias: bool, crop=None, pad: int = 0, c_off: int = 0):
         """sfk_roi_resize (include/sfk_v2.h): src (N,T,H,W,C) uint8, any byte strides (HWC or a permuted planar view);

@@ -2,55 +2,10 @@
 // and a clipping coefficient) and sfk_grad_norm (the global gradient norm behind that coefficient).  One streaming pass
 // each, built like sgd.hip: 16-byte loads and stores where every arena pointer of the slice is 16-byte aligned, a scalar
 // path otherwise and for the last count % 4 elements, a grid-stride loop under a grid cap.  Every product and sum is rounded
-// on its own (__fmul_rn / __fadd_rn), in torch's operation order, so nothing is contracted into an FMA.
-#include "sfk_common.h"
-#include "sfk_optim.h"
+// on its own (rn_mul / rn_add of optim_elem.h, compiled with contraction off), in torch's operation order: nothing becomes an FMA.
+#include "optim_elem.h"
 
 namespace {
-
-constexpr int kGridCap = 16384;          // workgroups of the update kernels (x 1024 elements per trip)
-constexpr int64_t kNormRowElems = 4096;  // elements per partial row below the row cap
-
-__global__ void optim_step_inc_kernel(int64_t* step) { step[0] += 1; }
-
-// the by-value part of sfk_optim_hp, as the kernels take it
-struct HpArgs {
-  const float* lr_table;
-  int64_t lr_len;
-  int64_t decay_count;
-  const float* clip_coef;
-  float wd;
-  int mode;
-};
-
-// uniform per workgroup: every lane reads the same addresses
-__device__ __forceinline__ float hp_lr(const HpArgs& h, int64_t s) {
-  int64_t i = s < 1 ? 1 : s;
-  if (i > h.lr_len) i = h.lr_len;
-  return h.lr_table[i - 1];
-}
-
-__device__ __forceinline__ float hp_grad(float g, float p, float gscale, bool clip, float coef, bool l2, float wd) {
-  float gs = __fmul_rn(g, gscale);
-  if (clip) gs = __fmul_rn(gs, coef);
-  if (l2) gs = __fadd_rn(gs, __fmul_rn(wd, p));
-  return gs;
-}
-
-struct AdamConst {
-  float b1, b2, one_m_b1, one_m_b2, eps, neg_step_size, inv_sqrt_bc2, decay_mul;
-};
-
-__device__ __forceinline__ void adam_hp_one(float& p, float g, float& m, float& v, bool decay, const AdamConst& c,
-                                            const HpArgs& h, float gscale, bool clip, float coef) {
-  const float gs = hp_grad(g, p, gscale, clip, coef, decay && h.mode == SFK_DECAY_L2, h.wd);
-  float pp = p;
-  if (decay && h.mode == SFK_DECAY_DECOUPLED) pp = __fmul_rn(pp, c.decay_mul);
-  m = __fadd_rn(__fmul_rn(c.b1, m), __fmul_rn(c.one_m_b1, gs));
-  v = __fadd_rn(__fmul_rn(c.b2, v), __fmul_rn(__fmul_rn(c.one_m_b2, gs), gs));
-  const float den = __fadd_rn(__fmul_rn(__fsqrt_rn(v), c.inv_sqrt_bc2), c.eps);
-  p = __fadd_rn(pp, __fmul_rn(c.neg_step_size, __fdiv_rn(m, den)));
-}
 
 template <typename S>
 __global__ __launch_bounds__(256) void adam_hp_kernel(float* __restrict__ p, const float* __restrict__ g,
@@ -69,7 +24,7 @@ __global__ __launch_bounds__(256) void adam_hp_kernel(float* __restrict__ p, con
   }
   __syncthreads();
   AdamConst c;
-  c.b1 = b1, c.b2 = b2, c.one_m_b1 = __fadd_rn(1.f, -b1), c.one_m_b2 = __fadd_rn(1.f, -b2), c.eps = eps;
+  c.b1 = b1, c.b2 = b2, c.one_m_b1 = rn_add(1.f, -b1), c.one_m_b2 = rn_add(1.f, -b2), c.eps = eps;
   c.neg_step_size = sc[0], c.inv_sqrt_bc2 = sc[1], c.decay_mul = sc[2];
   const bool clip = h.clip_coef != nullptr;
   const float coef = clip ? h.clip_coef[0] : 1.f;
@@ -106,18 +61,6 @@ __global__ __launch_bounds__(256) void adam_hp_kernel(float* __restrict__ p, con
   }
 }
 
-__device__ __forceinline__ float sgd_hp_one(float p, float g, float* buf, bool first, bool decay, float neg_lr, float mom,
-                                            float one_m_damp, bool nesterov, const HpArgs& h, float gscale, bool clip,
-                                            float coef) {
-  const float gs = hp_grad(g, p, gscale, clip, coef, decay, h.wd);
-  float d = gs;
-  if (buf) {
-    const float b = first ? gs : __fadd_rn(__fmul_rn(mom, *buf), __fmul_rn(one_m_damp, gs));
-    *buf = b;
-    d = nesterov ? __fadd_rn(gs, __fmul_rn(mom, b)) : b;
-  }
-  return __fadd_rn(p, __fmul_rn(neg_lr, d));
-}
 
 template <typename S>
 __global__ __launch_bounds__(256) void sgd_hp_kernel(float* __restrict__ p, const float* __restrict__ g,
@@ -161,17 +104,6 @@ __global__ __launch_bounds__(256) void sgd_hp_kernel(float* __restrict__ p, cons
   }
 }
 
-// fixed-order tree over the 256 lanes' doubles: the same association on every run
-__device__ __forceinline__ double block_sum_256(double x, double* red) {
-  red[threadIdx.x] = x;
-  __syncthreads();
-#pragma unroll
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // row b = the sum over the elements its 256 lanes meet in the grid-stride loop, 4 consecutive elements per lane and trip
 __global__ __launch_bounds__(256) void grad_norm_rows_kernel(const float* __restrict__ g, int64_t count, float gscale,
@@ -185,13 +117,13 @@ __global__ __launch_bounds__(256) void grad_norm_rows_kernel(const float* __rest
       const float* gp = reinterpret_cast<const float*>(&gv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const double x = (double)__fmul_rn(gp[j], gscale);
+        const double x = (double)rn_mul(gp[j], gscale);
         acc = fma(x, x, acc);
       }
     } else {
       const int64_t e1 = i + 4 < count ? i + 4 : count;
       for (int64_t e = i; e < e1; ++e) {
-        const double x = (double)__fmul_rn(g[e], gscale);
+        const double x = (double)rn_mul(g[e], gscale);
         acc = fma(x, x, acc);
       }
     }
@@ -200,31 +132,6 @@ __global__ __launch_bounds__(256) void grad_norm_rows_kernel(const float* __rest
   if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
-__global__ __launch_bounds__(256) void grad_norm_fold_kernel(const double* __restrict__ partials, int rows, float max_norm,
-                                                             float* __restrict__ out) {
-  __shared__ double red[256];
-  double acc = 0.0;
-  for (int r = threadIdx.x; r < rows; r += 256) acc += partials[r];
-  const double t = block_sum_256(acc, red);
-  if (threadIdx.x == 0) {
-    const float norm = (float)sqrt(t);
-    const float c = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));
-    out[0] = norm;
-    out[1] = c > 1.f ? 1.f : c;          // a NaN coefficient stays NaN (torch.clamp)
-  }
-}
-
-inline unsigned update_grid(int64_t count) {
-  int64_t b = (count + 1023) / 1024;
-  if (b > kGridCap) b = kGridCap;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
-inline int norm_rows(int64_t count) {
-  int64_t r = (count + kNormRowElems - 1) / kNormRowElems;
-  if (r > SFK_GRAD_NORM_MAX_PARTS) r = SFK_GRAD_NORM_MAX_PARTS;
-  return (int)(r < 1 ? 1 : r);
-}
 
 inline bool hp_ok(const sfk_optim_hp* hp, int64_t count, int max_mode) {
   if (!hp || hp->struct_size != sizeof(sfk_optim_hp)) return false;

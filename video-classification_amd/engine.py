@@ -196,6 +196,7 @@ class Engine:
         self._layers: Dict[str, _Layer] = {}
         self._bufs: Dict[str, torch.Tensor] = {}
         self._plans: Dict[tuple, Plan] = {}
+        self.fresh_keys = None                      # keys a pretrained load left untouched (ModelManager.load_pretrained); None = all of them
         self._build_params(seed)
         self.max_parts = _max_parts() if getattr(self.be, "name", "") == "hip" else 1024
         self.two_streams = True           # slow / fast pathway on two HIP streams (see OpList)
@@ -1416,3 +1417,65 @@ class Engine:
         tail = self.be.adam_hp(self.P.data[:cut], self.G[:cut], self.adam_m[:cut], self.adam_v[:cut], cut, lr_table,
                                betas[0], betas[1], eps, grad_scale, self.adam_step_tail, None, decay_count=min(dc, cut), **kw)
         return main, tail
+
+    # ---- parameter groups and frozen layers: selectors -> the arena segments of include/sfk_groups.h (HipBackend.group_table,
+    #      adam_groups / sgd_groups / grad_norm_groups).  Nothing above uses them: TrainStep knows no groups yet.
+    def param_tensors(self) -> List[Tuple[str, int, int]]:
+        """(state_dict key, arena offset, elements with the alignment padding behind the tensor) of every parameter, in
+        arena order: conv filters | FC weight | FC bias | per-layer gamma, beta (_build_params).  The ranges tile the arena."""
+        out = [(L.cb.conv_key + ".weight", L.w_off, round_up(L.w_numel, self.vec)) for L in self.layers]
+        hk = self.wiring.head_key
+        out.append((hk + ".weight", self.fc_w_off, self.fc_b_off - self.fc_w_off))
+        out.append((hk + ".bias", self.fc_b_off, self.layers[0].g_off - self.fc_b_off))
+        for L in self.layers:
+            pad = round_up(L.c, self.vec)
+            out.append((L.cb.norm_key + ".weight", L.g_off, pad))
+            out.append((L.cb.norm_key + ".bias", L.b_off, pad))
+        return out
+
+    def _state_keys(self) -> List[str]:
+        """the names state_dict() emits, without building it"""
+        keys = [k for k, _, _ in self.param_tensors()]
+        for L in self.layers:
+            keys += [L.cb.norm_key + s for s in (".running_mean", ".running_var", ".num_batches_tracked")]
+        return keys + list(self.dead)
+
+    def _matcher(self, selector: str, keys: List[str]):
+        """selector -> predicate over keys.  A checkpoint-key prefix ('blocks.1.'), or '@fresh' / '@pretrained': the keys a
+        pretrained load left untouched / filled (fresh_keys; None = nothing was loaded, every key is fresh).  A prefix that
+        matches no key of state_dict() is a ValueError; the two words may match nothing."""
+        if selector in ("@fresh", "@pretrained"):
+            fresh = set(keys) if self.fresh_keys is None else set(self.fresh_keys)
+            want = selector == "@fresh"
+            return lambda k: (k in fresh) == want
+        if not isinstance(selector, str) or not selector or selector.startswith("@"):
+            raise ValueError(f"parameter selector {selector!r}: a state_dict key prefix, '@fresh' or '@pretrained'")
+        if not any(k.startswith(selector) for k in keys):
+            raise ValueError(f"parameter selector {selector!r} matches no key of state_dict()")
+        return lambda k: k.startswith(selector)
+
+    def frozen_param_keys(self, freeze) -> frozenset:
+        keys = self._state_keys()
+        ms = [self._matcher(s, keys) for s in freeze]
+        return frozenset(k for k, _, _ in self.param_tensors() if any(m(k) for m in ms))
+
+    def param_segments(self, groups=(), freeze=(), decay_scope: str = "weights") -> List[Tuple[int, int, int, int]]:
+        """Sorted, disjoint arena ranges (begin, end, group, decay) for sfk_*_groups.  groups: selectors in priority order, the
+        first that matches a tensor wins and puts it into group i + 1; unmatched tensors are group 0 (multipliers 1).  A
+        tensor matched by any selector of `freeze` appears in no segment (frozen).  The alignment padding travels with its
+        tensor; adjacent ranges with the same group and decay flag merge.  decay: decay_count(decay_scope)'s rule."""
+        dc = self.decay_count(decay_scope)
+        keys = self._state_keys()
+        gm = [self._matcher(s, keys) for s in groups]
+        frozen = self.frozen_param_keys(freeze)
+        segs: List[List[int]] = []
+        for k, off, n in self.param_tensors():
+            if k in frozen or n == 0:
+                continue
+            grp = next((i + 1 for i, m in enumerate(gm) if m(k)), 0)
+            dec = 1 if off < dc else 0
+            if segs and segs[-1][1] == off and segs[-1][2] == grp and segs[-1][3] == dec:
+                segs[-1][1] = off + n
+            else:
+                segs.append([off, off + n, grp, dec])
+        return [tuple(s) for s in segs]

@@ -319,7 +319,7 @@ class ModelManager(_train.ModelManager):
         ckpt = Path("pretrained", "SLOWFAST_8x8_R50.pyth")          # :741-759 (absent offline: random init)
         if ckpt.is_file():
             state = torch.load(ckpt, map_location="cpu", weights_only=True)["model_state"]
-            model.load_state_dict(self.delete_mismatch(state), strict=False)
+            self.load_pretrained(model, self.delete_mismatch(state))
         else:
             print(f"warning: {ckpt} not found, training from the reference init scheme")
         return model

@@ -442,7 +442,7 @@ class ModelManager:
             state = torch.load(ckpt, map_location="cpu", weights_only=True)["model_state"]
             if tuple(state['blocks.6.proj.weight'].shape) != (self.cfg.CHALEARN.NUM_CLASS, 2304):
                 del state['blocks.6.proj.weight'], state['blocks.6.proj.bias']
-            model.load_state_dict(state, strict=False)
+            self.load_pretrained(model, state)
         return model
 
     def _prepare_canonical_data(self, batch):
@@ -450,6 +450,19 @@ class ModelManager:
         pathway's PackPathway gather (model.slow_t_index) happens inside its stem kernel."""
         x = torch.permute(self._float_clip(batch), [0, 2, 1, 3, 4])[:, 0:3]
         return [x, x], self._h2d(batch['label'])
+
+    fresh_keys = None          # the model keys the pretrained load left untouched (load_pretrained); None: nothing was loaded
+
+    def load_pretrained(self, model, state):
+        """load_state_dict(state, strict=False), and record which keys it left untouched: the selectors '@fresh' and
+        '@pretrained' of Engine.param_segments resolve against them.  Without a checkpoint file nothing is loaded and every
+        key is fresh."""
+        res = model.load_state_dict(state, strict=False)
+        self.fresh_keys = set(res.missing_keys)
+        eng = getattr(model, "engine", None)
+        if eng is not None:
+            eng.fresh_keys = set(self.fresh_keys)
+        return res
 
     @staticmethod
     def delete_mismatch(state_dict):
@@ -468,7 +481,7 @@ class ModelManager:
         ckpt = Path('pretrained', 'SLOWFAST_8x8_R50.pyth')          # train.py:116 (absent offline: random init)
         if ckpt.is_file():
             state = torch.load(ckpt, map_location="cpu", weights_only=True)["model_state"]
-            model.load_state_dict(self.delete_mismatch(state), strict=False)
+            self.load_pretrained(model, self.delete_mismatch(state))
         else:
             print(f'warning: {ckpt} not found, training from the reference init scheme')
         return model
