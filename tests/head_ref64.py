@@ -483,7 +483,7 @@ def check_adam(be, dev, count, step0, gscale, shadow_dtype, with_torch: bool = T
 
 
 def check_adam_split(be, dev, count, cut, step0, gscale, shadow_dtype=None, seed_no: int = 0) -> List:
-    """[cut:] with the step counter, then [:cut] with a scratch counter set to step - 1 (Engine.adam_split_ops as TrainStep
+    """[cut:] with the step counter, then [:cut] with a scratch counter set to step - 1 (optim.Optimizer.split_ops as TrainStep
     drives it), bit for bit against the single launch from the same state"""
     gen = torch.Generator(device=dev).manual_seed(500 + seed_no + count % 1000 + cut)
     p0, g0, m0, v0, _ = adam_inputs(count, step0, gen)

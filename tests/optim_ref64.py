@@ -225,7 +225,7 @@ def check_grad_norm(be, dev, count, kind="randn", off=0, gscale=0.5, max_norm=No
 
 def check_adam_hp_split(be, dev, count, cut, dc, step0, mode, clip=False, gscale=0.5, seed_no=0) -> List:
     """[cut:] with the step counter, then [:cut] with a scratch counter set to step - 1, each with its slice-relative
-    decay_count (Engine.adam_hp_split_ops as TrainStep drives it), bit for bit against the single launch"""
+    decay_count (optim.Optimizer.split_ops as TrainStep drives it), bit for bit against the single launch"""
     p0, g0, m0, v0, _ = _hp_inputs(count, step0, dev, 1000 + seed_no + count % 1000 + cut)
     st = _stream(dev)
     (b1, b2), eps = ADAM_BETAS, ADAM_EPS

@@ -312,3 +312,62 @@ def test_trainstep_adamw_steps_match_the_float64_restatement(clip):
                H.Exact(f"counter step {s}", int(eng.adam_step[0]) == s, "")]
         vs.append(H.Exact(f"rate step {s}", step.last_lr() == table32[s - 1], f"{step.last_lr()}"))
     report(vs)
+
+
+@pytest.mark.parametrize("route", ["default", "table-decoupled", "clipped"])
+def test_trainstep_issues_the_contract_launches(route, monkeypatch):
+    """which optimizer launches two eager bf16 steps of the depth-18 model issue through TrainStep on HipBackend, derived
+    from the contract, not recorded: without clipping the split pair -- [cut, n) with adam_step, then
+    [0, cut) with adam_step_tail, cut = the plan's tail_cut, each with its slice-relative decay_count under the hp route;
+    with clipping the norm, then ONE launch over [0, n) that reads the coefficient, and no pair"""
+    from optim_trace import LaunchTrace
+    from video_classification_amd.train import TrainStep
+    torch.manual_seed(7)
+    m = _mini(torch.bfloat16)
+    eng = m.engine
+    assert eng.two_streams and eng.options.split_adam
+    tr = LaunchTrace(eng, monkeypatch.setattr)
+    table = [1e-3, 5e-4, 2.5e-4]
+    kw = {"default": {}, "table-decoupled": dict(lr_table=table, weight_decay=WD, decay_mode="decoupled"),
+          "clipped": dict(clip_grad_norm=MAX_NORM)}[route]
+    step = TrainStep(eng, lr=1e-3, **kw)
+    x, labels = _clips(seed=11)
+    xd, yd = [t.to(DEV) for t in x], labels.to(DEV)
+    m.train()
+    for _ in range(2):
+        step(xd[0], xd[1], yd)
+    torch.cuda.synchronize()
+    (pl,) = eng._plans.values()
+    (ent,) = step._cache.values()
+    ops, n, dc, cut = ent["ops"], eng.arena_numel, eng.fc_b_off, pl.tail_cut[1]
+    assert 0 < cut < dc < n
+    built = tr.built
+    ran = [built[i] for i in tr.ran]
+    name = "adam" if route == "default" else "adam_hp"
+    assert all(b["call"] == name for b in built if b["call"] != "grad_norm")
+
+    def over(b, lo, hi, counter):
+        """the launch b updates [lo, hi) of P, G, m and v with that counter"""
+        want = [dict(arena=a, offset=lo, len=hi - lo) for a in ("P", "G", "adam_m", "adam_v")]
+        return b["args"][:5] == want + [hi - lo] and b["args"][10] == dict(arena=counter, offset=0, len=1)
+
+    if route == "clipped":
+        assert "adam_main" not in ops and "adam_tail" not in ops and "grad_norm" in ops
+        assert [b["call"] for b in ran] == ["grad_norm", "adam_hp"] * 2
+        norm, upd = ran[0], ran[1]
+        assert ran[2] is norm and ran[3] is upd
+        assert norm["args"][0] == dict(arena="G", offset=0, len=n) and norm["args"][5] == dict(arena="grad_norm", offset=0, len=2)
+        assert over(upd, 0, n, "adam_step") and upd["kwargs"]["clip_coef"] == dict(arena="grad_norm", offset=1, len=1)
+        assert int(eng.adam_step[0]) == 2 and step.grad_norm is eng.grad_norm
+        return
+    assert "adam_main" in ops and "adam_tail" in ops and "grad_norm" not in ops
+    assert [b["call"] for b in ran] == [name] * 4
+    main, tail = ran[0], ran[1]
+    assert ran[2] is main and ran[3] is tail
+    assert over(main, cut, n, "adam_step") and over(tail, 0, cut, "adam_step_tail")
+    if route == "table-decoupled":
+        for b, count in ((main, min(max(dc - cut, 0), n - cut)), (tail, min(dc, cut))):
+            assert b["kwargs"] == dict(weight_decay=WD, decay_mode="decoupled", decay_count=count, clip_coef="none")
+            assert b["args"][5] == dict(table=torch.tensor(table, dtype=torch.float32).tolist())
+        assert step.last_lr() == torch.tensor(table, dtype=torch.float32).tolist()[1]
+    assert int(eng.adam_step[0]) == int(eng.adam_step_tail[0]) == 2

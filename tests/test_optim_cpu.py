@@ -497,7 +497,8 @@ def test_trainstep_warmup_cosine_sgd_l2_clipping_equals_torch():
 
 
 def test_engine_split_pair_equals_the_single_launch_bit_for_bit():
-    """Engine.adam_hp_split_ops as TrainStep drives it (main, counter - 1 into the tail counter, tail) against adam_hp_ops"""
+    """optim.Optimizer.split_ops as TrainStep drives it (main, counter - 1 into the tail counter, tail) against update_ops"""
+    from video_classification_amd.optim import Optimizer
     a, b = _mini(seed=1), _mini(seed=1)
     gen = torch.Generator().manual_seed(9)
     table = torch.tensor(O.LR_TABLE)
@@ -505,14 +506,14 @@ def test_engine_split_pair_equals_the_single_launch_bit_for_bit():
         kw = dict(weight_decay=O.WD, decay_mode=mode, decay_scope=scope)
         cut = a.engine.layers[1].w_off                            # the first layer's filters | the rest
         assert 0 < cut < a.engine.fc_b_off and cut % 4 == 0
-        one = a.engine.adam_hp_ops(a.engine.lr_table(table), grad_scale=0.5, **kw)
-        main, tail = b.engine.adam_hp_split_ops(cut, b.engine.lr_table(table), grad_scale=0.5, **kw)
+        one = Optimizer(a.engine, lr_table=table, **kw).update_ops(grad_scale=0.5)
+        main, tail, set_tail = Optimizer(b.engine, lr_table=table, **kw).split_ops(cut, grad_scale=0.5)
         for _ in range(2):
             g = torch.randn(a.engine.arena_numel, generator=gen)
             a.engine.G.copy_(g); b.engine.G.copy_(g)
             one(0)
             main(0)
-            torch.sub(b.engine.adam_step, 1, out=b.engine.adam_step_tail)
+            set_tail()
             tail(0)
             for x, y in ((a.engine.P.data, b.engine.P.data), (a.engine.adam_m, b.engine.adam_m), (a.engine.adam_v, b.engine.adam_v)):
                 assert torch.equal(x.view(torch.int32), y.view(torch.int32)), mode

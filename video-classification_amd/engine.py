@@ -113,7 +113,7 @@ class Plan:
         self.grad_marks: List[Tuple[int, Tuple[int, int]]] = []
         self.stem_state: Dict[int, dict] = {}             # per pathway: buffers + slots of the ops bound to the clip tensors
         self.tail_cut: Optional[Tuple[int, int]] = None   # (index of the fast stem's filter-gradient op in bwd, arena offset
-                                                          #  below which only stem filters live): see Engine.adam_split_ops
+                                                          #  below which only stem filters live): see optim.Optimizer.split_ops
 
     def grad_segments(self, nseg: int) -> List[Tuple[int, int, List[Tuple[int, int]]]]:
         """Cut the backward schedule into nseg pieces [(op_begin, op_end, finished gradient ranges)], balanced by
@@ -282,9 +282,10 @@ class Engine:
         self.adam_m = None
         self.adam_v = None
         self.adam_step = None
+        self.adam_step_tail = None
         self.sgd_buf = None
         self.sgd_step = None
-        self.grad_norm = None          # (norm, clipping coefficient) of the last clipped step: grad_norm_ops
+        self.grad_norm = None          # (norm, clipping coefficient) of the last clipped step: optim_state
         self.grad_norm_parts = None
         # compute-precision copies of the filters: S = [cout][tap][cin] (forward, filter-gradient layout),
         # St = [cin][tap][cout] (data-gradient pass)
@@ -655,7 +656,7 @@ class Engine:
                 st["bwd_slot"] = len(pl.bwd)
                 if p == 1:
                     # the fast stem's filter gradient is the LAST kernel of the step (the trunk has finished ~0.4 ms before it):
-                    # TrainStep updates everything above `cut` beside it and only the stems' filters after it (adam_split_ops)
+                    # TrainStep updates everything above `cut` beside it and only the stems' filters after it (optim.Optimizer.split_ops)
                     cut = L.w_off + round_up(L.w_numel, self.vec)
                     if all(M.w_off >= cut or M.cb.is_stem for M in self.layers):
                         pl.tail_cut = (len(pl.bwd), cut)
@@ -1324,99 +1325,28 @@ class Engine:
         n, k = pl.logits.shape
         return self.be.softmax_ce(pl.logits, labels, n, k, gscale, pl.dlogits, loss_out, loss_sum, correct)
 
-    def _adam_state(self):
-        if self.adam_m is None:
-            self.adam_m = self._new(self.arena_numel)
-            self.adam_v = self._new(self.arena_numel)
-            self.adam_step = self._new(1, dtype=torch.int64)
-            # scratch counter of the split update's second launch (adam_split_ops): ONE tensor per engine, so that every cached
-            # TrainStep entry bakes in the same pointer and the value TrainStep writes before the launch is the one it reads
-            self.adam_step_tail = self._new(1, dtype=torch.int64)
-
-    def adam_ops(self, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, grad_scale: float = 1.0) -> Run:
-        self._adam_state()
-        return self.be.adam(self.P.data, self.G, self.adam_m, self.adam_v, self.arena_numel, lr, betas[0], betas[1],
-                            eps, grad_scale, self.adam_step, None)
-
-    def sgd_ops(self, lr: float, momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False,
-                grad_scale: float = 1.0) -> Run:
-        """torch.optim.SGD (no weight decay) over the whole arena in one sfk_sgd launch (include/sfk_v2.h), with a momentum
-        buffer the size of G and a step counter of its own, both allocated on first use.  Arena entries without a live
-        parameter (dead fusion weights, padding) keep G == 0 and therefore stay as they are, as in torch."""
-        if self.sgd_step is None:
-            self.sgd_buf = self._new(self.arena_numel)
-            self.sgd_step = self._new(1, dtype=torch.int64)
-        return self.be.sgd(self.P.data, self.G, self.sgd_buf, self.arena_numel, lr, momentum, dampening, nesterov,
-                           grad_scale, self.sgd_step, None)
-
-    def adam_split_ops(self, cut: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, grad_scale: float = 1.0):
-        """(main, tail): the same update as adam_ops in two launches -- arena [cut:] (increments the step counter) and [:cut]
-        (the stems' filters; sfk_adam increments the counter it is given, so the tail gets a scratch counter that
-        TrainStep sets to step - 1 first).  Element-wise identical to the single launch."""
-        self._adam_state()
+    def optim_state(self, kind: str):
+        """The optimizer state optim.Optimizer's launches read, allocated (zero) when a launch of that kind is first built; every
+        attribute is None until then.  ONE tensor per engine, so that every cached TrainStep entry bakes in the same pointers.
+        'adam': the moments, the step counter and the scratch counter of the split update's second launch; 'sgd': the momentum
+        buffer and a step counter of its own (arena entries without a live parameter keep G == 0 and stay as they are, as in
+        torch); 'grad_norm': (norm, clipping coefficient) of the last clipped step and sfk_grad_norm's partial rows."""
         n = self.arena_numel
-        main = self.be.adam(self.P.data[cut:], self.G[cut:], self.adam_m[cut:], self.adam_v[cut:], n - cut, lr, betas[0],
-                            betas[1], eps, grad_scale, self.adam_step, None)
-        tail = self.be.adam(self.P.data[:cut], self.G[:cut], self.adam_m[:cut], self.adam_v[:cut], cut, lr, betas[0],
-                            betas[1], eps, grad_scale, self.adam_step_tail, None)
-        return main, tail
+        if kind == "adam" and self.adam_m is None:
+            self.adam_m, self.adam_v = self._new(n), self._new(n)
+            self.adam_step, self.adam_step_tail = self._new(1, dtype=torch.int64), self._new(1, dtype=torch.int64)
+        elif kind == "sgd" and self.sgd_step is None:
+            self.sgd_buf, self.sgd_step = self._new(n), self._new(1, dtype=torch.int64)
+        elif kind == "grad_norm" and self.grad_norm is None:
+            self.grad_norm = self._new(2)
+            self.grad_norm_parts = self._new(self.be.grad_norm_parts(n), dtype=torch.float64)
 
-    # ---- the scheduled optimizer step (include/sfk_optim.h): the rate of step s read from a device table, weight decay and
-    #      gradient clipping.  adam_ops / sgd_ops / adam_split_ops above stay the default route and are not touched by these.
     def decay_count(self, scope: str) -> int:
         """arena elements [0, decay_count) decay: 'weights' = the conv filters and the FC weight (the arena is conv filters |
         FC weight | FC bias | BN gamma/beta, _build_params), 'all' = every parameter"""
         if scope not in ("weights", "all"):
             raise ValueError(f"decay_scope={scope!r}: 'weights' or 'all'")
         return self.fc_b_off if scope == "weights" else self.arena_numel
-
-    def lr_table(self, rates) -> torch.Tensor:
-        """the per-step rates as the device float32 table the hp launches index with their step counter"""
-        t = torch.as_tensor(rates, dtype=torch.float32).reshape(-1)
-        if t.numel() < 1:
-            raise ValueError("lr_table: at least one rate")
-        return t.to(self.device).contiguous()
-
-    def grad_norm_ops(self, max_norm: float, grad_scale: float = 1.0) -> Run:
-        """sfk_grad_norm over the whole gradient arena: self.grad_norm = (||G * grad_scale||_2, min(1, max_norm / (norm + 1e-6)))
-        on the device, float32[2]; the partial rows are allocated on first use"""
-        if self.grad_norm is None:
-            self.grad_norm = self._new(2)
-            self.grad_norm_parts = self._new(self.be.grad_norm_parts(self.arena_numel), dtype=torch.float64)
-        return self.be.grad_norm(self.G, self.arena_numel, grad_scale, max_norm, self.grad_norm_parts, self.grad_norm)
-
-    def adam_hp_ops(self, lr_table: torch.Tensor, betas=(0.9, 0.999), eps: float = 1e-8, grad_scale: float = 1.0,
-                    weight_decay: float = 0.0, decay_mode: str = "none", decay_scope: str = "weights", clip_coef=None) -> Run:
-        self._adam_state()
-        return self.be.adam_hp(self.P.data, self.G, self.adam_m, self.adam_v, self.arena_numel, lr_table, betas[0], betas[1],
-                               eps, grad_scale, self.adam_step, None, weight_decay=weight_decay, decay_mode=decay_mode,
-                               decay_count=self.decay_count(decay_scope), clip_coef=clip_coef)
-
-    def sgd_hp_ops(self, lr_table: torch.Tensor, momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False,
-                   grad_scale: float = 1.0, weight_decay: float = 0.0, decay_mode: str = "none",
-                   decay_scope: str = "weights", clip_coef=None) -> Run:
-        if self.sgd_step is None:
-            self.sgd_buf = self._new(self.arena_numel)
-            self.sgd_step = self._new(1, dtype=torch.int64)
-        return self.be.sgd_hp(self.P.data, self.G, self.sgd_buf, self.arena_numel, lr_table, momentum, dampening, nesterov,
-                              grad_scale, self.sgd_step, None, weight_decay=weight_decay, decay_mode=decay_mode,
-                              decay_count=self.decay_count(decay_scope), clip_coef=clip_coef)
-
-    def adam_hp_split_ops(self, cut: int, lr_table: torch.Tensor, betas=(0.9, 0.999), eps: float = 1e-8,
-                          grad_scale: float = 1.0, weight_decay: float = 0.0, decay_mode: str = "none",
-                          decay_scope: str = "weights"):
-        """(main, tail) as adam_split_ops: arena [cut:] through adam_step, [:cut] through adam_step_tail (both read the same
-        table entry, TrainStep sets the tail counter to step - 1 first), each with its slice-relative decay_count.  No
-        clipping here: the coefficient needs the last filter gradient, which the main launch does not wait for."""
-        self._adam_state()
-        n, dc = self.arena_numel, self.decay_count(decay_scope)
-        kw = dict(weight_decay=weight_decay, decay_mode=decay_mode, clip_coef=None)
-        main = self.be.adam_hp(self.P.data[cut:], self.G[cut:], self.adam_m[cut:], self.adam_v[cut:], n - cut, lr_table,
-                               betas[0], betas[1], eps, grad_scale, self.adam_step, None,
-                               decay_count=min(max(dc - cut, 0), n - cut), **kw)
-        tail = self.be.adam_hp(self.P.data[:cut], self.G[:cut], self.adam_m[:cut], self.adam_v[:cut], cut, lr_table,
-                               betas[0], betas[1], eps, grad_scale, self.adam_step_tail, None, decay_count=min(dc, cut), **kw)
-        return main, tail
 
     # ---- parameter groups and frozen layers: selectors -> the arena segments of include/sfk_groups.h (HipBackend.group_table,
     #      adam_groups / sgd_groups / grad_norm_groups).  Nothing above uses them: TrainStep knows no groups yet.

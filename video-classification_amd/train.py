@@ -31,6 +31,7 @@ from . import dist as sdist
 from .config import crop_resize_dict
 from .engine import Engine
 from .input_pipeline import STEM_CLIPS, h2d, is_pool_clips
+from .optim import Optimizer
 from .slowfast import init_my_slowfast
 
 
@@ -59,25 +60,11 @@ class TrainStep:
         > 0 runs sfk_grad_norm over the finished (reduced) gradients before one optimizer launch -- clip_grad_norm_(max_norm)
         -- and leaves (norm, coefficient) in self.grad_norm.  The optimizer state and the step count are not checkpointed
         (as in the reference), so a resumed run starts the table again."""
-        if optimizer not in ("adam", "sgd"):
-            raise ValueError(f"optimizer={optimizer!r}: 'adam' or 'sgd'")
-        if decay_mode not in ("none", "l2", "decoupled"):
-            raise ValueError(f"decay_mode={decay_mode!r}: 'none', 'l2' or 'decoupled'")
-        if decay_scope not in ("weights", "all"):
-            raise ValueError(f"decay_scope={decay_scope!r}: 'weights' or 'all'")
-        if weight_decay < 0 or clip_grad_norm < 0:
-            raise ValueError("weight_decay and clip_grad_norm must not be negative")
-        if weight_decay == 0 or decay_mode == "none":
-            weight_decay, decay_mode = 0.0, "none"
-        if optimizer == "sgd" and decay_mode == "decoupled":
-            raise ValueError("decay_mode='decoupled' needs optimizer='adam': torch has no decoupled SGD")
-        self.weight_decay, self.decay_mode, self.decay_scope = float(weight_decay), decay_mode, decay_scope
-        self.clip_grad_norm = float(clip_grad_norm)
-        self.hp = lr_table is not None or decay_mode != "none" or self.clip_grad_norm > 0     # the sfk_optim.h route
-        self.lr_table = engine.lr_table([lr] if lr_table is None else lr_table) if self.hp else None
-        self.grad_norm = None                             # device float32[2] (norm, coefficient) of the last step, with clipping
-        self.eng, self.lr, self.betas, self.eps = engine, lr, betas, eps
-        self.optimizer, self.momentum, self.dampening, self.nesterov = optimizer, momentum, dampening, nesterov
+        self.eng = engine
+        opt = self.opt = Optimizer(engine, optimizer, lr, betas, eps, momentum, dampening, nesterov, lr_table, weight_decay,
+                                   decay_mode, decay_scope, clip_grad_norm)      # validates the keywords; allocates no state
+        self.optimizer, self.momentum, self.hp, self.lr_table = opt.optimizer, opt.momentum, opt.hp, opt.lr_table
+        self.decay_mode, self.clip_grad_norm, self.last_lr = opt.decay_mode, opt.clip_grad_norm, opt.last_lr
         self.reducer = reducer
         self.world = reducer.world if reducer is not None else 1
         self.segmented = reducer is not None and reducer.active     # cut backward into segments and exchange them as they finish
@@ -106,64 +93,26 @@ class TrainStep:
         self.correct.zero_()
         self.steps = 0
 
+    grad_norm = property(lambda self: self.opt.grad_norm, doc="device float32[2] (norm, coefficient) of the last step; None "
+                         "until a clipped step has been built")
+
     def _build(self, pl, labels):
-        eng = self.eng
+        eng, opt = self.eng, self.opt
         gscale = self.reducer.grad_scale if self.reducer is not None else 1.0
-        if self.hp:
-            return self._build_hp(pl, labels, gscale)
-        if self.optimizer == "sgd":
-            opt = eng.sgd_ops(self.lr, self.momentum, self.dampening, self.nesterov, gscale)
-        else:
-            opt = eng.adam_ops(self.lr, self.betas, self.eps, gscale)
-        ops = dict(
-            loss=eng.loss_ops(pl, labels, self.loss, self.loss_sum, self.correct),
-            adam=opt,                 # the optimiser launch, Adam or SGD (the key bench.py's profiler reads)
-            zero_loss=eng.be.fill_zero(self.loss),
-            zero_grad=eng.be.fill_zero(eng.G),
-        )
-        # the optimiser beside the last kernel of the step (engine.Plan.tail_cut): eager four-lane single-rank Adam steps only
-        if (self.optimizer == "adam" and pl.tail_cut is not None and not self.segmented and not self.use_graph and eng.two_streams and eng.device.type == "cuda"
-                and eng.options.split_adam):
-            ops["adam_main"], ops["adam_tail"] = eng.adam_split_ops(pl.tail_cut[1], self.lr, self.betas, self.eps)
-        return ops
-
-    def _split_ok(self, pl) -> bool:
-        eng = self.eng
-        return (self.optimizer == "adam" and pl.tail_cut is not None and not self.segmented and not self.use_graph
-                and eng.two_streams and eng.device.type == "cuda" and eng.options.split_adam)
-
-    def _build_hp(self, pl, labels, gscale):
-        """the ops of _build with the optimizer launch of include/sfk_optim.h; `grad_norm` (clipping on) runs after the whole
-        backward, so the split update is used only without it"""
-        eng = self.eng
-        decay = dict(weight_decay=self.weight_decay, decay_mode=self.decay_mode, decay_scope=self.decay_scope)
         ops = dict(
             loss=eng.loss_ops(pl, labels, self.loss, self.loss_sum, self.correct),
             zero_loss=eng.be.fill_zero(self.loss),
             zero_grad=eng.be.fill_zero(eng.G),
         )
-        coef = None
-        if self.clip_grad_norm > 0:
-            ops["grad_norm"] = eng.grad_norm_ops(self.clip_grad_norm, gscale)
-            self.grad_norm = eng.grad_norm
-            coef = eng.grad_norm[1:2]
-        if self.optimizer == "sgd":
-            ops["adam"] = eng.sgd_hp_ops(self.lr_table, self.momentum, self.dampening, self.nesterov, gscale, clip_coef=coef, **decay)
-        else:
-            ops["adam"] = eng.adam_hp_ops(self.lr_table, self.betas, self.eps, gscale, clip_coef=coef, **decay)
-        if coef is None and self._split_ok(pl):
-            ops["adam_main"], ops["adam_tail"] = eng.adam_hp_split_ops(pl.tail_cut[1], self.lr_table, self.betas, self.eps, gscale, **decay)
+        if opt.clip_grad_norm > 0:
+            ops["grad_norm"] = opt.norm_ops(gscale)       # runs after the whole backward, so a clipped step is never split
+        ops["adam"] = opt.update_ops(gscale)              # the optimiser launch, Adam or SGD (the key bench.py's profiler reads)
+        # the optimiser beside the last kernel of the step (engine.Plan.tail_cut): eager four-lane single-rank Adam steps only.
+        # Not segmented, so the reducer's world, if there is one, is 1 and gscale is 1.
+        if (opt.can_split and pl.tail_cut is not None and not self.segmented and not self.use_graph and eng.two_streams
+                and eng.device.type == "cuda" and eng.options.split_adam):
+            ops["adam_main"], ops["adam_tail"], self._set_tail = opt.split_ops(pl.tail_cut[1], gscale)
         return ops
-
-    def last_lr(self) -> float:
-        """the rate the last optimizer step used (one device read: the step counter; the table is kept on the host side too)"""
-        eng = self.eng
-        if not self.hp:
-            return float(self.lr)
-        step = eng.sgd_step if self.optimizer == "sgd" else eng.adam_step
-        s = int(step[0]) if step is not None else 0
-        n = self.lr_table.numel()
-        return float(self.lr_table[min(max(s, 1), n) - 1])
 
     def _eager(self, pl, ops):
         eng = self.eng
@@ -184,7 +133,7 @@ class TrainStep:
                 ev.record(s_)
                 lanes[0].wait_event(ev)
             ops["adam_main"](st)
-            torch.sub(eng.adam_step, 1, out=eng.adam_step_tail)      # (the tail launch increments its counter: sfk_adam)
+            self._set_tail()                  # tail counter = step - 1, in the trunk's idle time (the tail launch increments it)
             eng._run_lanes(pl.bwd, i_wg)
             ops["adam_tail"](st)
             return
