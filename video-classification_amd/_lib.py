@@ -878,25 +878,25 @@ class HipBackend:
             _check(r, "sfk_stem_conv_tiles")
         return r
 
+    def _u8_stem_op(self, name: str, c_desc, temporal: bool, p: StemSrc, m: FMap, pre: tuple, post: tuple):
+        """one uint8 stem entry point: name(descriptor, [t_index, t_len, kt,] *pre, map, *post, stream); c_desc builds the
+        descriptor of p.src, the 2-D stems (not temporal) take no frame selection"""
+        assert temporal or p.t_index is None
+        d, fm = c_desc(p), _c_fmap(m)
+        sel = (_ptr(p.t_index), p.t_len, p.kt) if temporal else ()
+        return self._plain(name, C.byref(d), *sel, *map(_ptr, pre), C.byref(fm), *map(_ptr, post), keep=(d, fm, p, *pre, m, *post))
+
     def u8stem_conv_fwd(self, p: StemSrc, w: torch.Tensor, y: FMap, stats: Optional[torch.Tensor]):
-        d, fy = self._c_u8clip(p), _c_fmap(y)
-        return self._plain("sfk_u8stem_conv_fwd", C.byref(d), _ptr(p.t_index), p.t_len, p.kt, _ptr(w), C.byref(fy),
-                           _ptr(stats), keep=(d, fy, p, w, y, stats))
+        return self._u8_stem_op("sfk_u8stem_conv_fwd", self._c_u8clip, True, p, y, (w,), (stats,))
 
     def u8stem_conv_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
-        d, fy = self._c_u8clip(p), _c_fmap(dy)
-        return self._plain("sfk_u8stem_conv_wgrad", C.byref(d), _ptr(p.t_index), p.t_len, p.kt, C.byref(fy), _ptr(dw),
-                           keep=(d, fy, p, dy, dw))
+        return self._u8_stem_op("sfk_u8stem_conv_wgrad", self._c_u8clip, True, p, dy, (), (dw,))
 
     def u8stem2d_fwd(self, p: StemSrc, w: torch.Tensor, y: FMap, stats: Optional[torch.Tensor]):
-        assert p.t_index is None
-        d, fy = self._c_u8clip(p), _c_fmap(y)
-        return self._plain("sfk_u8stem2d_fwd", C.byref(d), _ptr(w), C.byref(fy), _ptr(stats), keep=(d, fy, p, w, y, stats))
+        return self._u8_stem_op("sfk_u8stem2d_fwd", self._c_u8clip, False, p, y, (w,), (stats,))
 
     def u8stem2d_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
-        assert p.t_index is None
-        d, fy = self._c_u8clip(p), _c_fmap(dy)
-        return self._plain("sfk_u8stem2d_wgrad", C.byref(d), C.byref(fy), _ptr(dw), keep=(d, fy, p, dy, dw))
+        return self._u8_stem_op("sfk_u8stem2d_wgrad", self._c_u8clip, False, p, dy, (), (dw,))
 
     # -- the uint8 stems reading the frame pool (include/sfk_u8stem_pool.h); `src` of the StemSrc is an input_pipeline.PoolClip
     #    (the BatchNorm partial-sum rows: u8stem_tiles, which reads the output map only)
@@ -915,24 +915,16 @@ class HipBackend:
         return d
 
     def u8pstem_conv_fwd(self, p: StemSrc, w: torch.Tensor, y: FMap, stats: Optional[torch.Tensor]):
-        d, fy = self._c_u8poolclip(p), _c_fmap(y)
-        return self._plain("sfk_u8pstem_conv_fwd", C.byref(d), _ptr(p.t_index), p.t_len, p.kt, _ptr(w), C.byref(fy),
-                           _ptr(stats), keep=(d, fy, p, w, y, stats))
+        return self._u8_stem_op("sfk_u8pstem_conv_fwd", self._c_u8poolclip, True, p, y, (w,), (stats,))
 
     def u8pstem_conv_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
-        d, fy = self._c_u8poolclip(p), _c_fmap(dy)
-        return self._plain("sfk_u8pstem_conv_wgrad", C.byref(d), _ptr(p.t_index), p.t_len, p.kt, C.byref(fy), _ptr(dw),
-                           keep=(d, fy, p, dy, dw))
+        return self._u8_stem_op("sfk_u8pstem_conv_wgrad", self._c_u8poolclip, True, p, dy, (), (dw,))
 
     def u8pstem2d_fwd(self, p: StemSrc, w: torch.Tensor, y: FMap, stats: Optional[torch.Tensor]):
-        assert p.t_index is None
-        d, fy = self._c_u8poolclip(p), _c_fmap(y)
-        return self._plain("sfk_u8pstem2d_fwd", C.byref(d), _ptr(w), C.byref(fy), _ptr(stats), keep=(d, fy, p, w, y, stats))
+        return self._u8_stem_op("sfk_u8pstem2d_fwd", self._c_u8poolclip, False, p, y, (w,), (stats,))
 
     def u8pstem2d_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
-        assert p.t_index is None
-        d, fy = self._c_u8poolclip(p), _c_fmap(dy)
-        return self._plain("sfk_u8pstem2d_wgrad", C.byref(d), C.byref(fy), _ptr(dw), keep=(d, fy, p, dy, dw))
+        return self._u8_stem_op("sfk_u8pstem2d_wgrad", self._c_u8poolclip, False, p, dy, (), (dw,))
 
     # -- generic plain-argument entry points
     def _plain(self, name, *args, keep=()):

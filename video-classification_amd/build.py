@@ -28,7 +28,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             os.path.join(ROOT, "include", "sfk_resident.h"), os.path.join(ROOT, "include", "sfk_roi_pool.h"),
             os.path.join(ROOT, "include", "sfk_roi_ragged.h"), os.path.join(ROOT, "include", "sfk_u8stem_pool.h"),
             os.path.join(ROOT, "include", "sfk_optim.h"), os.path.join(ROOT, "include", "sfk_groups.h"),
-            os.path.join(CSRC, "optim_elem.h")]
+            os.path.join(CSRC, "optim_elem.h"), os.path.join(CSRC, "stem_src.h")]
     flags = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
     flags += os.environ.get("SFK_EXTRA_FLAGS", "").split()          # experiment builds (tools/), with SFK_LIB_OUT
 

@@ -15,16 +15,15 @@
 //             to dw with fp32 atomics (dw zeroed on the stream first).
 // Both kernels also read the loader's HWC uint8 frames through a 256-entry f32 table with a per-clip crop shift
 // (S = U8Lut, include/sfk_u8stem.h): the normalised, cropped float clip is then never written.
+// The tile / patch geometry (TS, PR, PC, PLANE, NSLOT), ldsrc, plane_store, the MFMA operand fragments (Frag, store4) and the
+// host's view of a uint8 source are stem_src.h's, shared with stem_conv.hip; the source offsets of a tile and the loads of a
+// plane (PatchSlots, plane_fetch) are this file's own -- see stem_src.h for why.
 #include "sfk_common.h"
 #include "sfk_stem2d.h"
+#include "stem_src.h"
 
 namespace {
 
-constexpr int TS = 16;            // output tile edge (pixels)
-constexpr int PR = 2 * TS + 5;    // patch rows  (37)
-constexpr int PC = 40;            // patch cols  (38 used, padded)
-constexpr int PLANE = PR * PC;    // 1480
-constexpr int NSLOT = (PLANE + 255) / 256;   // 6 patch elements per thread and plane
 constexpr int CP = 4;             // planes per forward chunk: 28 filter rows = 7 K-steps of 32
 constexpr int CR = CP * 7;
 constexpr int WROW = CR * 8 + 8;  // staged filter row (+16 B for bf16: spreads the 16-byte reads over banks)
@@ -52,12 +51,9 @@ struct S2K {
   int pfill;                      // pooled S: the byte every pixel of a missing frame has
 };
 
-template <typename S> __device__ __forceinline__ float ldsrc(const void* p, int64_t off);
-template <> __device__ __forceinline__ float ldsrc<float>(const void* p, int64_t off) { return static_cast<const float*>(p)[off]; }
-template <> __device__ __forceinline__ float ldsrc<bf16_t>(const void* p, int64_t off) { return (float)static_cast<const bf16_t*>(p)[off]; }
-
+// (stem_conv.hip has the same struct with the masking at the use; keep the two in step otherwise)
 struct PatchSlots {
-  int64_t off[NSLOT];
+  int64_t off[NSLOT];   // hi*sh + wi*sw of the current tile, 0 where !ok: readers add it to the plane's base as it is
   bool ok[NSLOT];
   template <typename S>
   __device__ __forceinline__ void set_tile(const S2K& k, int n, int ho0, int wo0) {
@@ -128,69 +124,11 @@ __device__ __forceinline__ void plane_fetch(const S2K& k, const PatchSlots& ps, 
   }
 }
 
-template <typename T>
-__device__ __forceinline__ void plane_store(T* patch, const float (&v)[NSLOT]) {
-#pragma unroll
-  for (int i = 0; i < NSLOT; ++i) {
-    const int e = threadIdx.x + 256 * i;
-    if (e < PLANE) patch[e] = (T)v[i];
-  }
-}
-
 __device__ __forceinline__ void tile_coords(const S2K& k, int tile, int& n, int& ho0, int& wo0) {
   uint32_t q1, tw, n_, th;
   k.dtw.divmod((uint32_t)tile, q1, tw);
   k.dth.divmod(q1, n_, th);
   n = (int)n_; ho0 = (int)th * TS; wo0 = (int)tw * TS;
-}
-
-template <typename T> struct Frag;
-template <> struct Frag<bf16_t> {
-  typedef bf16x8 ab;
-  static __device__ __forceinline__ ab run8(const bf16_t* p) {   // 8 consecutive elements, 4-byte aligned
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-    uint4 v = make_uint4(q[0], q[1], q[2], q[3]);
-    return *reinterpret_cast<ab*>(&v);
-  }
-  static __device__ __forceinline__ ab ld16(const bf16_t* p) { return *reinterpret_cast<const ab*>(p); }
-  static __device__ __forceinline__ void zero(ab& v) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = (bf16_t)0.f;
-  }
-  static __device__ __forceinline__ void set(ab& v, int i, float f) { v[i] = (bf16_t)f; }
-  static __device__ __forceinline__ void mma(f32x4& acc, const ab& a, const ab& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-  }
-};
-struct F8 { float v[8]; };
-template <> struct Frag<float> {
-  typedef F8 ab;
-  static __device__ __forceinline__ ab run8(const float* p) {    // 8 consecutive floats, 8-byte aligned
-    ab r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float2 t = *reinterpret_cast<const float2*>(p + 2 * i);
-      r.v[2 * i] = t.x; r.v[2 * i + 1] = t.y;
-    }
-    return r;
-  }
-  static __device__ __forceinline__ ab ld16(const float* p) { return run8(p); }
-  static __device__ __forceinline__ void zero(ab& v) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v.v[i] = 0.f;
-  }
-  static __device__ __forceinline__ void set(ab& v, int i, float f) { v.v[i] = f; }
-  static __device__ __forceinline__ void mma(f32x4& acc, const ab& a, const ab& b) {
-#pragma unroll
-    for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[s], b.v[s], acc, 0, 0, 0);
-  }
-};
-
-__device__ __forceinline__ void store4(float* p, const f32x4& v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-__device__ __forceinline__ void store4(bf16_t* p, const f32x4& v) {
-  bf16x4 o;
-  o[0] = (bf16_t)v[0]; o[1] = (bf16_t)v[1]; o[2] = (bf16_t)v[2]; o[3] = (bf16_t)v[3];
-  *reinterpret_cast<bf16x4*>(p) = o;
 }
 
 // ------------------------------------------------------------------------------------------ forward
@@ -408,10 +346,11 @@ __global__ __launch_bounds__(256) void stem2d_wgrad_kernel(const S2K k) {
 constexpr int LDS_FWD = 64 * WROW * 2 * 2 + CP * PLANE * 2 * 2 + 4 * 64 * 2 * 4;   // 85120 B either way (bf16 x 2 buffers, f32 x 1)
 constexpr int LDS_LUT = 256 * 4;                                                   // + the table of the uint8 source
 
-int fill(const sfk_stem2d_src* s, const sfk_fmap* y, S2K& k) {
+// bytes: the source is a uint8 view (src_dtype is not read)
+int fill(const sfk_stem2d_src* s, const sfk_fmap* y, S2K& k, bool bytes = false) {
   if (!s || !y || s->struct_size != sizeof(sfk_stem2d_src)) return SFK_ERR_INVALID;
   if (!s->src || !sfk_fmap_ok(y)) return SFK_ERR_INVALID;
-  if (s->src_dtype != SFK_F32 && s->src_dtype != SFK_BF16) return SFK_ERR_INVALID;
+  if (!bytes && s->src_dtype != SFK_F32 && s->src_dtype != SFK_BF16) return SFK_ERR_INVALID;
   if (s->n <= 0 || s->t <= 0 || s->c <= 0 || s->h_in <= 0 || s->w_in <= 0) return SFK_ERR_INVALID;
   if (s->sn < 0 || s->st < 0 || s->sc < 0 || s->sh < 0 || s->sw < 0) return SFK_ERR_INVALID;
   const int ho = (s->h_in + 6 - 7) / 2 + 1, wo = (s->w_in + 6 - 7) / 2 + 1;
@@ -437,35 +376,22 @@ int fill(const sfk_stem2d_src* s, const sfk_fmap* y, S2K& k) {
   return SFK_OK;
 }
 
-// the logical (n, t, c, h, w) clip of an sfk_u8_clip as the kernels index it: channel c at byte c0 + c
-int fill_u8(const sfk_u8_clip* x, const sfk_fmap* y, S2K& k) {
-  if (!sfk_u8_clip_ok(x)) return SFK_ERR_INVALID;
-  sfk_stem2d_src s{};
-  s.struct_size = sizeof(sfk_stem2d_src);
-  s.src_dtype = SFK_F32;          // (fill's element-type check only: S = U8Lut reads bytes through the table)
-  s.src = x->src + x->c0;
-  s.sn = x->sn; s.st = x->st; s.sc = 1; s.sh = x->sh; s.sw = x->sw;
-  s.n = x->n; s.t = x->t; s.c = x->c; s.h_in = x->h; s.w_in = x->w;
-  const int st = fill(&s, y, k);
-  if (st != SFK_OK) return st;
-  k.lut = x->lut; k.crop = x->crop; k.pad = x->pad;
-  return SFK_OK;
-}
+// S2K of a source descriptor under a map: an sfk_stem2d_src as it is ...
+int fill_src(const sfk_stem2d_src* s, const sfk_fmap* y, S2K& k) { return fill(s, y, k); }
 
-// ... and of an sfk_u8_pool_clip: the pool is the source, the clip stride is unused (plane_base goes through the index table)
-int fill_u8p(const sfk_u8_pool_clip* x, const sfk_fmap* y, S2K& k) {
-  if (!sfk_u8_pool_clip_ok(x)) return SFK_ERR_INVALID;
+// ... and either uint8 descriptor through its view (stem_src.h): channel c at byte c of the view's src
+template <typename X>
+int fill_src(const X* x, const sfk_fmap* y, S2K& k) {
+  U8View v;
+  if (sfk_u8_view(x, v) != SFK_OK) return SFK_ERR_INVALID;
   sfk_stem2d_src s{};
   s.struct_size = sizeof(sfk_stem2d_src);
-  s.src_dtype = SFK_F32;          // (fill's element-type check only, as in fill_u8)
-  s.src = x->pool + x->c0;
-  s.sn = 0; s.st = x->frame_stride; s.sc = 1; s.sh = x->row_stride; s.sw = x->pixel_pitch;
-  s.n = x->n; s.t = x->t; s.c = x->c; s.h_in = x->h; s.w_in = x->w;
-  const int st = fill(&s, y, k);
-  if (st != SFK_OK) return st;
-  k.lut = x->lut; k.crop = x->crop; k.pad = x->pad;
-  k.pindex = x->index; k.pframes = x->frames; k.pfill = x->fill;
-  return SFK_OK;
+  s.src = v.src;
+  s.sn = v.sn; s.st = v.st; s.sc = 1; s.sh = v.sh; s.sw = v.sw;
+  s.n = v.n; s.t = v.t; s.c = v.c; s.h_in = v.h; s.w_in = v.w;
+  const int st = fill(&s, y, k, true);
+  if (st == SFK_OK) sfk_u8_view_tail(v, k);
+  return st;
 }
 
 template <typename S>
@@ -500,6 +426,30 @@ int launch_wgrad(S2K& k, const sfk_fmap* dy, hipStream_t hs) {
   return SFK_OK;
 }
 
+// The entry points over a source descriptor X read as source tag S: the argument checks in their order (the map before
+// the filter), then the launch
+template <typename S, typename X>
+int stem2d_fwd(const X* x, const void* w, const sfk_fmap* y, float* stats, sfk_stream_t stream) {
+  S2K k;
+  const int st = fill_src(x, y, k);
+  if (st != SFK_OK) return st;
+  if (!w) return SFK_ERR_INVALID;
+  if ((((uintptr_t)w) & 15) != 0) return SFK_ERR_UNSUPPORTED;
+  k.w = w;
+  k.stats = stats;
+  return launch_fwd<S>(k, y, static_cast<hipStream_t>(stream));
+}
+
+template <typename S, typename X>
+int stem2d_wgrad(const X* x, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
+  S2K k;
+  const int st = fill_src(x, dy, k);
+  if (st != SFK_OK) return st;
+  if (!dw) return SFK_ERR_INVALID;
+  k.dw = dw;
+  return launch_wgrad<S>(k, dy, static_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 extern "C" int sfk_stem2d_abi_version(void) { return SFK_STEM2D_ABI_VERSION; }
@@ -510,66 +460,29 @@ extern "C" int sfk_stem2d_tiles(const sfk_stem2d_src* s, const sfk_fmap* y) {
   return st != SFK_OK ? st : k.ntiles;
 }
 
+// (a null or mistyped s: either instantiation's fill refuses it)
 extern "C" int sfk_stem2d_fwd(const sfk_stem2d_src* s, const void* w, const sfk_fmap* y, float* stats, sfk_stream_t stream) {
-  S2K k;
-  const int st = fill(s, y, k);
-  if (st != SFK_OK) return st;
-  if (!w) return SFK_ERR_INVALID;
-  if ((((uintptr_t)w) & 15) != 0) return SFK_ERR_UNSUPPORTED;
-  k.w = w;
-  k.stats = stats;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  return s->src_dtype == SFK_BF16 ? launch_fwd<bf16_t>(k, y, hs) : launch_fwd<float>(k, y, hs);
+  return s && s->src_dtype == SFK_BF16 ? stem2d_fwd<bf16_t>(s, w, y, stats, stream) : stem2d_fwd<float>(s, w, y, stats, stream);
 }
 
 extern "C" int sfk_stem2d_wgrad(const sfk_stem2d_src* s, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
-  S2K k;
-  const int st = fill(s, dy, k);
-  if (st != SFK_OK) return st;
-  if (!dw) return SFK_ERR_INVALID;
-  k.dw = dw;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  return s->src_dtype == SFK_BF16 ? launch_wgrad<bf16_t>(k, dy, hs) : launch_wgrad<float>(k, dy, hs);
+  return s && s->src_dtype == SFK_BF16 ? stem2d_wgrad<bf16_t>(s, dy, dw, stream) : stem2d_wgrad<float>(s, dy, dw, stream);
 }
 
 // ------------------------------------------------------------------------------------------ uint8 frames (sfk_u8stem.h)
 extern "C" int sfk_u8stem2d_fwd(const sfk_u8_clip* x, const void* w, const sfk_fmap* y, float* stats, sfk_stream_t stream) {
-  S2K k;
-  const int st = fill_u8(x, y, k);
-  if (st != SFK_OK) return st;
-  if (!w) return SFK_ERR_INVALID;
-  if ((((uintptr_t)w) & 15) != 0) return SFK_ERR_UNSUPPORTED;
-  k.w = w;
-  k.stats = stats;
-  return launch_fwd<U8Lut>(k, y, static_cast<hipStream_t>(stream));
+  return stem2d_fwd<U8Lut>(x, w, y, stats, stream);
 }
 
 extern "C" int sfk_u8stem2d_wgrad(const sfk_u8_clip* x, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
-  S2K k;
-  const int st = fill_u8(x, dy, k);
-  if (st != SFK_OK) return st;
-  if (!dw) return SFK_ERR_INVALID;
-  k.dw = dw;
-  return launch_wgrad<U8Lut>(k, dy, static_cast<hipStream_t>(stream));
+  return stem2d_wgrad<U8Lut>(x, dy, dw, stream);
 }
 
 // ------------------------------------------------------------------------------------------ uint8 frames in a frame pool (sfk_u8stem_pool.h)
 extern "C" int sfk_u8pstem2d_fwd(const sfk_u8_pool_clip* x, const void* w, const sfk_fmap* y, float* stats, sfk_stream_t stream) {
-  S2K k;
-  const int st = fill_u8p(x, y, k);
-  if (st != SFK_OK) return st;
-  if (!w) return SFK_ERR_INVALID;
-  if ((((uintptr_t)w) & 15) != 0) return SFK_ERR_UNSUPPORTED;
-  k.w = w;
-  k.stats = stats;
-  return launch_fwd<U8PoolLut>(k, y, static_cast<hipStream_t>(stream));
+  return stem2d_fwd<U8PoolLut>(x, w, y, stats, stream);
 }
 
 extern "C" int sfk_u8pstem2d_wgrad(const sfk_u8_pool_clip* x, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
-  S2K k;
-  const int st = fill_u8p(x, dy, k);
-  if (st != SFK_OK) return st;
-  if (!dw) return SFK_ERR_INVALID;
-  k.dw = dw;
-  return launch_wgrad<U8PoolLut>(k, dy, static_cast<hipStream_t>(stream));
+  return stem2d_wgrad<U8PoolLut>(x, dy, dw, stream);
 }

@@ -9,14 +9,14 @@
 //   wgrad   : pixels are the K dim: A = dY^T via ds_read_b64_tr_b16, B = 8 pixels (stride-2 columns) of one (kh,kw)
 // The clip is read in place through element strides (N,T,C,H,W dataset memory or N,C,T,H,W) with an optional frame
 // index (PackPathway), as f32 or bf16 -- or, for the generic kernels, as the loader's HWC uint8 frames through a 256-entry
-// f32 table with a per-clip crop shift (S = U8Lut, include/sfk_u8stem.h).
+// f32 table with a per-clip crop shift (S = U8Lut, include/sfk_u8stem.h).  The tile / patch geometry, ldsrc, plane_store, the
+// MFMA operand fragments (Frag, store4) and the host's view of a uint8 source are stem_src.h's, shared with stem2d.hip; the
+// source offsets of a tile and the loads of a plane (PatchSlots, plane_fetch) are this file's own -- see stem_src.h for why.
 #include "sfk_common.h"
+#include "stem_src.h"
 
 namespace {
 
-constexpr int TS = 16;            // output tile edge (pixels)
-constexpr int PR = 2 * TS + 5;    // patch rows  (37)
-constexpr int PC = 40;            // patch cols  (2*15 + 7 + 1 = 38 used, padded)
 constexpr int KH = 7;
 
 struct StemK {
@@ -48,17 +48,9 @@ struct StemK {
   int pfill;                      // pooled S: the byte every pixel of a missing frame has
 };
 
-template <typename S> __device__ __forceinline__ float ldsrc(const void* p, int64_t off);
-template <> __device__ __forceinline__ float ldsrc<float>(const void* p, int64_t off) { return static_cast<const float*>(p)[off]; }
-template <> __device__ __forceinline__ float ldsrc<bf16_t>(const void* p, int64_t off) { return (float)static_cast<const bf16_t*>(p)[off]; }
-
-// The patch of one (frame, channel) plane is PR*PC = 1480 elements = NSLOT slots per thread.  A thread's slots have the
-// same (row, col) for every plane and tile, so their source offsets are computed once per tile and the loads of a plane
-// (or several planes) are issued back to back -- the loader is latency-bound otherwise.
-constexpr int NSLOT = (PR * PC + 255) / 256;   // 6
-
+// (stem2d.hip has the same struct with the masking in set_tile; keep the two in step otherwise)
 struct PatchSlots {
-  int64_t off[NSLOT];   // hi*sh + wi*sw of the current tile
+  int64_t off[NSLOT];   // hi*sh + wi*sw of the current tile, ALSO where !ok: readers add `ok[i] ? off[i] : 0` to the plane's base
   bool ok[NSLOT];
   template <typename S>
   __device__ __forceinline__ void set_tile(const StemK& k, int n, int ho0, int wo0) {
@@ -135,15 +127,6 @@ __device__ __forceinline__ void plane_fetch(const StemK& k, const PatchSlots& ps
   }
 }
 
-template <typename T>
-__device__ __forceinline__ void plane_store(T* patch, const float (&v)[NSLOT]) {
-#pragma unroll
-  for (int i = 0; i < NSLOT; ++i) {
-    const int e = threadIdx.x + 256 * i;
-    if (e < PR * PC) patch[e] = (T)v[i];
-  }
-}
-
 // S = U8Pix<CIN>: the CIN channel bytes of a pixel are contiguous in the HWC frames.  Byte loads of one channel plane put
 // neighbouring lanes sw bytes apart (a wave-wide load spans ~11 cache lines for 21-channel pixels) and every plane touches
 // the same lines again; instead each lane loads the aligned dwords that hold its pixel's CIN bytes once per frame tap and
@@ -197,45 +180,6 @@ __device__ __forceinline__ void tile_coords(const StemK& k, int tile, int& n, in
 }
 
 // ------------------------------------------------------------------------------------------ forward
-template <typename T> struct Frag;
-template <> struct Frag<bf16_t> {
-  typedef bf16x8 ab;
-  static __device__ __forceinline__ ab run8(const bf16_t* p) {   // 8 consecutive elements, 4-byte aligned
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-    uint4 v = make_uint4(q[0], q[1], q[2], q[3]);
-    return *reinterpret_cast<ab*>(&v);
-  }
-  static __device__ __forceinline__ ab ld16(const bf16_t* p) { return *reinterpret_cast<const ab*>(p); }
-  static __device__ __forceinline__ void mma(f32x4& acc, const ab& a, const ab& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
-  }
-};
-struct F8 { float v[8]; };
-template <> struct Frag<float> {
-  typedef F8 ab;
-  static __device__ __forceinline__ ab run8(const float* p) {    // 8 consecutive floats, 8-byte aligned
-    ab r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float2 t = *reinterpret_cast<const float2*>(p + 2 * i);
-      r.v[2 * i] = t.x; r.v[2 * i + 1] = t.y;
-    }
-    return r;
-  }
-  static __device__ __forceinline__ ab ld16(const float* p) { return run8(p); }
-  static __device__ __forceinline__ void mma(f32x4& acc, const ab& a, const ab& b) {
-#pragma unroll
-    for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.v[s], b.v[s], acc, 0, 0, 0);
-  }
-};
-
-__device__ __forceinline__ void store4(float* p, const f32x4& v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-__device__ __forceinline__ void store4(bf16_t* p, const f32x4& v) {
-  bf16x4 o;
-  o[0] = (bf16_t)v[0]; o[1] = (bf16_t)v[1]; o[2] = (bf16_t)v[2]; o[3] = (bf16_t)v[3];
-  *reinterpret_cast<bf16x4*>(p) = o;
-}
-
 // FN = co fragments (cout <= 16*FN).  A block walks tiles blockIdx.x, +gridDim.x, ... (filters are staged once);
 // one tile = 16x16 output pixels, wave w owns output rows 4w..4w+3.
 template <typename T, typename S, int FN>
@@ -1306,10 +1250,11 @@ inline int64_t stem_src_extent(const sfk_stem_src* s, int n) {
                 (int64_t)(s->h_in - 1) * s->sh + (int64_t)(s->w_in - 1) * s->sw + 1);
 }
 
-int fill(const sfk_stem_src* s, int cout, int t_out, int ho, int wo, StemK& k) {
+// bytes: the source is a uint8 view (src_dtype is not read)
+int fill(const sfk_stem_src* s, int cout, int t_out, int ho, int wo, StemK& k, bool bytes = false) {
   if (!s || !s->src || s->cin <= 0 || s->kt <= 0 || !(s->kt & 1) || s->t_in <= 0 || s->h_in <= 0 || s->w_in <= 0)
     return SFK_ERR_INVALID;
-  if (s->src_dtype != SFK_F32 && s->src_dtype != SFK_BF16) return SFK_ERR_INVALID;
+  if (!bytes && s->src_dtype != SFK_F32 && s->src_dtype != SFK_BF16) return SFK_ERR_INVALID;
   const int t_log = s->t_index ? s->t_len : s->t_in;
   if (t_log <= 0 || t_out != t_log) return SFK_ERR_INVALID;
   if (ho != (s->h_in + 6 - 7) / 2 + 1 || wo != (s->w_in + 6 - 7) / 2 + 1) return SFK_ERR_INVALID;
@@ -1328,37 +1273,24 @@ int fill(const sfk_stem_src* s, int cout, int t_out, int ho, int wo, StemK& k) {
   return SFK_OK;
 }
 
-// the logical (n, ci, t, h, w) clip of an sfk_u8_clip as the generic kernels index it: channel ci at byte c0 + ci
-int fill_u8(const sfk_u8_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt, int n, int cout, int t_out, int ho,
-            int wo, StemK& k) {
-  if (!sfk_u8_clip_ok(x) || x->n != n) return SFK_ERR_INVALID;   // (the tiles index clips and crop rows by the map's n)
-  sfk_stem_src s{};
-  s.src = x->src + x->c0;
-  s.src_dtype = SFK_F32;          // (fill's element-type check only: S = U8Lut reads bytes through the table)
-  s.sn = x->sn; s.sc = 1; s.st = x->st; s.sh = x->sh; s.sw = x->sw;
-  s.cin = x->c; s.t_in = x->t; s.h_in = x->h; s.w_in = x->w;
-  s.t_index = t_index; s.t_len = t_len; s.kt = kt;
-  const int st = fill(&s, cout, t_out, ho, wo, k);
-  if (st != SFK_OK) return st;
-  k.lut = x->lut; k.crop = x->crop; k.pad = x->pad;
-  return SFK_OK;
+// StemK of a source descriptor under a map: an sfk_stem_src as it is (it carries its own frame selection) ...
+int fill_src(const sfk_stem_src* s, const int32_t*, int32_t, int32_t, const sfk_fmap* m, StemK& k) {
+  return fill(s, m->c, m->t, m->h, m->w, k);
 }
 
-// ... and of an sfk_u8_pool_clip: the pool is the source, the clip stride is unused (plane_base goes through the index table)
-int fill_u8p(const sfk_u8_pool_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt, int n, int cout, int t_out, int ho,
-             int wo, StemK& k) {
-  if (!sfk_u8_pool_clip_ok(x) || x->n != n) return SFK_ERR_INVALID;
+// ... and either uint8 descriptor through its view (stem_src.h): channel ci at byte ci of the view's src
+template <typename X>
+int fill_src(const X* x, const int32_t* t_index, int32_t t_len, int32_t kt, const sfk_fmap* m, StemK& k) {
+  U8View v;
+  if (sfk_u8_view(x, v) != SFK_OK || v.n != m->n) return SFK_ERR_INVALID;   // (the tiles index clips and crop rows by the map's n)
   sfk_stem_src s{};
-  s.src = x->pool + x->c0;
-  s.src_dtype = SFK_F32;          // (fill's element-type check only, as in fill_u8)
-  s.sn = 0; s.sc = 1; s.st = x->frame_stride; s.sh = x->row_stride; s.sw = x->pixel_pitch;
-  s.cin = x->c; s.t_in = x->t; s.h_in = x->h; s.w_in = x->w;
+  s.src = v.src;
+  s.sn = v.sn; s.sc = 1; s.st = v.st; s.sh = v.sh; s.sw = v.sw;
+  s.cin = v.c; s.t_in = v.t; s.h_in = v.h; s.w_in = v.w;
   s.t_index = t_index; s.t_len = t_len; s.kt = kt;
-  const int st = fill(&s, cout, t_out, ho, wo, k);
-  if (st != SFK_OK) return st;
-  k.lut = x->lut; k.crop = x->crop; k.pad = x->pad;
-  k.pindex = x->index; k.pframes = x->frames; k.pfill = x->fill;
-  return SFK_OK;
+  const int st = fill(&s, m->c, m->t, m->h, m->w, k, true);
+  if (st == SFK_OK) sfk_u8_view_tail(v, k);
+  return st;
 }
 
 // the generic forward (any cin / kt / source type): one 16x16 tile per block iteration, filters and patches in LDS
@@ -1418,6 +1350,52 @@ int stem_wgrad_generic(StemK& k, const sfk_fmap* dy, hipStream_t hs) {
   return SFK_OK;
 }
 
+// What the forward entry points share: the argument checks in their order, and the StemK of (source, filter, map)
+template <typename X>
+int fwd_args(const X* x, const int32_t* t_index, int32_t t_len, int32_t kt, const void* w, const sfk_fmap* y, float* stats,
+             StemK& k) {
+  if (!w || !sfk_fmap_ok(y)) return SFK_ERR_INVALID;
+  const int st = fill_src(x, t_index, t_len, kt, y, k);
+  if (st != SFK_OK) return st;
+  if ((y->ld % 4) || (y->c_off % 4) || (((uintptr_t)y->ptr) & 15) || (((uintptr_t)w) & 15)) return SFK_ERR_UNSUPPORTED;
+  k.w = w; k.y = y->ptr; k.yld = y->ld; k.yoff = y->c_off; k.stats = stats; k.dw = nullptr;
+  k.ntiles = y->n * y->t * k.tiles_h * k.tiles_w;
+  return SFK_OK;
+}
+
+// ... and the filter-gradient ones
+template <typename X>
+int wgrad_args(const X* x, const int32_t* t_index, int32_t t_len, int32_t kt, const sfk_fmap* dy, float* dw, StemK& k) {
+  if (!dw || !sfk_fmap_ok(dy)) return SFK_ERR_INVALID;
+  const int st = fill_src(x, t_index, t_len, kt, dy, k);
+  if (st != SFK_OK) return st;
+  if (!sfk_fmap_vec_ok(dy)) return SFK_ERR_UNSUPPORTED;
+  k.w = nullptr; k.y = dy->ptr; k.yld = dy->ld; k.yoff = dy->c_off; k.stats = nullptr; k.dw = dw;
+  k.ntiles = dy->n * dy->t * k.tiles_h * k.tiles_w;
+  return SFK_OK;
+}
+
+// The uint8 entry points, X = sfk_u8_clip (tags U8Lut / U8Pix) or sfk_u8_pool_clip (U8PoolLut / U8PoolPix).  The reference
+// geometries' channel counts stage whole pixels in the forward (stage_u8_pixels); any other count a plane at a time.
+template <typename X, typename Lut, typename Pix5, typename Pix15>
+int u8_fwd(const X* x, const int32_t* t_index, int32_t t_len, int32_t kt, const void* w, const sfk_fmap* y, float* stats,
+           sfk_stream_t stream) {
+  StemK k;
+  const int st = fwd_args(x, t_index, t_len, kt, w, y, stats, k);
+  if (st != SFK_OK) return st;
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  if (x->c == 5) return stem_fwd_generic<Pix5>(k, y, hs);
+  if (x->c == 15) return stem_fwd_generic<Pix15>(k, y, hs);
+  return stem_fwd_generic<Lut>(k, y, hs);
+}
+
+template <typename X, typename Lut>
+int u8_wgrad(const X* x, const int32_t* t_index, int32_t t_len, int32_t kt, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
+  StemK k;
+  const int st = wgrad_args(x, t_index, t_len, kt, dy, dw, k);
+  return st != SFK_OK ? st : stem_wgrad_generic<Lut>(k, dy, static_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 extern "C" int sfk_stem_kp(int32_t cin, int32_t kt) { return ((kt * cin * KH + 3) / 4) * 4 * 8; }
@@ -1429,13 +1407,9 @@ extern "C" int sfk_stem_conv_tiles(const sfk_stem_src* s, const sfk_fmap* y) {
 
 extern "C" int sfk_stem_conv_fwd(const sfk_stem_src* s, const void* w, const sfk_fmap* y, float* stats,
                                  sfk_stream_t stream) {
-  if (!w || !sfk_fmap_ok(y)) return SFK_ERR_INVALID;
   StemK k;
-  const int st = fill(s, y->c, y->t, y->h, y->w, k);
+  const int st = fwd_args(s, nullptr, 0, 0, w, y, stats, k);
   if (st != SFK_OK) return st;
-  if ((y->ld % 4) || (y->c_off % 4) || (((uintptr_t)y->ptr) & 15) || (((uintptr_t)w) & 15)) return SFK_ERR_UNSUPPORTED;
-  k.w = w; k.y = y->ptr; k.yld = y->ld; k.yoff = y->c_off; k.stats = stats; k.dw = nullptr;
-  k.ntiles = y->n * y->t * k.tiles_h * k.tiles_w;
   // canonical fast stem geometry in bf16 with 16-byte addressable rows: temporal pairs over a rolling frame ring
   if (y->dtype == SFK_BF16 && s->src_dtype == SFK_BF16 && s->cin == 3 && (s->kt == 5 || s->kt == 3) && y->c <= 8 &&
       s->sw == 1 && (s->w_in % 8) == 0 && !((s->sn | s->sc | s->st | s->sh) & 7) && !(((uintptr_t)s->src) & 15) &&
@@ -1494,13 +1468,9 @@ extern "C" int sfk_stem_conv_fwd(const sfk_stem_src* s, const void* w, const sfk
 }
 
 extern "C" int sfk_stem_conv_wgrad(const sfk_stem_src* s, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
-  if (!dw || !sfk_fmap_ok(dy)) return SFK_ERR_INVALID;
   StemK k;
-  const int st = fill(s, dy->c, dy->t, dy->h, dy->w, k);
+  const int st = wgrad_args(s, nullptr, 0, 0, dy, dw, k);
   if (st != SFK_OK) return st;
-  if (!sfk_fmap_vec_ok(dy)) return SFK_ERR_UNSUPPORTED;
-  k.w = nullptr; k.y = dy->ptr; k.yld = dy->ld; k.yoff = dy->c_off; k.stats = nullptr; k.dw = dw;
-  k.ntiles = dy->n * dy->t * k.tiles_h * k.tiles_w;
   hipStream_t hs = static_cast<hipStream_t>(stream);
   // canonical fast stem geometry in bf16 with 16-byte addressable rows: the input-frame-stationary kernel
   if (dy->dtype == SFK_BF16 && s->src_dtype == SFK_BF16 && s->cin == 3 && s->kt <= 5 && dy->c <= 8 && s->sw == 1 &&
@@ -1525,29 +1495,12 @@ extern "C" int sfk_u8stem_abi_version(void) { return SFK_U8STEM_ABI_VERSION; }
 
 extern "C" int sfk_u8stem_conv_fwd(const sfk_u8_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt, const void* w,
                                    const sfk_fmap* y, float* stats, sfk_stream_t stream) {
-  if (!w || !sfk_fmap_ok(y)) return SFK_ERR_INVALID;
-  StemK k;
-  const int st = fill_u8(x, t_index, t_len, kt, y->n, y->c, y->t, y->h, y->w, k);
-  if (st != SFK_OK) return st;
-  if ((y->ld % 4) || (y->c_off % 4) || (((uintptr_t)y->ptr) & 15) || (((uintptr_t)w) & 15)) return SFK_ERR_UNSUPPORTED;
-  k.w = w; k.y = y->ptr; k.yld = y->ld; k.yoff = y->c_off; k.stats = stats; k.dw = nullptr;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  // the reference geometries' channel counts stage whole pixels (stage_u8_pixels); any other count a plane at a time
-  if (x->c == 5) return stem_fwd_generic<U8Pix<5>>(k, y, hs);
-  if (x->c == 15) return stem_fwd_generic<U8Pix<15>>(k, y, hs);
-  return stem_fwd_generic<U8Lut>(k, y, hs);
+  return u8_fwd<sfk_u8_clip, U8Lut, U8Pix<5>, U8Pix<15>>(x, t_index, t_len, kt, w, y, stats, stream);
 }
 
 extern "C" int sfk_u8stem_conv_wgrad(const sfk_u8_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt,
                                      const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
-  if (!dw || !sfk_fmap_ok(dy)) return SFK_ERR_INVALID;
-  StemK k;
-  const int st = fill_u8(x, t_index, t_len, kt, dy->n, dy->c, dy->t, dy->h, dy->w, k);
-  if (st != SFK_OK) return st;
-  if (!sfk_fmap_vec_ok(dy)) return SFK_ERR_UNSUPPORTED;
-  k.w = nullptr; k.y = dy->ptr; k.yld = dy->ld; k.yoff = dy->c_off; k.stats = nullptr; k.dw = dw;
-  k.ntiles = dy->n * dy->t * k.tiles_h * k.tiles_w;
-  return stem_wgrad_generic<U8Lut>(k, dy, static_cast<hipStream_t>(stream));
+  return u8_wgrad<sfk_u8_clip, U8Lut>(x, t_index, t_len, kt, dy, dw, stream);
 }
 
 // ------------------------------------------------------------------------------------------ uint8 frames in a frame pool (sfk_u8stem_pool.h)
@@ -1555,27 +1508,10 @@ extern "C" int sfk_u8stem_pool_abi_version(void) { return SFK_U8STEM_POOL_ABI_VE
 
 extern "C" int sfk_u8pstem_conv_fwd(const sfk_u8_pool_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt, const void* w,
                                     const sfk_fmap* y, float* stats, sfk_stream_t stream) {
-  if (!w || !sfk_fmap_ok(y)) return SFK_ERR_INVALID;
-  StemK k;
-  const int st = fill_u8p(x, t_index, t_len, kt, y->n, y->c, y->t, y->h, y->w, k);
-  if (st != SFK_OK) return st;
-  if ((y->ld % 4) || (y->c_off % 4) || (((uintptr_t)y->ptr) & 15) || (((uintptr_t)w) & 15)) return SFK_ERR_UNSUPPORTED;
-  k.w = w; k.y = y->ptr; k.yld = y->ld; k.yoff = y->c_off; k.stats = stats; k.dw = nullptr;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  // whole pixels for the reference geometries' channel counts, as sfk_u8stem_conv_fwd
-  if (x->c == 5) return stem_fwd_generic<U8PoolPix<5>>(k, y, hs);
-  if (x->c == 15) return stem_fwd_generic<U8PoolPix<15>>(k, y, hs);
-  return stem_fwd_generic<U8PoolLut>(k, y, hs);
+  return u8_fwd<sfk_u8_pool_clip, U8PoolLut, U8PoolPix<5>, U8PoolPix<15>>(x, t_index, t_len, kt, w, y, stats, stream);
 }
 
 extern "C" int sfk_u8pstem_conv_wgrad(const sfk_u8_pool_clip* x, const int32_t* t_index, int32_t t_len, int32_t kt,
                                       const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
-  if (!dw || !sfk_fmap_ok(dy)) return SFK_ERR_INVALID;
-  StemK k;
-  const int st = fill_u8p(x, t_index, t_len, kt, dy->n, dy->c, dy->t, dy->h, dy->w, k);
-  if (st != SFK_OK) return st;
-  if (!sfk_fmap_vec_ok(dy)) return SFK_ERR_UNSUPPORTED;
-  k.w = nullptr; k.y = dy->ptr; k.yld = dy->ld; k.yoff = dy->c_off; k.stats = nullptr; k.dw = dw;
-  k.ntiles = dy->n * dy->t * k.tiles_h * k.tiles_w;
-  return stem_wgrad_generic<U8PoolLut>(k, dy, static_cast<hipStream_t>(stream));
+  return u8_wgrad<sfk_u8_pool_clip, U8PoolLut>(x, t_index, t_len, kt, dy, dw, stream);
 }

@@ -23,7 +23,7 @@ import torch
 
 from . import arch
 from ._lib import BN_FOLD_ROWS, BnBwdFuse, ConvEpilogue, ConvPass, FMap, StemSrc, WgradPass, stem_kp
-from .input_pipeline import STEM_CLIPS, PoolClip, U8Clip
+from .input_pipeline import STEM_CLIPS, PoolClip
 from .plan import ConvGeom, dgrad_passes, fwd_pass, round_up, wgrad_taps
 
 Run = Callable[[int], None]
@@ -625,6 +625,16 @@ class Engine:
         return reduced
 
     # ---- stem: direct (kt,7,7)/(1,2,2) conv from the clip -> BN -> ReLU -> MaxPool
+    def _stem_entry(self, x5):
+        """(tiles, fwd, wgrad): the backend's stem methods for this kind of source -- a float clip, or uint8 frames the stem
+        reads itself, stacked (U8Clip, include/sfk_u8stem.h) or in the frame pool (PoolClip, include/sfk_u8stem_pool.h) -- under
+        the 3-D stem or res2d's Conv2d over the T*C stacked planes (include/sfk_stem2d.h)"""
+        op = "2d" if self.spec.frames_as_channels else "_conv"
+        if not isinstance(x5, STEM_CLIPS):
+            return tuple(getattr(self.be, f"stem{op}_{what}") for what in ("tiles", "fwd", "wgrad"))
+        pre = "u8pstem" if isinstance(x5, PoolClip) else "u8stem"
+        return self.be.u8stem_tiles, getattr(self.be, f"{pre}{op}_fwd"), getattr(self.be, f"{pre}{op}_wgrad")
+
     def _stem_ops(self, pl: Plan, p: int, x5: torch.Tensor, t_index, rec=None):
         """(re)create the two ops that hold the clip's address: forward conv and filter gradient"""
         L = self._layers[self.wiring.stems[p].conv_key]
@@ -632,16 +642,7 @@ class Engine:
         st = pl.stem_state[p]
         esz = 2 if self.dtype == torch.bfloat16 else 4
         flops = 2.0 * st["y"].pixels * L.c * L.cb.geom.cin * L.cb.geom.wtaps
-        f2d = self.spec.frames_as_channels               # res2d: Conv2d over the T*C stacked planes (include/sfk_stem2d.h)
-        if isinstance(x5, PoolClip):                     # the stem reads the frame pool through its index table (include/sfk_u8stem_pool.h)
-            fwd_fn, wgrad_fn = ((self.be.u8pstem2d_fwd, self.be.u8pstem2d_wgrad) if f2d else
-                                (self.be.u8pstem_conv_fwd, self.be.u8pstem_conv_wgrad))
-        elif isinstance(x5, U8Clip):                     # the stem reads the uint8 frames itself (include/sfk_u8stem.h)
-            fwd_fn, wgrad_fn = ((self.be.u8stem2d_fwd, self.be.u8stem2d_wgrad) if f2d else
-                                (self.be.u8stem_conv_fwd, self.be.u8stem_conv_wgrad))
-        else:
-            fwd_fn, wgrad_fn = ((self.be.stem2d_fwd, self.be.stem2d_wgrad) if f2d else
-                                (self.be.stem_conv_fwd, self.be.stem_conv_wgrad))
+        _, fwd_fn, wgrad_fn = self._stem_entry(x5)
         fwd = fwd_fn(src, self.S[L.w_off:L.w_off + L.w_numel], st["y"], st["stats"])
         meta = dict(kind="stem_fwd", layer=L.cb.conv_key, cout=L.c, flops=flops,
                     bytes=float(x5.numel() * x5.element_size() + st["y"].pixels * L.c * esz))
@@ -683,11 +684,7 @@ class Engine:
         pl.stem_state[p] = st
         rec = None
         if train:
-            if isinstance(x5, STEM_CLIPS):
-                tiles = self.be.u8stem_tiles
-            else:
-                tiles = self.be.stem2d_tiles if self.spec.frames_as_channels else self.be.stem_conv_tiles
-            mt = tiles(StemSrc(x5, t_index, g.k[0]), y)
+            mt = self._stem_entry(x5)[0](StemSrc(x5, t_index, g.k[0]), y)
             st["stats"] = self._buf(f"stats.{tag}", mt * L.c * 2, torch.float32)
             self._stem_ops(pl, p, x5, t_index)
             mean = self._buf(f"mean.{tag}", L.c, torch.float32)
