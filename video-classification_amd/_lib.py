@@ -235,6 +235,14 @@ class _JitterDesc(C.Structure):
                 ("workspace", C.c_void_p)]
 
 
+class _MixDesc(C.Structure):
+    """include/sfk_mix.h sfk_mix_desc: element (n, t, c, y, x) of the c mixed channels at
+    x[n*sn + t*st + (c_off + c)*sc + y*sh + x], mixed in place with its partner clip by the per-clip rows[n][8]"""
+    _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_int32), ("x", C.c_void_p), ("sn", C.c_int64), ("st", C.c_int64),
+                ("sc", C.c_int64), ("sh", C.c_int64), ("n", C.c_int32), ("t", C.c_int32), ("c", C.c_int32), ("h", C.c_int32),
+                ("w", C.c_int32), ("c_off", C.c_int32), ("rows", C.c_void_p)]
+
+
 class _OptimHp(C.Structure):
     """include/sfk_optim.h sfk_optim_hp: the device learning-rate table, weight decay and clipping coefficient shared by
     sfk_adam_hp and sfk_sgd_hp"""
@@ -491,6 +499,14 @@ SIGNATURES_GROUPS = {
     "sfk_sgd_groups": [_PF, _PF, _PF, _I64, C.POINTER(_GroupsHp), _F, _F, _I32, _F, _PV, _PV, _I32, _PV],
     "sfk_grad_norm_groups": [_PF, _I64, _PV, _PV, _I32, _F, _F, _PV, _PF, _PV],
 }
+# include/sfk_mix.h: Mixup / CutMix of the float clip in place and the soft-target loss, same library, its own header and version
+MIX_ABI_VERSION = 1        # include/sfk_mix.h SFK_MIX_ABI_VERSION
+MIX_ROW_FLOATS = 8         # include/sfk_mix.h SFK_MIX_ROW_FLOATS: partner, lam, y0, x0, y1, x1, weight, reserved
+SIGNATURES_MIX = {
+    "sfk_mix_abi_version": [],
+    "sfk_clip_mix": [C.POINTER(_MixDesc), _PV],
+    "sfk_softmax_ce_mix": [_PF, _PV, _PF, _F, _I32, _I32, _F, _PF, _PF, _PF, _PV, _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_groups_prepare": C.c_int64, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
@@ -535,6 +551,12 @@ def new_roi_desc() -> "_RoiDesc":
 def new_jitter_desc() -> "_JitterDesc":
     d = _JitterDesc()
     d.struct_size = C.sizeof(_JitterDesc)
+    return d
+
+
+def new_mix_desc() -> "_MixDesc":
+    d = _MixDesc()
+    d.struct_size = C.sizeof(_MixDesc)
     return d
 
 
@@ -606,7 +628,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib = C.CDLL(path)
     for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL,
                   SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL, SIGNATURES_ROI_RAGGED, SIGNATURES_U8STEM_POOL,
-                  SIGNATURES_OPTIM, SIGNATURES_GROUPS):
+                  SIGNATURES_OPTIM, SIGNATURES_GROUPS, SIGNATURES_MIX):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -637,6 +659,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk optim ABI version mismatch: library {lib.sfk_optim_abi_version()}, binding {OPTIM_ABI_VERSION}")
     if lib.sfk_groups_abi_version() != GROUPS_ABI_VERSION:
         raise SfkError(f"libsfk groups ABI version mismatch: library {lib.sfk_groups_abi_version()}, binding {GROUPS_ABI_VERSION}")
+    if lib.sfk_mix_abi_version() != MIX_ABI_VERSION:
+        raise SfkError(f"libsfk mix ABI version mismatch: library {lib.sfk_mix_abi_version()}, binding {MIX_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -1110,6 +1134,14 @@ class HipBackend:
         return self._plain("sfk_softmax_ce", _ptr(logits), _ptr(labels), n, k, gscale, _ptr(dlogits), _ptr(loss_out),
                            _ptr(loss_sum), _ptr(correct), keep=(logits, labels, dlogits, loss_out, loss_sum, correct))
 
+    def softmax_ce_mix(self, logits, labels, rows, smoothing, n, k, gscale, dlogits, loss_out, loss_sum, correct):
+        """sfk_softmax_ce_mix (include/sfk_mix.h): softmax_ce with the soft target of the mix table ``rows`` ((n, 8) float32
+        on the device, or None: every row identity) and the label-smoothing mass ``smoothing`` in [0, 1)"""
+        assert rows is None or (rows.dtype == torch.float32 and rows.is_contiguous() and tuple(rows.shape) == (n, MIX_ROW_FLOATS))
+        return self._plain("sfk_softmax_ce_mix", _ptr(logits), _ptr(labels), _ptr(rows), smoothing, n, k, gscale,
+                           _ptr(dlogits), _ptr(loss_out), _ptr(loss_sum), _ptr(correct),
+                           keep=(logits, labels, rows, dlogits, loss_out, loss_sum, correct))
+
     # -- optimiser / misc
     def adam(self, p, g, m, v, count, lr, b1, b2, eps, gscale, step, shadow=None):
         sd = _DT[shadow.dtype] if shadow is not None else SFK_F32
@@ -1266,6 +1298,21 @@ class HipBackend:
         d.n, d.t, d.h, d.w = n, t, h, w
         d.c_off, d.bgr, d.mean, d.std = c_off, 1 if bgr else 0, mean, std
         return self._plain("sfk_color_jitter", C.byref(d), keep=(d, clip, params, workspace))
+
+    def clip_mix(self, clip, rows, c_off: int = 0, c: Optional[int] = None):
+        """sfk_clip_mix (include/sfk_mix.h): clip (N,T,C,H,W) f32|bf16 with unit W stride, channels c_off .. c_off+c-1 (c None:
+        all from c_off) of every clip mixed IN PLACE with its partner's; rows (N,8) float32 = partner, lam, y0, x0, y1, x1,
+        weight, reserved on the device, read when the launch runs."""
+        assert clip.dim() == 5 and clip.stride(4) == 1
+        n, t, ch, h, w = clip.shape
+        c = ch - c_off if c is None else c
+        assert 0 <= c_off and 0 < c and c_off + c <= ch
+        assert rows.dtype == torch.float32 and rows.is_contiguous() and tuple(rows.shape) == (n, MIX_ROW_FLOATS)
+        d = new_mix_desc()
+        d.dtype, d.x, d.rows = _DT[clip.dtype], clip.data_ptr(), rows.data_ptr()
+        d.sn, d.st, d.sc, d.sh = clip.stride()[:4]
+        d.n, d.t, d.c, d.h, d.w, d.c_off = n, t, c, h, w, c_off
+        return self._plain("sfk_clip_mix", C.byref(d), keep=(d, clip, rows))
 
     @staticmethod
     def _fill_pool_desc(d, pool, index, lut, fill, out, c0, c):

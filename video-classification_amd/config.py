@@ -107,6 +107,12 @@ _C.MODEL.JITTER_BRIGHTNESS = 0.5   # dataset/chalearn_dataset.py:49: ColorJitter
 _C.MODEL.JITTER_CONTRAST = 0.3
 _C.MODEL.JITTER_SATURATION = 0.2
 _C.MODEL.JITTER_HUE = 0.1
+_C.MODEL.LABEL_SMOOTHING = 0.0     # the loss's smoothing mass eps: target (1 - eps) t + eps / K (include/sfk_mix.h); 0: sfk_softmax_ce as ever
+_C.MODEL.MIXUP_ALPHA = 0.0         # > 0: Mixup with lam ~ Beta(alpha, alpha) on the device float clip, pairs i <-> N-1-i (input_pipeline.draw_mix)
+_C.MODEL.CUTMIX_ALPHA = 0.0        # > 0: CutMix, the partner's box pasted; both > 0: CutMix with probability MIX_SWITCH_PROB
+_C.MODEL.MIX_PROB = 1.0            # the probability that a pair is mixed at all
+_C.MODEL.MIX_SWITCH_PROB = 0.5
+_C.MODEL.MIX_SEED = 0              # the draws come from a generator seeded by (MIX_SEED, epoch, rank), in the main process
 _C.MODEL.RESIDENT_TRAIN = False  # keep the decoded train frames on the device and gather the cropped clips there (input_pipeline.ResidentTrainSet)
 _C.MODEL.RESIDENT_GB = 32.0     # RESIDENT_TRAIN: the size of the frame arena, GiB (its last BATCH_SIZE * CLIP_LEN slots are the spill region)
 _C.MODEL.RESIDENT_STORE = 'frame'  # v2 RESIDENT_TRAIN: 'frame' keeps whole frames in a FramePool, 'box' only each video's part-box rectangle in a BoxArena of RESIDENT_GB bytes

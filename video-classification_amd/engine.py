@@ -1318,9 +1318,15 @@ class Engine:
         self._run_lanes(pl.bwd)
 
     # ---- fused loss + optimiser (train.py:228-231 without the per-step .item() sync of :236)
-    def loss_ops(self, pl: Plan, labels: torch.Tensor, loss_out, loss_sum, correct, gscale: float = 1.0) -> Run:
+    def loss_ops(self, pl: Plan, labels: torch.Tensor, loss_out, loss_sum, correct, gscale: float = 1.0,
+                 label_smoothing: float = 0.0, mix: Optional[torch.Tensor] = None) -> Run:
+        """the loss launch: sfk_softmax_ce, or -- with label smoothing or a mix table (include/sfk_mix.h) -- the one
+        sfk_softmax_ce_mix in its place"""
         n, k = pl.logits.shape
-        return self.be.softmax_ce(pl.logits, labels, n, k, gscale, pl.dlogits, loss_out, loss_sum, correct)
+        if label_smoothing == 0.0 and mix is None:
+            return self.be.softmax_ce(pl.logits, labels, n, k, gscale, pl.dlogits, loss_out, loss_sum, correct)
+        return self.be.softmax_ce_mix(pl.logits, labels, mix, label_smoothing, n, k, gscale, pl.dlogits, loss_out, loss_sum,
+                                      correct)
 
     def optim_state(self, kind: str):
         """The optimizer state optim.Optimizer's launches read, allocated (zero) when a launch of that kind is first built; every

@@ -310,6 +310,7 @@ class ModelManager(_train.ModelManager):
         self._lut = None
         self._roi = None
         self._jit = None
+        self._mix = None
         self.arch = "ref"
         self.init_model = self._init_v2_model
         self.prepare_data = self._prepare_v2_data
@@ -323,6 +324,9 @@ class ModelManager(_train.ModelManager):
         else:
             print(f"warning: {ckpt} not found, training from the reference init scheme")
         return model
+
+    def mix_channels(self) -> int:
+        return 7                                         # R, G, B, U, V and the two flow channels: the model reads them all
 
     def roi_resize(self) -> "RoiResize":
         if self._roi is None:
@@ -340,19 +344,26 @@ class ModelManager(_train.ModelManager):
         float batch {'rgb', 'uv', 'flow'} is the reference's permute + cat (:761-769).  An optional 'jitter' (N, 8) entry
         (input_pipeline.draw_color_jitter) applies ColorJitter to the R, G, B planes on the device: after the resize and
         the crop of a uint8 batch ("Optional Augment (crop&pad, color jitter)", :608-611), to the device copy of 'rgb' of
-        a float batch; the values are image values in [0, 1] (mean 0, std 1)."""
+        a float batch; the values are image values in [0, 1] (mean 0, std 1).  An optional 'mix' entry (the device table of
+        input_pipeline.ClipMix.load) then mixes the finished float clip with its partner clip (_mix_clip)."""
         y = self._h2d(batch["label"])
         if "clip_v2" in batch or "frames_u8" in batch:
             x = batch["clip_v2"] if "clip_v2" in batch else self.roi_resize()(batch["frames_u8"], batch["box"], batch.get("crop"))
             if "jitter" in batch:
                 self.color_jitter()(x, batch["jitter"])
+            x = self._mix_clip(x, batch)
             x = torch.permute(x, [0, 2, 1, 3, 4])
             return [x[:, 0:5], x[:, 5:7]], y
         rgb, uv, flow = (self._h2d(batch[k]) for k in ("rgb", "uv", "flow"))
         if "jitter" in batch:
             rgb = self.color_jitter()(self._own(rgb, batch["rgb"]), batch["jitter"])
         rgb, uv, flow = (torch.permute(t, [0, 2, 1, 3, 4]) for t in (rgb, uv, flow))
-        return [torch.cat([rgb, uv], dim=1), flow], y
+        slow = torch.cat([rgb, uv], dim=1)
+        if "mix" in batch:                               # the float batch: one launch per pathway tensor, through their (N,T,C,S,S) views
+            flow = flow.contiguous()                     # (the permuted view is the loader's own memory on a device batch)
+            for x in (slow, flow):
+                self._mix_clip(torch.permute(x, [0, 2, 1, 3, 4]), batch)
+        return [slow, flow], y
 
 
 class Trainer(_train.Trainer):
@@ -375,7 +386,10 @@ class Trainer(_train.Trainer):
             raise ValueError("MODEL.WEIGHT_DECAY_MODE: decoupled needs Adam; the v2 trainer runs SGD (torch has no decoupled "
                              "SGD): set WEIGHT_DECAY_MODE: l2")
         return _train.TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer, optimizer="sgd",
-                                momentum=self.momentum, **kw)
+                                momentum=self.momentum, **kw, **self._mix_kwargs())
+
+    def mix_frame(self) -> int:
+        return int(self.cfg.MODEL.INPUT_SIZE)
 
     def _offers_resident(self, train_set) -> bool:
         from .input_pipeline import GESTURE_METHODS, offers_resident

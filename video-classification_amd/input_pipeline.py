@@ -27,6 +27,7 @@ numerically this step is "parity unpinned" against torchvision itself (tests/tes
 from __future__ import annotations
 
 import bisect
+import math
 
 from dataclasses import dataclass
 from typing import Optional
@@ -124,6 +125,107 @@ class ColorJitter:
         assert tuple(params.shape) == (n, 8), tuple(params.shape)
         stream = stream_of(self.device)
         self.be.color_jitter(clip, params, self.workspace(n, t, h, w), c_off, bgr, mean, std)(stream)
+        return clip
+
+
+def identity_mix_rows(n: int) -> torch.Tensor:
+    """(n, 8) float32 identity rows of the mix table (include/sfk_mix.h): {own index, 1, 0, 0, 0, 0, 1, 0}"""
+    out = torch.zeros(n, 8, dtype=torch.float32)
+    out[:, 0] = torch.arange(n, dtype=torch.float32)
+    out[:, 1] = 1.0
+    out[:, 6] = 1.0
+    return out
+
+
+def _draw_beta(alpha: float, generator: Optional[torch.Generator]) -> float:
+    """one Beta(alpha, alpha) draw as g1 / (g1 + g2) of two Gamma(alpha, 1) draws (float64) from ``generator``"""
+    g = torch._standard_gamma(torch.full((2,), float(alpha), dtype=torch.float64), generator=generator)
+    s = float(g[0] + g[1])
+    return float(g[0]) / s if s > 0 else 0.5
+
+
+def draw_mix(n: int, h: int, w: int, mixup_alpha: float = 0.0, cutmix_alpha: float = 0.0, prob: float = 1.0,
+             switch_prob: float = 0.5, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """(n, 8) float32 rows {partner, lam, y0, x0, y1, x1, weight, 0} for ``sfk_clip_mix`` / ``sfk_softmax_ce_mix``
+    (include/sfk_mix.h) on frames of h x w.  Pairing is the flip i <-> n-1-i (the loader's batch is already shuffled); the
+    middle clip of an odd batch pairs with itself and keeps the identity row, without a draw.  One draw per pair, shared by
+    both members, in this order: u ~ U[0, 1): u >= prob gives identity rows; when both alphas are > 0, v ~ U[0, 1): v <
+    switch_prob chooses CutMix (else whichever alpha is > 0); lam ~ Beta(alpha, alpha).  Mixup: lam as drawn, an empty box,
+    weight = lam.  CutMix: lam = 1 and the usual box -- sides int(h sqrt(1 - lam)), int(w sqrt(1 - lam)), centre (cy, cx)
+    uniform over the frame (cy first), [c - side // 2, c + side // 2) clipped to the frame -- and weight = 1 - box area /
+    (h w) after clipping.  Stated in plain torch: timm is not installed here, parity with timm itself is unpinned."""
+    assert n > 0 and h > 0 and w > 0 and mixup_alpha >= 0 and cutmix_alpha >= 0 and 0 <= prob <= 1 and 0 <= switch_prob <= 1
+    out = identity_mix_rows(n)
+    if mixup_alpha <= 0 and cutmix_alpha <= 0:
+        return out
+    for i in range(n // 2):
+        j = n - 1 - i
+        out[i, 0], out[j, 0] = float(j), float(i)
+        if float(torch.rand(1, generator=generator)) >= prob:
+            continue
+        cut = cutmix_alpha > 0 and (mixup_alpha <= 0 or float(torch.rand(1, generator=generator)) < switch_prob)
+        lam = _draw_beta(cutmix_alpha if cut else mixup_alpha, generator)
+        if cut:
+            ratio = math.sqrt(max(0.0, 1.0 - lam))
+            ch, cw = int(h * ratio), int(w * ratio)
+            cy = int(torch.randint(0, h, (1,), generator=generator))
+            cx = int(torch.randint(0, w, (1,), generator=generator))
+            y0, y1 = min(max(cy - ch // 2, 0), h), min(max(cy + ch // 2, 0), h)
+            x0, x1 = min(max(cx - cw // 2, 0), w), min(max(cx + cw // 2, 0), w)
+            row = [1.0, y0, x0, y1, x1, 1.0 - ((y1 - y0) * (x1 - x0)) / float(h * w)]
+        else:
+            row = [lam, 0, 0, 0, 0, lam]
+        out[i, 1:7] = out[j, 1:7] = torch.tensor(row, dtype=torch.float32)
+    return out
+
+
+class ClipMix:
+    """Mixup / CutMix of a float clip batch (N, T, C, H, W) that already lives on the device, IN PLACE, by ``sfk_clip_mix``
+    (include/sfk_mix.h): one launch on the current stream that reads both members of a pair once and writes both, with no
+    second clip.  The object owns ONE device table of ``batch_size`` rows: ``load`` validates a batch's host rows
+    (``draw_mix``) and copies them into its first n rows, so the table's address is the same from step to step and a
+    captured train step (``TrainStep(..., mix=table)``) follows every new draw."""
+
+    def __init__(self, device="cuda", backend=None, batch_size: int = 1):
+        self.be, self.device = hip_backend(backend), torch.device(device)
+        self.table = identity_mix_rows(int(batch_size)).to(self.device)
+
+    @staticmethod
+    def validate(rows: torch.Tensor, h: int, w: int) -> torch.Tensor:
+        """the host rows as contiguous float32, or ValueError: a partner outside [0, n) or not mutual, lam or weight outside
+        [0, 1], a box outside the h x w frame"""
+        rows = rows.detach().to("cpu", torch.float32).contiguous()
+        if rows.dim() != 2 or rows.shape[1] != 8:
+            raise ValueError(f"mix rows must be (n, 8), got {tuple(rows.shape)}")
+        n = rows.shape[0]
+        part = rows[:, 0]
+        if not bool(((part >= 0) & (part < n) & (part == part.floor())).all()):
+            raise ValueError(f"mix rows: a partner is outside [0, {n})")
+        pi = part.long()
+        if not bool((pi[pi] == torch.arange(n)).all()):
+            raise ValueError("mix rows: a partner is not mutual (partner[partner[i]] != i)")
+        for name, col in (("lam", 1), ("weight", 6)):
+            if not bool(((rows[:, col] >= 0) & (rows[:, col] <= 1)).all()):
+                raise ValueError(f"mix rows: a {name} is outside [0, 1]")
+        y0, x0, y1, x1 = rows[:, 2], rows[:, 3], rows[:, 4], rows[:, 5]
+        if not bool(((y0 >= 0) & (x0 >= 0) & (y1 <= h) & (x1 <= w) & (y0 <= h) & (x0 <= w) & (y1 >= 0) & (x1 >= 0)).all()):
+            raise ValueError(f"mix rows: a box is outside the {h} x {w} frame")
+        return rows
+
+    def load(self, rows: torch.Tensor, h: int, w: int) -> torch.Tensor:
+        """validate (n, 8) host rows for frames of h x w, copy them into the first n rows of the table, return that view"""
+        rows = self.validate(rows, h, w)
+        n = rows.shape[0]
+        if n > self.table.shape[0]:
+            raise ValueError(f"{n} mix rows for a table of {self.table.shape[0]} (the batch size it was built for)")
+        view = self.table[:n]
+        view.copy_(h2d(rows, self.device), non_blocking=True)
+        return view
+
+    def __call__(self, clip: torch.Tensor, table: torch.Tensor, c_off: int = 0, c: Optional[int] = None) -> torch.Tensor:
+        assert clip.dim() == 5 and clip.stride(4) == 1 and clip.device.type == self.device.type
+        assert table.dtype == torch.float32 and tuple(table.shape) == (clip.shape[0], 8), tuple(table.shape)
+        self.be.clip_mix(clip, table, c_off, c)(stream_of(self.device))
         return clip
 
 

@@ -47,7 +47,7 @@ class TrainStep:
                  reducer: Optional[sdist.GradReducer] = None, overlap_segments: int = 6, optimizer: str = "adam",
                  momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False, lr_table=None,
                  weight_decay: float = 0.0, decay_mode: str = "none", decay_scope: str = "weights",
-                 clip_grad_norm: float = 0.0):
+                 clip_grad_norm: float = 0.0, label_smoothing: float = 0.0):
         """optimizer 'adam' (train.py:182: lr, betas, eps) or 'sgd' (the v2 trainer, new_feature_test.py:832: lr, momentum,
         dampening, nesterov; one sfk_sgd launch over the arena, never split beside the last kernel).
 
@@ -59,8 +59,15 @@ class TrainStep:
         'decoupled' (AdamW; Adam only) over decay_scope 'weights' (conv filters and the FC weight) | 'all'; clip_grad_norm
         > 0 runs sfk_grad_norm over the finished (reduced) gradients before one optimizer launch -- clip_grad_norm_(max_norm)
         -- and leaves (norm, coefficient) in self.grad_norm.  The optimizer state and the step count are not checkpointed
-        (as in the reference), so a resumed run starts the table again."""
+        (as in the reference), so a resumed run starts the table again.
+
+        label_smoothing in [0, 1) and the ``mix`` table of a call (include/sfk_mix.h: two labels with a weight per clip): at
+        0 and None the loss launch is sfk_softmax_ce as ever; otherwise the one sfk_softmax_ce_mix launch takes its place
+        and nothing else of the step changes."""
         self.eng = engine
+        self.label_smoothing = float(label_smoothing)
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
         opt = self.opt = Optimizer(engine, optimizer, lr, betas, eps, momentum, dampening, nesterov, lr_table, weight_decay,
                                    decay_mode, decay_scope, clip_grad_norm)      # validates the keywords; allocates no state
         self.optimizer, self.momentum, self.hp, self.lr_table = opt.optimizer, opt.momentum, opt.hp, opt.lr_table
@@ -96,11 +103,15 @@ class TrainStep:
     grad_norm = property(lambda self: self.opt.grad_norm, doc="device float32[2] (norm, coefficient) of the last step; None "
                          "until a clipped step has been built")
 
-    def _build(self, pl, labels):
+    def _build(self, pl, labels, mix=None):
         eng, opt = self.eng, self.opt
         gscale = self.reducer.grad_scale if self.reducer is not None else 1.0
+        if self.label_smoothing == 0.0 and mix is None:
+            loss = eng.loss_ops(pl, labels, self.loss, self.loss_sum, self.correct)
+        else:
+            loss = eng.loss_ops(pl, labels, self.loss, self.loss_sum, self.correct, label_smoothing=self.label_smoothing, mix=mix)
         ops = dict(
-            loss=eng.loss_ops(pl, labels, self.loss, self.loss_sum, self.correct),
+            loss=loss,
             zero_loss=eng.be.fill_zero(self.loss),
             zero_grad=eng.be.fill_zero(eng.G),
         )
@@ -151,16 +162,20 @@ class TrainStep:
             ops["grad_norm"](st)
         ops["adam"](st)
 
-    def __call__(self, x_slow, x_fast, labels, slow_t_index=None) -> torch.Tensor:
+    def __call__(self, x_slow, x_fast, labels, slow_t_index=None, mix=None) -> torch.Tensor:
+        """mix: None, or the (N, 8) float32 device table of the batch's mix rows (input_pipeline.ClipMix.load): the loss takes
+        its soft target from it.  Its CONTENTS are read when the launch runs; its address is part of the cache key."""
         eng = self.eng
         x_slow = eng.input_view(x_slow)      # res2d: the (N, C, T, H, W) view of its stacked-frames input; else x as it is
         pl = eng._plan_for(x_slow, x_fast, slow_t_index, True)
-        key = (pl.serial, labels.data_ptr(), pl.graph_epoch)
+        if mix is not None:
+            assert mix.dtype == torch.float32 and mix.is_contiguous() and tuple(mix.shape) == (labels.shape[0], 8), tuple(mix.shape)
+        key = (pl.serial, labels.data_ptr(), pl.graph_epoch) + (() if mix is None else (mix.data_ptr(),))
         ent = self._cache.get(key)
         if ent is None:
             if len(self._cache) > 4:
                 self._cache.clear()
-            ent = {"ops": self._build(pl, labels), "graph": None, "calls": 0, "labels": labels}
+            ent = {"ops": self._build(pl, labels, mix), "graph": None, "calls": 0, "labels": labels, "mix": mix}
             self._cache[key] = ent
         ent["calls"] += 1
         if not self.use_graph:
@@ -187,6 +202,23 @@ class TrainStep:
         return self.loss
 
 
+def mix_settings(cfg):
+    """MODEL.LABEL_SMOOTHING and the MODEL.MIX* keys: (label_smoothing, draw_mix keywords | None, seed).  The keywords are
+    None when both alphas are 0: no table is drawn, no clip is mixed."""
+    m = cfg.MODEL
+    eps = float(m.get("LABEL_SMOOTHING", 0.0))
+    mixup, cutmix = float(m.get("MIXUP_ALPHA", 0.0)), float(m.get("CUTMIX_ALPHA", 0.0))
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"MODEL.LABEL_SMOOTHING must be in [0, 1), got {eps}")
+    if mixup < 0 or cutmix < 0:
+        raise ValueError(f"MODEL.MIXUP_ALPHA / MODEL.CUTMIX_ALPHA must be >= 0, got {mixup} / {cutmix}")
+    draw = None
+    if mixup > 0 or cutmix > 0:
+        draw = dict(mixup_alpha=mixup, cutmix_alpha=cutmix, prob=float(m.get("MIX_PROB", 1.0)),
+                    switch_prob=float(m.get("MIX_SWITCH_PROB", 0.5)))
+    return eps, draw, int(m.get("MIX_SEED", 0))
+
+
 def jitter_ranges(cfg):
     """MODEL.COLOR_JITTER on: the (brightness, contrast, saturation, hue) ranges of MODEL.JITTER_*; off: None"""
     m = cfg.MODEL
@@ -209,6 +241,7 @@ class ModelManager:
         self._pre = None
         self._lut = None
         self._jit = None
+        self._mix = None
         self._resize = None
         name = cfg.MODEL.NAME
         self.arch = str(cfg.MODEL.get("ARCH", "ref")).lower()
@@ -286,17 +319,21 @@ class ModelManager:
             return None
         if "jitter" in batch:
             raise ValueError(self._NO_FLOAT_CLIP.format("POOL_STEM"))
+        if "mix" in batch:
+            raise ValueError(self._NO_FLOAT_CLIP_MIX.format("POOL_STEM"))
         return list(x)
 
     _NO_FLOAT_CLIP = ("MODEL.{0}: true reads the uint8 frames in the stems, so there is no float clip for the "
                       "batch's 'jitter' entry to work on; turn {0} or MODEL.COLOR_JITTER off")
+    _NO_FLOAT_CLIP_MIX = ("MODEL.{0}: true reads the uint8 frames in the stems, so there is no float clip for the "
+                          "batch's 'mix' entry to work on; turn {0} or MODEL.MIXUP_ALPHA / MODEL.CUTMIX_ALPHA off")
 
     def _u8_float(self, batch) -> torch.Tensor:
-        """DevicePreprocess: (N,T,S,S,P) uint8 -> (N,T,P,S,S) float32 on the device (then the batch's 'jitter', if any)"""
+        """DevicePreprocess: (N,T,S,S,P) uint8 -> (N,T,P,S,S) float32 on the device (then the batch's 'jitter' and 'mix', if any)"""
         if self._pre is None:
             from .input_pipeline import DevicePreprocess
             self._pre = DevicePreprocess(self.device, self.backend)
-        return self._jitter_v1(self._pre(batch[self._u8_key(batch)], batch.get("crop")), batch)
+        return self._mix_clip(self._jitter_v1(self._pre(batch[self._u8_key(batch)], batch.get("crop")), batch), batch)
 
     # ---- the device-side ColorJitter: a batch carrying 'jitter' (N,8), the draws of input_pipeline.draw_color_jitter
     def color_jitter(self) -> "ColorJitter":
@@ -305,18 +342,43 @@ class ModelManager:
             self._jit = ColorJitter(self.device, self.backend)
         return self._jit
 
+    # ---- the device-side Mixup / CutMix: a batch carrying 'mix', the (N,8) device table of input_pipeline.ClipMix.load
+    def clip_mix(self, batch_size: int = 1) -> "ClipMix":
+        """the ClipMix object, its table grown to batch_size rows (the Trainer asks once, before the first step)"""
+        if self._mix is None or self._mix.table.shape[0] < batch_size:
+            from .input_pipeline import ClipMix
+            self._mix = ClipMix(self.device, self.backend, batch_size)
+        return self._mix
+
+    def _mix_clip(self, x: torch.Tensor, batch) -> torch.Tensor:
+        """Mixup / CutMix of the float (N,T,C,S,S) clip with its partner clip, in place, when the batch carries 'mix': after
+        the crop and the jitter, before the permute and the channel slices, so one launch serves both pathways.  The
+        channels the model reads are mixed (mix_channels), the others stay as they are."""
+        if "mix" not in batch:
+            return x
+        return self.clip_mix()(x, batch["mix"], 0, min(self.mix_channels(), x.shape[2]))
+
+    def mix_channels(self) -> int:
+        """the leading channels of the (N,T,21,S,S) loader clip the model reads, which are the ones worth mixing: B, G, R for the
+        canonical stems, BGR+UV and the flow (the depth channel, 20, is dropped) for SlowFast, BGR+UV for res3d and res2d"""
+        if self.arch == "canonical8x8":
+            return 3
+        return 20 if "slowfast" in self.cfg.MODEL.NAME else 5
+
     @staticmethod
     def _own(x: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
-        """x as a unit-stride tensor that is not the loader's own memory (the jitter works in place)"""
+        """x as a unit-stride tensor that is not the loader's own memory (the jitter and the mix work in place)"""
         if x.stride(-1) != 1:
             return x.contiguous()
         return x.clone() if x.untyped_storage().data_ptr() == src.untyped_storage().data_ptr() else x
 
     def _float_clip(self, batch) -> torch.Tensor:
-        """the float32 (N,T,21,S,S) loader batch on the device (then the batch's 'jitter', if any)"""
+        """the float32 (N,T,21,S,S) loader batch on the device (then the batch's 'jitter' and 'mix', if any)"""
         src = batch[self.cfg.MODEL.R3D_INPUT]
         x = self._h2d(src)
-        return self._jitter_v1(self._own(x, src), batch) if "jitter" in batch else x
+        if "jitter" not in batch and "mix" not in batch:
+            return x
+        return self._mix_clip(self._jitter_v1(self._own(x, src), batch), batch)
 
     def _jitter_v1(self, x: torch.Tensor, batch) -> torch.Tensor:
         """ColorJitter on channels 0..2 (B, G, R: cv2.imread order) of the normalised (N,T,21,S,S) clip, in place, when the
@@ -333,6 +395,8 @@ class ModelManager:
         from .input_pipeline import normalize_lut, u8_pathways
         if "jitter" in batch:
             raise ValueError(self._NO_FLOAT_CLIP.format("U8_STEM"))
+        if "mix" in batch:
+            raise ValueError(self._NO_FLOAT_CLIP_MIX.format("U8_STEM"))
         if self._lut is None:
             self._lut = normalize_lut().to(self.device)
         frames = self._h2d(batch[self._u8_key(batch)])
@@ -377,6 +441,8 @@ class ModelManager:
             return self._float_clip(batch)[:, :, :5], self._h2d(batch['label'])
         if "jitter" in batch:
             raise ValueError("a 'jitter' entry needs MODEL.RES2D_BACKEND = 'engine' (the torch backend has no device kernels)")
+        if "mix" in batch:
+            raise ValueError("a 'mix' entry needs MODEL.RES2D_BACKEND = 'engine' (the torch backend has no device kernels)")
         dev = "cpu" if torch.device(self.device).type != "cuda" else self.device
         x = batch[self.cfg.MODEL.R3D_INPUT][:, :, :5].to(dev)
         n, t, c, h, w = x.size()
@@ -468,7 +534,8 @@ class ModelManager:
         A batch that carries ``<R3D_INPUT>_u8`` (N,T,S,S,21 uint8 frames, optional ``crop`` (N,2)) instead of the float32
         tensor takes the uint8 transport: normalise + RandomCrop run on the device (input_pipeline.py), or, with
         MODEL.U8_STEM, inside the two stems, which read the frames as U8Clips over channels 0:5 and 5:20.
-        An optional ``jitter`` (N,8) entry applies ColorJitter to the B, G, R planes of the float clip (_jitter_v1)."""
+        An optional ``jitter`` (N,8) entry applies ColorJitter to the B, G, R planes of the float clip (_jitter_v1); an
+        optional ``mix`` entry (the device table of ClipMix.load) then mixes the clip with its partner (_mix_clip)."""
         batch = self._resized(batch)
         clips = self._pool_clips(batch)                  # MODEL.POOL_STEM on a pooled route: PoolClips over channels 0:5 and 5:20
         if clips is not None:
@@ -794,6 +861,7 @@ class Trainer:
         self.max_historical_acc = 0.
         self.load_ckpt()
         eng = getattr(self.model, "engine", None)
+        self.label_smoothing, self.mix_draw, self.mix_seed = mix_settings(cfg)
         # Adam is created AFTER the checkpoint load, its state is never saved (train.py:180-182)
         if eng is None:                                  # res2d: a plain torch module, the reference's own five lines
             from .res2d import TorchStep
@@ -801,10 +869,15 @@ class Trainer:
             if self._optim_kwargs():
                 raise ValueError("MODEL.LR_SCHEDULE / WEIGHT_DECAY / CLIP_GRAD_NORM need the engine's optimizer launch: MODEL.NAME "
                                  "res2d with the torch backend is host plumbing (torch.optim.Adam); use RES2D_BACKEND = 'engine'")
+            if self.label_smoothing > 0 or self.mix_draw is not None:
+                raise ValueError("MODEL.LABEL_SMOOTHING / MIXUP_ALPHA / CUTMIX_ALPHA need the engine's loss launch: MODEL.NAME res2d "
+                                 "with the torch backend is host plumbing (nn.CrossEntropyLoss); use RES2D_BACKEND = 'engine'")
             self.step = TorchStep(self.model, lr=cfg.MODEL.LR)
         else:
             reducer = sdist.GradReducer(eng.G, bucket_mb=cfg.DIST.BUCKET_MB) if self.world > 1 else None
             self.step = self._make_step(eng, use_graph, reducer)
+            if self.mix_draw is not None:                # the one device table every step's rows are written into
+                self.mm.clip_mix(int(self.batch_size))
 
     # ---- what a derived trainer (gesture_v2.Trainer) swaps: the model manager, the optimiser, the train loader's drop_last
     train_drop_last = True                               # train.py:164
@@ -826,8 +899,30 @@ class Trainer:
         from .schedule import optim_kwargs
         return optim_kwargs(self.cfg, self.steps_per_epoch)
 
+    def _mix_kwargs(self) -> dict:
+        """MODEL.LABEL_SMOOTHING as a TrainStep keyword ({} at the default)"""
+        return {"label_smoothing": self.label_smoothing} if self.label_smoothing > 0 else {}
+
+    def mix_frame(self) -> int:
+        """the side of the square frames the mix boxes are drawn on"""
+        return int(crop_resize_dict[self.cfg.MODEL.R3D_INPUT])
+
+    def _mix_generator(self) -> torch.Generator:
+        """the epoch's generator of the mix draws, seeded by (MODEL.MIX_SEED, epoch, rank) and advanced per step"""
+        return torch.Generator().manual_seed(((self.mix_seed * 1000003 + int(self.epoch)) * 1000003 + int(self.rank)) % (2 ** 63))
+
+    def _attach_mix(self, batch, gen):
+        """draw the batch's mix rows, write them into the device table, attach the table's first n rows as batch['mix']"""
+        from .input_pipeline import draw_mix
+        n, s = int(batch["label"].shape[0]), self.mix_frame()
+        table = self.mm.clip_mix(n).load(draw_mix(n, s, s, generator=gen, **self.mix_draw), s, s)
+        batch = dict(batch)
+        batch["mix"] = table
+        return batch, table
+
     def _make_step(self, eng, use_graph, reducer):
-        return TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer, **self._optim_kwargs())
+        return TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer, **self._optim_kwargs(),
+                         **self._mix_kwargs())
 
     def _reference_datasets(self):
         try:
@@ -938,12 +1033,16 @@ class Trainer:
         if getattr(self, "train_sampler", None) is not None:
             self.train_sampler.set_epoch(self.epoch)     # a new permutation of the epoch, the same on every rank
         resident = getattr(self, "resident", None)       # MODEL.RESIDENT_TRAIN: clips gathered from the frames on the device
+        mix_gen = self._mix_generator() if self.mix_draw is not None else None
         for batch in (self.train_loader if resident is None else resident.epoch(self.epoch)):
+            kw = {}
+            if mix_gen is not None:                      # MODEL.MIXUP_ALPHA / CUTMIX_ALPHA: the clip and the loss share one table
+                batch, kw["mix"] = self._attach_mix(batch, mix_gen)
             x, y_true = self.mm.prepare_data(batch)
             if isinstance(x, (torch.Tensor,) + STEM_CLIPS):    # res3d / res2d: one input tensor (or uint8 clip)
-                self.step(x, None, y_true)
+                self.step(x, None, y_true, **kw)
             else:
-                self.step(x[0], x[1], y_true, slow_t_index=self.model.slow_t_index)
+                self.step(x[0], x[1], y_true, slow_t_index=self.model.slow_t_index, **kw)
             self.num_step += 1
             seen += int(y_true.shape[0])
             if self.debug:
