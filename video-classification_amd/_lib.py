@@ -243,6 +243,19 @@ class _MixDesc(C.Structure):
                 ("w", C.c_int32), ("c_off", C.c_int32), ("rows", C.c_void_p)]
 
 
+class _EmaTensor(C.Structure):
+    """include/sfk_ema.h sfk_ema_tensor: a live tensor outside the arena and its average, n elements each"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("n", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class _EmaDesc(C.Structure):
+    """include/sfk_ema.h sfk_ema_desc: the live arena p, its average e, the device table of small tensors, the rate and the
+    device step counter shared by sfk_ema_update and sfk_ema_swap"""
+    _fields_ = [("struct_size", C.c_uint32), ("warmup", C.c_int32), ("p", C.c_void_p), ("e", C.c_void_p), ("count", C.c_int64),
+                ("table", C.c_void_p), ("ntensors", C.c_int32), ("reserved0", C.c_int32), ("decay", C.c_double),
+                ("step", C.c_void_p)]
+
+
 class _OptimHp(C.Structure):
     """include/sfk_optim.h sfk_optim_hp: the device learning-rate table, weight decay and clipping coefficient shared by
     sfk_adam_hp and sfk_sgd_hp"""
@@ -507,6 +520,15 @@ SIGNATURES_MIX = {
     "sfk_clip_mix": [C.POINTER(_MixDesc), _PV],
     "sfk_softmax_ce_mix": [_PF, _PV, _PF, _F, _I32, _I32, _F, _PF, _PF, _PF, _PV, _PV],
 }
+# include/sfk_ema.h: the exponential moving average of the weights and the exchange that evaluates it, same library, its own
+# header and version
+EMA_ABI_VERSION = 1        # include/sfk_ema.h SFK_EMA_ABI_VERSION
+EMA_MAX_TENSORS = 4096     # include/sfk_ema.h SFK_EMA_MAX_TENSORS
+SIGNATURES_EMA = {
+    "sfk_ema_abi_version": [],
+    "sfk_ema_update": [C.POINTER(_EmaDesc), _PV],
+    "sfk_ema_swap": [C.POINTER(_EmaDesc), _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_groups_prepare": C.c_int64, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
@@ -558,6 +580,24 @@ def new_mix_desc() -> "_MixDesc":
     d = _MixDesc()
     d.struct_size = C.sizeof(_MixDesc)
     return d
+
+
+def new_ema_desc() -> "_EmaDesc":
+    d = _EmaDesc()
+    d.struct_size = C.sizeof(_EmaDesc)
+    return d
+
+
+class EmaTable:
+    """The table of include/sfk_ema.h, ready to launch: the (src, dst) tensors it points into, kept alive, and its device
+    copy (None when it has no entry).  Built once (HipBackend.ema_table) and shared by the update and the swap."""
+
+    def __init__(self, pairs, dev):
+        self.pairs, self.dev = pairs, dev
+
+    @property
+    def ntensors(self) -> int:
+        return len(self.pairs)
 
 
 def new_pool_desc() -> "_PoolDesc":
@@ -628,7 +668,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib = C.CDLL(path)
     for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL,
                   SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL, SIGNATURES_ROI_RAGGED, SIGNATURES_U8STEM_POOL,
-                  SIGNATURES_OPTIM, SIGNATURES_GROUPS, SIGNATURES_MIX):
+                  SIGNATURES_OPTIM, SIGNATURES_GROUPS, SIGNATURES_MIX, SIGNATURES_EMA):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -661,6 +701,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk groups ABI version mismatch: library {lib.sfk_groups_abi_version()}, binding {GROUPS_ABI_VERSION}")
     if lib.sfk_mix_abi_version() != MIX_ABI_VERSION:
         raise SfkError(f"libsfk mix ABI version mismatch: library {lib.sfk_mix_abi_version()}, binding {MIX_ABI_VERSION}")
+    if lib.sfk_ema_abi_version() != EMA_ABI_VERSION:
+        raise SfkError(f"libsfk ema ABI version mismatch: library {lib.sfk_ema_abi_version()}, binding {EMA_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -1313,6 +1355,48 @@ class HipBackend:
         d.sn, d.st, d.sc, d.sh = clip.stride()[:4]
         d.n, d.t, d.c, d.h, d.w, d.c_off = n, t, c, h, w, c_off
         return self._plain("sfk_clip_mix", C.byref(d), keep=(d, clip, rows))
+
+    def ema_table(self, pairs) -> EmaTable:
+        """pairs: (src, dst) float32 contiguous tensors of equal size on one device, src the live tensor and dst its average
+        (include/sfk_ema.h sfk_ema_tensor).  Validates, uploads the table once and keeps the tensors alive."""
+        pairs = [(s, d) for s, d in pairs]
+        if len(pairs) > EMA_MAX_TENSORS:
+            raise SfkError(f"sfk_ema table: {len(pairs)} tensors, the cap is {EMA_MAX_TENSORS}")
+        host = (_EmaTensor * max(len(pairs), 1))()
+        for k, (s, d) in enumerate(pairs):
+            for t in (s, d):
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.device != pairs[0][0].device:
+                    raise SfkError(f"sfk_ema table entry {k}: float32 contiguous tensors on one device")
+            if s.numel() != d.numel() or s.numel() < 1 or s.numel() >= 2 ** 31 or s.data_ptr() == d.data_ptr():
+                raise SfkError(f"sfk_ema table entry {k}: src and dst are two tensors of the same size ({s.numel()}, {d.numel()})")
+            host[k] = _EmaTensor(s.data_ptr(), d.data_ptr(), s.numel(), 0)
+        dev = None
+        if pairs:
+            raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8)[:len(pairs) * C.sizeof(_EmaTensor)]
+            dev = raw.to(pairs[0][0].device)
+        return EmaTable(pairs, dev)
+
+    @staticmethod
+    def _ema_desc(p, e, count, table, decay, warmup, step):
+        assert p.dtype == torch.float32 and e.dtype == torch.float32 and p.is_contiguous() and e.is_contiguous()
+        assert 0 < count <= p.numel() and count <= e.numel() and p.data_ptr() != e.data_ptr()
+        assert step is None or (step.dtype == torch.int64 and step.numel() >= 1)
+        d = new_ema_desc()
+        d.p, d.e, d.count, d.warmup, d.decay, d.step = p.data_ptr(), e.data_ptr(), int(count), 1 if warmup else 0, float(decay), _ptr(step)
+        if table is not None:
+            d.table, d.ntensors = _ptr(table.dev), table.ntensors
+        return d
+
+    def ema_update(self, p, e, count, table: Optional[EmaTable], decay: float, warmup: bool, step):
+        """sfk_ema_update (include/sfk_ema.h): step[0] += 1 = t, w = (float)(1 - (warmup ? min(decay, (1 + t) / (10 + t)) :
+        decay)), then e = e + w * (p - e) over the first count elements of the arenas and over every table pair"""
+        d = self._ema_desc(p, e, count, table, decay, warmup, step)
+        return self._plain("sfk_ema_update", C.byref(d), keep=(d, p, e, table, step))
+
+    def ema_swap(self, p, e, count, table: Optional[EmaTable]):
+        """sfk_ema_swap (include/sfk_ema.h): the bits of p and e, and of every table pair, exchanged"""
+        d = self._ema_desc(p, e, count, table, 0.0, False, None)
+        return self._plain("sfk_ema_swap", C.byref(d), keep=(d, p, e, table))
 
     @staticmethod
     def _fill_pool_desc(d, pool, index, lut, fill, out, c0, c):

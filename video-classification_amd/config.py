@@ -113,6 +113,9 @@ _C.MODEL.CUTMIX_ALPHA = 0.0        # > 0: CutMix, the partner's box pasted; both
 _C.MODEL.MIX_PROB = 1.0            # the probability that a pair is mixed at all
 _C.MODEL.MIX_SWITCH_PROB = 0.5
 _C.MODEL.MIX_SEED = 0              # the draws come from a generator seeded by (MIX_SEED, epoch, rank), in the main process
+_C.MODEL.EMA_DECAY = 0.0           # > 0: keep an exponential moving average of the weights and BatchNorm statistics on the device (include/sfk_ema.h); 0: nothing is built
+_C.MODEL.EMA_WARMUP = False        # the rate of step t is min(EMA_DECAY, (1 + t) / (10 + t)) (timm's ModelEmaV2)
+_C.MODEL.EMA_EVAL = 'ema'          # what train() evaluates and saves with EMA on: 'ema' | 'live' | 'both' (both accuracies printed; the averaged model selects and is saved)
 _C.MODEL.RESIDENT_TRAIN = False  # keep the decoded train frames on the device and gather the cropped clips there (input_pipeline.ResidentTrainSet)
 _C.MODEL.RESIDENT_GB = 32.0     # RESIDENT_TRAIN: the size of the frame arena, GiB (its last BATCH_SIZE * CLIP_LEN slots are the spill region)
 _C.MODEL.RESIDENT_STORE = 'frame'  # v2 RESIDENT_TRAIN: 'frame' keeps whole frames in a FramePool, 'box' only each video's part-box rectangle in a BoxArena of RESIDENT_GB bytes

@@ -287,6 +287,10 @@ class Engine:
         self.sgd_step = None
         self.grad_norm = None          # (norm, clipping coefficient) of the last clipped step: optim_state
         self.grad_norm_parts = None
+        self.ema_P = None              # the averaged arena, the averaged rm / rv of every layer, the counter, the table: optim_state
+        self.ema_stats = None
+        self.ema_step = None
+        self.ema_table = None
         # compute-precision copies of the filters: S = [cout][tap][cin] (forward, filter-gradient layout),
         # St = [cin][tap][cout] (data-gradient pass)
         self.S = self.P.data if self.dtype == torch.float32 else self._new(self.conv_total, dtype=self.dtype)
@@ -1333,7 +1337,9 @@ class Engine:
         attribute is None until then.  ONE tensor per engine, so that every cached TrainStep entry bakes in the same pointers.
         'adam': the moments, the step counter and the scratch counter of the split update's second launch; 'sgd': the momentum
         buffer and a step counter of its own (arena entries without a live parameter keep G == 0 and stay as they are, as in
-        torch); 'grad_norm': (norm, clipping coefficient) of the last clipped step and sfk_grad_norm's partial rows."""
+        torch); 'grad_norm': (norm, clipping coefficient) of the last clipped step and sfk_grad_norm's partial rows; 'ema' (include/sfk_ema.h,
+        ema.WeightEma): the averaged arena and the averaged running statistics, both copies of the live ones, their step
+        counter and the uploaded table."""
         n = self.arena_numel
         if kind == "adam" and self.adam_m is None:
             self.adam_m, self.adam_v = self._new(n), self._new(n)
@@ -1343,6 +1349,23 @@ class Engine:
         elif kind == "grad_norm" and self.grad_norm is None:
             self.grad_norm = self._new(2)
             self.grad_norm_parts = self._new(self.be.grad_norm_parts(n), dtype=torch.float64)
+        elif kind == "ema" and self.ema_P is None:
+            # the average starts as a copy of the live model (ema.WeightEma.reset re-copies it); the table's dst entries are
+            # views into ONE buffer, layer after layer (rm, rv)
+            self.ema_P = self.P.data.clone()
+            self.ema_stats = torch.cat([t.reshape(-1) for L in self.layers for t in (L.rm, L.rv)])     # cat copies
+            self.ema_step = self._new(1, dtype=torch.int64)
+            self.ema_table = self.be.ema_table(self.ema_stat_pairs())
+
+    def ema_stat_pairs(self) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        """(live, averaged) running mean and running variance of every layer, in the table's order; the averaged ones are
+        views into ema_stats"""
+        pairs, off = [], 0
+        for L in self.layers:
+            for live in (L.rm, L.rv):
+                pairs.append((live, self.ema_stats[off:off + L.c]))
+                off += L.c
+        return pairs
 
     def decay_count(self, scope: str) -> int:
         """arena elements [0, decay_count) decay: 'weights' = the conv filters and the FC weight (the arena is conv filters |

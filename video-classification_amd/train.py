@@ -17,6 +17,7 @@ What differs from /root/reference/train.py, and why:
 """
 from __future__ import annotations
 
+import contextlib
 import glob
 import os
 from pathlib import Path
@@ -47,7 +48,7 @@ class TrainStep:
                  reducer: Optional[sdist.GradReducer] = None, overlap_segments: int = 6, optimizer: str = "adam",
                  momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False, lr_table=None,
                  weight_decay: float = 0.0, decay_mode: str = "none", decay_scope: str = "weights",
-                 clip_grad_norm: float = 0.0, label_smoothing: float = 0.0):
+                 clip_grad_norm: float = 0.0, label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = False):
         """optimizer 'adam' (train.py:182: lr, betas, eps) or 'sgd' (the v2 trainer, new_feature_test.py:832: lr, momentum,
         dampening, nesterov; one sfk_sgd launch over the arena, never split beside the last kernel).
 
@@ -63,8 +64,19 @@ class TrainStep:
 
         label_smoothing in [0, 1) and the ``mix`` table of a call (include/sfk_mix.h: two labels with a weight per clip): at
         0 and None the loss launch is sfk_softmax_ce as ever; otherwise the one sfk_softmax_ce_mix launch takes its place
-        and nothing else of the step changes."""
+        and nothing else of the step changes.
+
+        ema_decay in [0, 1), ema_warmup (include/sfk_ema.h, ema.WeightEma): at 0 self.ema is None and the step issues exactly
+        the launches above.  Otherwise one sfk_ema_update launch follows the step's last optimizer launch on the trunk: the
+        average of the arena and of the BatchNorm running statistics, with its own step counter on the device.  With world >
+        1 every rank averages its own identical copy; nothing is communicated.  The average is not checkpointed separately:
+        self.ema.applied() evaluates and saves it.  Eager steps only: with use_graph the keyword is refused (DESIGN.md
+        section 20 -- the captured step with the launch in it ended its capture in a host segmentation fault on the GPU, the
+        cause is not known, and the captured route was taken out)."""
         self.eng = engine
+        ema_decay = float(ema_decay)
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay}")
         self.label_smoothing = float(label_smoothing)
         if not 0.0 <= self.label_smoothing < 1.0:
             raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
@@ -81,6 +93,13 @@ class TrainStep:
             # keeps the four compute lanes for an A/B on a multi-GPU node
             engine.wgrad_one_lane = engine.options.dist_wgrad_one_lane or engine.wgrad_one_lane
         self.use_graph = use_graph and not self.segmented and engine.device.type == "cuda"
+        self.ema = None
+        if ema_decay > 0:
+            if self.use_graph:
+                raise ValueError("ema_decay > 0 needs an eager step: the captured step (use_graph=True) with the sfk_ema_update "
+                                 "launch in it is not offered (DESIGN.md section 20)")
+            from .ema import WeightEma
+            self.ema = WeightEma(engine, ema_decay, ema_warmup)
         self.overlap_segments = overlap_segments
         dev = engine.device
         self.loss = torch.zeros(1, device=dev)            # mean loss of the last step
@@ -123,6 +142,8 @@ class TrainStep:
         if (opt.can_split and pl.tail_cut is not None and not self.segmented and not self.use_graph and eng.two_streams
                 and eng.device.type == "cuda" and eng.options.split_adam):
             ops["adam_main"], ops["adam_tail"], self._set_tail = opt.split_ops(pl.tail_cut[1], gscale)
+        if self.ema is not None:
+            ops["ema"] = self.ema.update_ops()            # after the step's last optimizer launch, on the trunk
         return ops
 
     def _eager(self, pl, ops):
@@ -147,6 +168,8 @@ class TrainStep:
             self._set_tail()                  # tail counter = step - 1, in the trunk's idle time (the tail launch increments it)
             eng._run_lanes(pl.bwd, i_wg)
             ops["adam_tail"](st)
+            if "ema" in ops:
+                ops["ema"](st)
             return
         if not self.segmented:
             eng._run_lanes(pl.bwd)
@@ -161,6 +184,8 @@ class TrainStep:
         if "grad_norm" in ops:
             ops["grad_norm"](st)
         ops["adam"](st)
+        if "ema" in ops:
+            ops["ema"](st)
 
     def __call__(self, x_slow, x_fast, labels, slow_t_index=None, mix=None) -> torch.Tensor:
         """mix: None, or the (N, 8) float32 device table of the batch's mix rows (input_pipeline.ClipMix.load): the loss takes
@@ -217,6 +242,17 @@ def mix_settings(cfg):
         draw = dict(mixup_alpha=mixup, cutmix_alpha=cutmix, prob=float(m.get("MIX_PROB", 1.0)),
                     switch_prob=float(m.get("MIX_SWITCH_PROB", 0.5)))
     return eps, draw, int(m.get("MIX_SEED", 0))
+
+
+def ema_settings(cfg):
+    """MODEL.EMA_DECAY, EMA_WARMUP, EMA_EVAL: (decay, warmup, 'ema' | 'live' | 'both')"""
+    m = cfg.MODEL
+    decay, which = float(m.get("EMA_DECAY", 0.0)), str(m.get("EMA_EVAL", "ema"))
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"MODEL.EMA_DECAY must be in [0, 1), got {decay}")
+    if which not in ("ema", "live", "both"):
+        raise ValueError(f"MODEL.EMA_EVAL must be 'ema', 'live' or 'both', got {which!r}")
+    return decay, bool(m.get("EMA_WARMUP", False)), which
 
 
 def jitter_ranges(cfg):
@@ -862,6 +898,7 @@ class Trainer:
         self.load_ckpt()
         eng = getattr(self.model, "engine", None)
         self.label_smoothing, self.mix_draw, self.mix_seed = mix_settings(cfg)
+        self.ema_decay, self.ema_warmup, self.ema_eval = ema_settings(cfg)
         # Adam is created AFTER the checkpoint load, its state is never saved (train.py:180-182)
         if eng is None:                                  # res2d: a plain torch module, the reference's own five lines
             from .res2d import TorchStep
@@ -872,10 +909,17 @@ class Trainer:
             if self.label_smoothing > 0 or self.mix_draw is not None:
                 raise ValueError("MODEL.LABEL_SMOOTHING / MIXUP_ALPHA / CUTMIX_ALPHA need the engine's loss launch: MODEL.NAME res2d "
                                  "with the torch backend is host plumbing (nn.CrossEntropyLoss); use RES2D_BACKEND = 'engine'")
+            if self.ema_decay > 0:
+                raise ValueError("MODEL.EMA_DECAY needs the engine's parameter arena and its sfk_ema_update launch: MODEL.NAME res2d "
+                                 "with the torch backend is host plumbing (torch.optim.Adam); use RES2D_BACKEND = 'engine'")
             self.step = TorchStep(self.model, lr=cfg.MODEL.LR)
         else:
             reducer = sdist.GradReducer(eng.G, bucket_mb=cfg.DIST.BUCKET_MB) if self.world > 1 else None
             self.step = self._make_step(eng, use_graph, reducer)
+            if self.step.ema is not None:
+                # the average starts from the weights load_ckpt left.  A fresh engine's average is that copy already
+                # (Engine.optim_state); this matters for an engine whose average existed before this trainer
+                self.step.ema.reset()
             if self.mix_draw is not None:                # the one device table every step's rows are written into
                 self.mm.clip_mix(int(self.batch_size))
 
@@ -903,6 +947,10 @@ class Trainer:
         """MODEL.LABEL_SMOOTHING as a TrainStep keyword ({} at the default)"""
         return {"label_smoothing": self.label_smoothing} if self.label_smoothing > 0 else {}
 
+    def _ema_kwargs(self) -> dict:
+        """MODEL.EMA_DECAY / EMA_WARMUP as TrainStep keywords ({} at the default)"""
+        return {"ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup} if self.ema_decay > 0 else {}
+
     def mix_frame(self) -> int:
         """the side of the square frames the mix boxes are drawn on"""
         return int(crop_resize_dict[self.cfg.MODEL.R3D_INPUT])
@@ -922,7 +970,7 @@ class Trainer:
 
     def _make_step(self, eng, use_graph, reducer):
         return TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer, **self._optim_kwargs(),
-                         **self._mix_kwargs())
+                         **self._mix_kwargs(), **self._ema_kwargs())
 
     def _reference_datasets(self):
         try:
@@ -1061,21 +1109,40 @@ class Trainer:
             print(f'lr: {self.step.last_lr():.6g}' + ('' if gn is None else f', grad_norm: {float(gn[0]):.4g}'))
         return loss_avg, correct / max(seen, 1)
 
+    def _evaluates_average(self) -> bool:
+        """MODEL.EMA_DECAY > 0 on the engine and EMA_EVAL 'ema' or 'both': train() evaluates and saves the averaged model"""
+        return getattr(self.step, "ema", None) is not None and self.ema_eval != "live"
+
+    def _averaged(self):
+        """the context train() evaluates and saves in: when _evaluates_average() the engine holds the averaged weights and
+        running statistics inside it (ema.WeightEma.applied) and the live ones again after it; otherwise nothing happens"""
+        return self.step.ema.applied() if self._evaluates_average() else contextlib.nullcontext()
+
     def train(self):
+        """With MODEL.EMA_DECAY > 0 (and EMA_EVAL not 'live') the epoch's evaluation and every checkpoint are the AVERAGED
+        model's, in the ordinary flat state_dict format; 'both' evaluates the live model first and prints both accuracies.
+        The average and its counter are not checkpointed separately, as the optimizer state is not."""
         max_epoch = self.cfg.MODEL.MAX_EPOCH if not self.debug else 3
         acc, epoch = 0.0, 0
+        averaged = self._evaluates_average()
         for epoch in range(max_epoch):
             print(f'========== Training epoch {epoch}')
             self.num_step = 0
             self.epoch = epoch
             self.train_epoch()
-            acc = self.run_eval()['acc']
-            if acc > self.max_historical_acc:
-                self.max_historical_acc = acc
-                self.save_ckpt(epoch, acc)
-            else:
-                print("Not saved. Current best acc: %.3f" % (self.max_historical_acc))
-        self.save_ckpt(epoch, acc)
+            if averaged and self.ema_eval == "both":
+                print('Live Accuracy: %.3f' % self.run_eval()['acc'])
+            with self._averaged():
+                acc = self.run_eval()['acc']
+                if averaged:
+                    print('EMA Accuracy: %.3f' % acc)
+                if acc > self.max_historical_acc:
+                    self.max_historical_acc = acc
+                    self.save_ckpt(epoch, acc)
+                else:
+                    print("Not saved. Current best acc: %.3f" % (self.max_historical_acc))
+        with self._averaged():
+            self.save_ckpt(epoch, acc)
 
     def run_eval(self, dataset_loader=None):
         """Batched no-grad forward over uniform windows; softmax; per-video mean over its clips; argmax
