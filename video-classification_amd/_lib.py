@@ -294,6 +294,15 @@ class _PoolCropDesc(C.Structure):
                 ("lut", C.c_void_p), ("crop", C.c_void_p), ("fill", C.c_int32), ("pad", C.c_int32), ("out", C.c_void_p)]
 
 
+class _PoolWarpDesc(C.Structure):
+    """include/sfk_warp.h sfk_pool_warp_desc: sfk_pool_crop_desc with the per-clip matrix table (n, 6) float32 in place of crop
+    and pad; index may be NULL (frame n*t + tt)"""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_int32), ("pool", C.c_void_p), ("frame_stride", C.c_int64),
+                ("row_stride", C.c_int64), ("pixel_pitch", C.c_int32), ("frames", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("c0", C.c_int32), ("c", C.c_int32), ("n", C.c_int32), ("t", C.c_int32), ("index", C.c_void_p),
+                ("lut", C.c_void_p), ("warp", C.c_void_p), ("fill", C.c_int32), ("out", C.c_void_p)]
+
+
 class _RoiPoolDesc(C.Structure):
     """include/sfk_roi_pool.h sfk_roi_pool_desc: sfk_roi_desc with its source addressing replaced by a frame pool -- byte
     (f, y, x, ch) at pool[f*frame_stride + y*row_stride + x*pixel_pitch + c0 + ch], clip n, time t reads frame index[n][t]"""
@@ -529,6 +538,17 @@ SIGNATURES_EMA = {
     "sfk_ema_update": [C.POINTER(_EmaDesc), _PV],
     "sfk_ema_swap": [C.POINTER(_EmaDesc), _PV],
 }
+# include/sfk_warp.h: the per-clip affine sampling of the frame pool (rotate, scale, shear, flip), same library, its own header
+# and version
+WARP_ABI_VERSION = 1       # include/sfk_warp.h SFK_WARP_ABI_VERSION
+WARP_TILE_H, WARP_TILE_W = 16, 32      # include/sfk_warp.h SFK_WARP_TILE_H / _W: the output tile of one workgroup
+WARP_LDS_BYTES = 32 * 1024             # include/sfk_warp.h SFK_WARP_LDS_BYTES
+WARP_ROW_FLOATS = 6        # (a, b, c, d, e, f): output pixel (x, y) reads source (a x + b y + c, d x + e y + f)
+SIGNATURES_WARP = {
+    "sfk_warp_abi_version": [],
+    "sfk_u8_pool_gather_warp": [C.POINTER(_PoolWarpDesc), _PV],
+    "sfk_warp_fallback_tiles": [_I32, _I32, _I32, _I32, _PF],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_groups_prepare": C.c_int64, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
@@ -612,6 +632,12 @@ def new_pool_crop_desc() -> "_PoolCropDesc":
     return d
 
 
+def new_pool_warp_desc() -> "_PoolWarpDesc":
+    d = _PoolWarpDesc()
+    d.struct_size = C.sizeof(_PoolWarpDesc)
+    return d
+
+
 def new_roi_pool_desc() -> "_RoiPoolDesc":
     d = _RoiPoolDesc()
     d.struct_size = C.sizeof(_RoiPoolDesc)
@@ -668,7 +694,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib = C.CDLL(path)
     for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL,
                   SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL, SIGNATURES_ROI_RAGGED, SIGNATURES_U8STEM_POOL,
-                  SIGNATURES_OPTIM, SIGNATURES_GROUPS, SIGNATURES_MIX, SIGNATURES_EMA):
+                  SIGNATURES_OPTIM, SIGNATURES_GROUPS, SIGNATURES_MIX, SIGNATURES_EMA, SIGNATURES_WARP):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -703,6 +729,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk mix ABI version mismatch: library {lib.sfk_mix_abi_version()}, binding {MIX_ABI_VERSION}")
     if lib.sfk_ema_abi_version() != EMA_ABI_VERSION:
         raise SfkError(f"libsfk ema ABI version mismatch: library {lib.sfk_ema_abi_version()}, binding {EMA_ABI_VERSION}")
+    if lib.sfk_warp_abi_version() != WARP_ABI_VERSION:
+        raise SfkError(f"libsfk warp ABI version mismatch: library {lib.sfk_warp_abi_version()}, binding {WARP_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -1430,6 +1458,40 @@ class HipBackend:
             assert crop.device == index.device
         d.crop, d.pad = (None if crop is None else crop.data_ptr()), int(pad)
         return self._plain("sfk_u8_pool_gather_crop", C.byref(d), keep=(d, pool, index, lut, crop, out))
+
+    def u8_pool_gather_warp(self, pool, index, lut, fill: int, warp, out, c0: int = 0, c: Optional[int] = None):
+        """sfk_u8_pool_gather_warp (include/sfk_warp.h): ``u8_pool_gather_crop`` sampling through a matrix per clip -- warp
+        (N,6) float32 (a, b, c, d, e, f) on the device, read when the launch runs: out[n,t,ch,y,x] is the bilinear sample of the
+        normalised frame at (a x + b y + c, d x + e y + f), zeros outside the frame (lut[fill] for a missing frame).  index
+        (N,T) int32, or None: pool is then the stacked batch (N,T,H,W,P) itself and clip n, time t reads frame n*T + t."""
+        if index is None:
+            assert pool.dim() == 5 and pool.is_contiguous(), "index=None: pool is the stacked (N,T,H,W,P) batch"
+            n, t = int(pool.shape[0]), int(pool.shape[1])
+            pool = pool.view((n * t,) + tuple(pool.shape[2:]))
+            f, h, w, p = pool.shape
+            c = p - c0 if c is None else c
+            assert pool.dtype == torch.uint8 and 0 <= c0 and 0 < c and c0 + c <= p
+            assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
+            assert out.is_contiguous() and tuple(out.shape) == (n, t, c, h, w), (tuple(out.shape), (n, t, c, h, w))
+            d = new_pool_warp_desc()
+            d.out_dtype, d.pool, d.index, d.lut, d.out = _DT[out.dtype], pool.data_ptr(), None, lut.data_ptr(), out.data_ptr()
+            d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
+            d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
+        else:
+            d = self._fill_pool_desc(new_pool_warp_desc(), pool, index, lut, fill, out, c0, c)
+        assert warp.dtype == torch.float32 and tuple(warp.shape) == (d.n, WARP_ROW_FLOATS) and warp.is_contiguous()
+        assert warp.device == out.device
+        d.warp = warp.data_ptr()
+        return self._plain("sfk_u8_pool_gather_warp", C.byref(d), keep=(d, pool, index, lut, warp, out))
+
+    def warp_fallback_tiles(self, h: int, w: int, pixel_pitch: int, c: int, row) -> int:
+        """sfk_warp_fallback_tiles (include/sfk_warp.h), host only: how many output tiles of an h x w frame take their taps
+        from global memory under the matrix row (6 floats) -- the staged box would not fit the launch's LDS"""
+        m = (C.c_float * WARP_ROW_FLOATS)(*[float(v) for v in row])
+        r = int(self.lib.sfk_warp_fallback_tiles(int(h), int(w), int(pixel_pitch), int(c), m))
+        if r < 0:
+            _check(r, "sfk_warp_fallback_tiles")
+        return r
 
     def roi_resize_pool(self, pool, index, lut, fill: int, box, out, antialias: bool, crop=None, pad: int = 0, c0: int = 0,
                         c: Optional[int] = None, c_off: int = 0):

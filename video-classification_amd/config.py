@@ -107,7 +107,12 @@ _C.MODEL.JITTER_BRIGHTNESS = 0.5   # dataset/chalearn_dataset.py:49: ColorJitter
 _C.MODEL.JITTER_CONTRAST = 0.3
 _C.MODEL.JITTER_SATURATION = 0.2
 _C.MODEL.JITTER_HUE = 0.1
-_C.MODEL.LABEL_SMOOTHING = 0.0     # the loss's smoothing mass eps: target (1 - eps) t + eps / K (include/sfk_mix.h); 0: sfk_softmax_ce as ever
+_C.MODEL.AFFINE = False            # train clips are sampled through a random affine matrix per clip ON the device (include/sfk_warp.h) instead of RandomCrop's integer shift; the translation is still RandomCrop's draw
+_C.MODEL.AFFINE_DEGREES = 10.0     # rotation, uniform in [-deg, deg] (input_pipeline.draw_affine)
+_C.MODEL.AFFINE_SCALE = (0.85, 1.15)   # isotropic scale, uniform in [lo, hi]
+_C.MODEL.AFFINE_SHEAR = 0.0        # x shear, degrees, uniform in [-shear, shear]
+_C.MODEL.AFFINE_FLIP = 0.0         # probability of a horizontal flip; 0 because left and right hands differ
+_C.MODEL.LABEL_SMOOTHING = 0.0    # the loss's smoothing mass eps: target (1 - eps) t + eps / K (include/sfk_mix.h); 0: sfk_softmax_ce as ever
 _C.MODEL.MIXUP_ALPHA = 0.0         # > 0: Mixup with lam ~ Beta(alpha, alpha) on the device float clip, pairs i <-> N-1-i (input_pipeline.draw_mix)
 _C.MODEL.CUTMIX_ALPHA = 0.0        # > 0: CutMix, the partner's box pasted; both > 0: CutMix with probability MIX_SWITCH_PROB
 _C.MODEL.MIX_PROB = 1.0            # the probability that a pair is mixed at all

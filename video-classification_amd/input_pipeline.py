@@ -54,6 +54,96 @@ def draw_crop_offsets(n: int, padding: int, generator: Optional[torch.Generator]
     return out
 
 
+def identity_warp_rows(n: int) -> torch.Tensor:
+    """(n, 6) float32 identity rows of the warp table (include/sfk_warp.h): (1, 0, 0, 0, 1, 0)"""
+    return torch.tensor([1.0, 0.0, 0.0, 0.0, 1.0, 0.0], dtype=torch.float32).repeat(int(n), 1)
+
+
+def validate_warp_rows(rows: torch.Tensor) -> torch.Tensor:
+    """the host rows of a warp table as contiguous (n, 6) float32, or ValueError: a wrong shape, or an entry that is not a
+    finite number (the kernel is memory-safe for any row and writes zeros for such a one; the host refuses it all the same,
+    as ``ClipMix.validate`` refuses its rows, because a clip of zeros is never what a loader meant)"""
+    rows = torch.as_tensor(rows).detach().to("cpu", torch.float32).contiguous()
+    if rows.dim() != 2 or rows.shape[1] != 6:
+        raise ValueError(f"warp rows must be (n, 6), got {tuple(rows.shape)}")
+    if not bool(torch.isfinite(rows).all()):
+        raise ValueError("warp rows: an entry is not finite")
+    return rows
+
+
+def _affine_linear(angle: float, scale: float, shear: float) -> torch.Tensor:
+    """float64 (2, 2) L = R(angle) . Sh(shear) . scale: rotation [[cos, -sin], [sin, cos]], x shear [[1, tan], [0, 1]], degrees"""
+    a, s = math.radians(float(angle)), math.radians(float(shear))
+    rot = torch.tensor([[math.cos(a), -math.sin(a)], [math.sin(a), math.cos(a)]], dtype=torch.float64)
+    sh = torch.tensor([[1.0, math.tan(s)], [0.0, 1.0]], dtype=torch.float64)
+    return rot @ sh * float(scale)
+
+
+def affine_forward(size: int, padding: int, top: int, left: int, angle: float = 0.0, scale: float = 1.0, shear: float = 0.0,
+                   flipped: bool = False) -> torch.Tensor:
+    """float64 (2, 3) source -> output map of one clip: p_out = F . L . (p_src - ctr) + ctr - (left - padding, top - padding),
+    L = R . Sh . scale about the centre ctr = ((S-1)/2, (S-1)/2), F = diag(-1, 1) when flipped, then RandomCrop's shift"""
+    ctr = torch.full((2,), (int(size) - 1) / 2.0, dtype=torch.float64)
+    lin = _affine_linear(angle, scale, shear)
+    if flipped:
+        lin = torch.tensor([[-1.0, 0.0], [0.0, 1.0]], dtype=torch.float64) @ lin
+    d = torch.tensor([float(int(left) - int(padding)), float(int(top) - int(padding))], dtype=torch.float64)
+    return torch.cat([lin, (ctr - d - lin @ ctr)[:, None]], 1)
+
+
+def affine_inverse(size: int, padding: int, top: int, left: int, angle: float = 0.0, scale: float = 1.0, shear: float = 0.0,
+                   flipped: bool = False) -> torch.Tensor:
+    """float64 (2, 3) output -> source map, ``affine_forward``'s inverse written out (no matrix is inverted numerically):
+    A = (1 / scale) . Sh(-shear) . R(-angle) . F and p_src = A . (p_out + (left - padding, top - padding) - ctr) + ctr.  With
+    angle 0, scale 1, shear 0 and no flip A is exactly the identity and the row exactly (1, 0, left - padding, 0, 1, top -
+    padding)."""
+    ctr = torch.full((2,), (int(size) - 1) / 2.0, dtype=torch.float64)
+    a, s = math.radians(float(angle)), math.radians(float(shear))
+    rot_t = torch.tensor([[math.cos(a), math.sin(a)], [-math.sin(a), math.cos(a)]], dtype=torch.float64)
+    sh_i = torch.tensor([[1.0, -math.tan(s)], [0.0, 1.0]], dtype=torch.float64)
+    inv = sh_i @ rot_t * (1.0 / float(scale))
+    if flipped:
+        inv = inv @ torch.tensor([[-1.0, 0.0], [0.0, 1.0]], dtype=torch.float64)
+    d = torch.tensor([float(int(left) - int(padding)), float(int(top) - int(padding))], dtype=torch.float64)
+    return torch.cat([inv, (inv @ (d - ctr) + ctr)[:, None]], 1)
+
+
+def draw_affine_params(padding: int, degrees: float = 0.0, scale=(1.0, 1.0), shear: float = 0.0, flip: float = 0.0,
+                       generator: Optional[torch.Generator] = None) -> tuple:
+    """one clip's draws, (top, left, angle, scale, shear, flipped), in the fixed order of ``draw_affine``"""
+    top = int(torch.randint(0, 2 * padding + 1, (1,), generator=generator))
+    left = int(torch.randint(0, 2 * padding + 1, (1,), generator=generator))
+    u = [float(torch.rand(1, dtype=torch.float64, generator=generator)) for _ in range(4)]
+    lo, hi = float(scale[0]), float(scale[1])
+    return (top, left, -float(degrees) + 2.0 * float(degrees) * u[0], lo + (hi - lo) * u[1],
+            -float(shear) + 2.0 * float(shear) * u[2], u[3] < float(flip))
+
+
+def draw_affine(n: int, size: int, padding: int, degrees: float = 0.0, scale=(1.0, 1.0), shear: float = 0.0, flip: float = 0.0,
+                generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """(n, 6) float32 rows (a, b, c, d, e, f) for ``sfk_u8_pool_gather_warp`` (include/sfk_warp.h) on S x S frames: the INVERSE
+    (output -> source) matrix of a random affine transform about the centre ((S-1)/2, (S-1)/2), formed in float64
+    (``affine_inverse``) and rounded once to fp32.  Output pixel (x, y) reads the source at (a x + b y + c, d x + e y + f).
+    Composition, source -> output: rotation . shear . scale about the centre (the angle uniform in [-degrees, degrees], the
+    isotropic scale uniform in [scale[0], scale[1]], the x shear uniform in [-shear, shear] degrees), an optional horizontal
+    flip about the centre (probability ``flip``), then RandomCrop's translation by (padding - left, padding - top).
+    Draw order per clip, FIXED and independent of the configuration, so the stream position never depends on which ranges
+    are degenerate: (top, left) by the very ``torch.randint(0, 2 * padding + 1, (1,))`` calls ``draw_crop_offsets`` makes,
+    then one float64 ``torch.rand(1)`` each for the angle, the scale, the shear and the flip (flipped when u < flip, so 0
+    never flips and 1 always does).  With degrees 0, scale (1, 1), shear 0 and flip 0 the row is exactly (1, 0, left - padding,
+    0, 1, top - padding): RandomCrop's.
+    All 21 channels of a clip are warped as IMAGES -- BGR, U, V, the five flow images and depth alike: the flow is stored as
+    colour images and nothing re-orients its vectors under a rotation or a flip.  ``flip`` defaults to 0 because left and right
+    hands differ.  Stated in plain torch: torchvision is not installed here, parity with its RandomAffine is unpinned."""
+    lo, hi = float(scale[0]), float(scale[1])
+    assert n > 0 and size > 0 and padding >= 0 and degrees >= 0 and 0 < lo <= hi and 0 <= shear < 90 and 0 <= flip <= 1
+    out = torch.empty(n, 6, dtype=torch.float32)
+    for i in range(n):
+        p = draw_affine_params(padding, degrees, (lo, hi), shear, flip, generator)
+        out[i] = affine_inverse(size, padding, *p).reshape(6).to(torch.float32)
+    return out
+
+
 def draw_color_jitter(n: int, brightness: float = 0.5, contrast: float = 0.3, saturation: float = 0.2, hue: float = 0.1,
                       generator: Optional[torch.Generator] = None) -> torch.Tensor:
     """(n, 8) float32 rows (order[4], b, c, s, h) for ``sfk_color_jitter``: per clip the draws of torchvision's
@@ -230,16 +320,28 @@ class ClipMix:
 
 
 class DevicePreprocess:
-    """uint8 frames (N, T, S, S, C) -> normalised clip batch (N, T, C, S, S) on the device."""
+    """uint8 frames (N, T, S, S, C) -> normalised clip batch (N, T, C, S, S) on the device.  crop (N, 2): RandomCrop's shift,
+    by ``sfk_u8_normalize_crop``; warp (N, 6) float32 (``draw_affine``) instead: every clip sampled through its matrix, by ONE
+    ``sfk_u8_pool_gather_warp`` launch (include/sfk_warp.h) over the stacked frames, which are a pool that needs no index
+    table; the rows are validated on the host first (``validate_warp_rows``).  crop and warp together is a ValueError."""
 
     def __init__(self, device="cuda", backend=None, out_dtype: torch.dtype = torch.float32):
         self.be, self.device, self.out_dtype = hip_backend(backend), torch.device(device), out_dtype
         self.lut = normalize_lut().to(self.device)
 
-    def __call__(self, frames_u8: torch.Tensor, crop: Optional[torch.Tensor] = None, padding: Optional[int] = None):
+    def __call__(self, frames_u8: torch.Tensor, crop: Optional[torch.Tensor] = None, padding: Optional[int] = None,
+                 warp: Optional[torch.Tensor] = None):
         assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 5
+        if crop is not None and warp is not None:
+            raise ValueError("DevicePreprocess: crop and warp together (a warp row carries RandomCrop's translation itself)")
         n, t, h, w, c = frames_u8.shape
         x = h2d(frames_u8, self.device).contiguous()
+        if warp is not None:
+            rows = validate_warp_rows(warp)
+            assert tuple(rows.shape) == (n, 6), tuple(rows.shape)
+            out = torch.empty(n, t, c, h, w, dtype=self.out_dtype, device=self.device)
+            self.be.u8_pool_gather_warp(x, None, self.lut, MISSING_BYTE, h2d(rows, self.device), out)(stream_of(self.device))
+            return out
         if crop is not None:
             padding = h // 10 if padding is None else padding
             crop = h2d(crop.to(torch.int32), self.device).contiguous()
@@ -330,7 +432,7 @@ class FramePool:
         self.bytes_uploaded = 0
         self._resize = {}                       # (size, channels) -> the PadResize of add_raw
         self._byte_lut = None                   # roi_gather's table, made at its first call
-        self._tables = {}                       # clip's persistent device tables: 'index' / 'crop' -> flat int32 buffer
+        self._tables = {}                       # persistent device tables: clip's 'index' / 'crop' (int32), gather's 'warp' (float32) -> flat buffer
         self.capacity = None if capacity is None else int(capacity)
         if self.capacity is not None and self.capacity <= 0:
             raise ValueError(f"FramePool: capacity {capacity} frames")
@@ -448,12 +550,12 @@ class FramePool:
         return idx
 
     def _table(self, name: str, host: torch.Tensor) -> torch.Tensor:
-        """host int32 table -> its view of the pool's persistent device buffer `name`, written on the current stream.  The
+        """host table (int32; float32 for 'warp') -> its view of the pool's persistent device buffer `name`, written on the current stream.  The
         buffer is sized at first use and grows to the largest table seen, so equal-shaped batches get the SAME address (a
         smaller one the same base); the copy is ordered behind every launch already enqueued that reads the old contents."""
         buf = self._tables.get(name)
         if buf is None or buf.numel() < host.numel():
-            buf = self._tables[name] = torch.empty(host.numel(), dtype=torch.int32, device=self.device)
+            buf = self._tables[name] = torch.empty(host.numel(), dtype=host.dtype, device=self.device)
         view = buf[:host.numel()].view(host.shape)
         src = host
         if src.device.type == "cpu" and self.device.type == "cuda" and not src.is_pinned():
@@ -478,15 +580,26 @@ class FramePool:
         return [PoolClip(self.arena, index, int(c0), int(c), crop, padding, self.lut, self.fill) for c0, c in channels]
 
     def gather(self, index_rows: torch.Tensor, out_dtype: torch.dtype = torch.float32, c0: int = 0,
-               c: Optional[int] = None, crop: Optional[torch.Tensor] = None, padding: Optional[int] = None) -> torch.Tensor:
+               c: Optional[int] = None, crop: Optional[torch.Tensor] = None, padding: Optional[int] = None,
+               warp: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(N, T) arena slots (or -1) -> the (N, T, c, S, S) clips DevicePreprocess would write from the materialised frames;
         crop (N, 2) int32 (top, left): with that RandomCrop (padding defaults to S // 10, as DevicePreprocess's), by ONE
-        ``sfk_u8_pool_gather_crop`` launch instead of the ``sfk_u8_pool_gather`` one"""
+        ``sfk_u8_pool_gather_crop`` launch instead of the ``sfk_u8_pool_gather`` one; warp (N, 6) float32 (``draw_affine``)
+        instead of crop: every clip sampled through its matrix, by ONE ``sfk_u8_pool_gather_warp`` launch (include/sfk_warp.h),
+        the validated rows written into the pool's persistent 'warp' table"""
         idx = self._checked_rows(index_rows)
         _, h, w, p = self.arena.shape
         c = p - c0 if c is None else c
+        if crop is not None and warp is not None:
+            raise ValueError("gather: crop and warp together (a warp row carries RandomCrop's translation itself)")
         out = torch.empty(idx.shape[0], idx.shape[1], c, h, w, dtype=out_dtype, device=self.device)
         stream = stream_of(self.device)
+        if warp is not None:
+            rows = validate_warp_rows(warp)
+            assert tuple(rows.shape) == (idx.shape[0], 6), tuple(rows.shape)
+            self.be.u8_pool_gather_warp(self.arena, h2d(idx, self.device), self.lut, self.fill, self._table("warp", rows), out,
+                                        c0, c)(stream)
+            return out
         if crop is not None:
             crop = torch.as_tensor(crop).to(torch.int32).contiguous()
             assert tuple(crop.shape) == (idx.shape[0], 2), tuple(crop.shape)
@@ -1199,7 +1312,9 @@ class ResidentTrainSet(_ResidentSet):
     Arena: capacity_frames slots (default floor(MODEL.RESIDENT_GB * 2^30 / (S*S*21))); the last batch_size * CLIP_LEN of
     them are the spill region, the rest the resident region.
     Plan: ``plan(e)`` batches are (videos, indices (N, T), crop (N, 2), jitter (N, 8) | None); per clip the start, then the
-    crop (``draw_crop_offsets``), then the jitter row.
+    crop (``draw_crop_offsets``), then the jitter row.  affine = (degrees, (lo, hi), shear, flip) (MODEL.AFFINE): the third
+    column is the (N, 6) float32 warp row of ``draw_affine`` instead, told from the int32 crop rows by its dtype, and a batch
+    is one ``sfk_u8_pool_gather_warp`` launch (include/sfk_warp.h); with stem_channels it is a ValueError (no float clip).
     ``epoch(e)`` yields {'<key>': (N, T, 21, S, S) float32 on the device, 'label': (N,), optionally 'jitter': (N, 8)}: what
     every model's prepare_data takes under the float key (like pooled eval, whatever MODEL.U8_STEM says).
     stem_channels (MODEL.POOL_STEM): the (c0, c) channel range of every pathway's stem.  '<key>' is then the list of
@@ -1207,10 +1322,16 @@ class ResidentTrainSet(_ResidentSet):
     spilled clip's slots are released when the consumer comes back for the next batch, after it has enqueued that step."""
 
     def __init__(self, train_set, cfg, device="cuda", backend=None, batch_size: int = 1, drop_last: bool = True, seed: int = 0,
-                 capacity_frames: Optional[int] = None, num_workers: int = 0, jitter=None, stem_channels=None):
+                 capacity_frames: Optional[int] = None, num_workers: int = 0, jitter=None, stem_channels=None, affine=None):
         super().__init__(train_set, cfg, device, backend, batch_size, drop_last, seed, num_workers, jitter)
         from .config import crop_resize_dict
         self.key = cfg.MODEL.R3D_INPUT
+        # MODEL.AFFINE: (degrees, (scale lo, hi), shear, flip) -- the plan's third column is then the warp row, not the crop row
+        self.affine = None if affine is None else (float(affine[0]), tuple(float(v) for v in affine[1]), float(affine[2]),
+                                                   float(affine[3]))
+        if self.affine is not None and stem_channels is not None:
+            raise ValueError("ResidentTrainSet: MODEL.POOL_STEM reads the uint8 frames in the stems, so there is no float clip "
+                             "for MODEL.AFFINE to sample; turn POOL_STEM or AFFINE off")
         # MODEL.POOL_STEM: the (c0, c) range each pathway's stem reads; the batch is then those PoolClips, not the float clip
         self.stem_channels = None if stem_channels is None else [(int(c0), int(c)) for c0, c in stem_channels]
         self.lazy_batch = self.stem_channels is not None
@@ -1220,6 +1341,8 @@ class ResidentTrainSet(_ResidentSet):
         self._make_pool(capacity_frames)
 
     def _clip_rows(self, g, video, indices) -> tuple:
+        if self.affine is not None:             # the same stream position for (top, left) as the crop row's
+            return (draw_affine(1, self.size, self.size // 10, *self.affine, generator=g)[0],)
         return (draw_crop_offsets(1, self.size // 10, g)[0],)
 
     def _upload(self, item, windows) -> int:
@@ -1230,6 +1353,8 @@ class ResidentTrainSet(_ResidentSet):
     def _batch(self, table, entry) -> dict:
         if self.stem_channels is not None:
             return {self.key: self.pool.clip(table, self.stem_channels, crop=entry[2])}
+        if entry[2].dtype == torch.float32:     # (N, 6) warp rows (MODEL.AFFINE); the crop rows are (N, 2) int32
+            return {self.key: self.pool.gather(table, torch.float32, 0, None, warp=entry[2])}
         return {self.key: self.pool.gather(table, torch.float32, 0, None, crop=entry[2])}
 
 

@@ -264,6 +264,27 @@ def jitter_ranges(cfg):
             float(m.get("JITTER_SATURATION", 0.2)), float(m.get("JITTER_HUE", 0.1)))
 
 
+def affine_ranges(cfg):
+    """MODEL.AFFINE on: (degrees, (scale lo, scale hi), shear, flip) of MODEL.AFFINE_*, ``input_pipeline.draw_affine``'s
+    arguments; off: None"""
+    m = cfg.MODEL
+    if not bool(m.get("AFFINE", False)):
+        return None
+    lo, hi = m.get("AFFINE_SCALE", (0.85, 1.15))
+    return (float(m.get("AFFINE_DEGREES", 10.0)), (float(lo), float(hi)), float(m.get("AFFINE_SHEAR", 0.0)),
+            float(m.get("AFFINE_FLIP", 0.0)))
+
+
+def draw_crop_or_warp(cfg, size: int, generator=None) -> tuple:
+    """('crop', (2,) int32) of RandomCrop(size, padding = size // 10), or, under MODEL.AFFINE, ('warp', (6,) float32) of
+    ``draw_affine`` -- whose first two draws are the crop's, so everything drawn after it keeps its stream position"""
+    from .input_pipeline import draw_affine, draw_crop_offsets
+    ranges = affine_ranges(cfg)
+    if ranges is None:
+        return "crop", draw_crop_offsets(1, size // 10, generator)[0]
+    return "warp", draw_affine(1, size, size // 10, *ranges, generator=generator)[0]
+
+
 class ModelManager:
     """Name -> (init_model, prepare_data), as reference train.py:39-60.  'slowfast*' and 'res3d' (SURVEY.md section
     8f-4: hub slow_r50 with a 5-channel stem, train.py:79-89 / (deprecated)/train_3dresnet.py:47-51) run on this
@@ -357,19 +378,25 @@ class ModelManager:
             raise ValueError(self._NO_FLOAT_CLIP.format("POOL_STEM"))
         if "mix" in batch:
             raise ValueError(self._NO_FLOAT_CLIP_MIX.format("POOL_STEM"))
+        if "warp" in batch:
+            raise ValueError(self._NO_FLOAT_CLIP_WARP.format("POOL_STEM"))
         return list(x)
 
     _NO_FLOAT_CLIP = ("MODEL.{0}: true reads the uint8 frames in the stems, so there is no float clip for the "
                       "batch's 'jitter' entry to work on; turn {0} or MODEL.COLOR_JITTER off")
+    _NO_FLOAT_CLIP_WARP = ("MODEL.{0}: true reads the uint8 frames in the stems, so there is no float clip for the "
+                           "batch's 'warp' entry to be sampled into; turn {0} or MODEL.AFFINE off")
     _NO_FLOAT_CLIP_MIX = ("MODEL.{0}: true reads the uint8 frames in the stems, so there is no float clip for the "
                           "batch's 'mix' entry to work on; turn {0} or MODEL.MIXUP_ALPHA / MODEL.CUTMIX_ALPHA off")
 
     def _u8_float(self, batch) -> torch.Tensor:
-        """DevicePreprocess: (N,T,S,S,P) uint8 -> (N,T,P,S,S) float32 on the device (then the batch's 'jitter' and 'mix', if any)"""
+        """DevicePreprocess: (N,T,S,S,P) uint8 -> (N,T,P,S,S) float32 on the device, RandomCrop-ped by the batch's 'crop' or
+        sampled through its 'warp' rows (MODEL.AFFINE) (then the batch's 'jitter' and 'mix', if any)"""
         if self._pre is None:
             from .input_pipeline import DevicePreprocess
             self._pre = DevicePreprocess(self.device, self.backend)
-        return self._mix_clip(self._jitter_v1(self._pre(batch[self._u8_key(batch)], batch.get("crop")), batch), batch)
+        x = self._pre(batch[self._u8_key(batch)], batch.get("crop"), warp=batch.get("warp"))
+        return self._mix_clip(self._jitter_v1(x, batch), batch)
 
     # ---- the device-side ColorJitter: a batch carrying 'jitter' (N,8), the draws of input_pipeline.draw_color_jitter
     def color_jitter(self) -> "ColorJitter":
@@ -411,6 +438,9 @@ class ModelManager:
     def _float_clip(self, batch) -> torch.Tensor:
         """the float32 (N,T,21,S,S) loader batch on the device (then the batch's 'jitter' and 'mix', if any)"""
         src = batch[self.cfg.MODEL.R3D_INPUT]
+        if "warp" in batch:
+            raise ValueError("a 'warp' entry beside a float32 loader batch: the loader has already cropped the clip, the affine "
+                             "sampling (MODEL.AFFINE) needs the uint8 transport or MODEL.RESIDENT_TRAIN")
         x = self._h2d(src)
         if "jitter" not in batch and "mix" not in batch:
             return x
@@ -433,6 +463,8 @@ class ModelManager:
             raise ValueError(self._NO_FLOAT_CLIP.format("U8_STEM"))
         if "mix" in batch:
             raise ValueError(self._NO_FLOAT_CLIP_MIX.format("U8_STEM"))
+        if "warp" in batch:
+            raise ValueError(self._NO_FLOAT_CLIP_WARP.format("U8_STEM"))
         if self._lut is None:
             self._lut = normalize_lut().to(self.device)
         frames = self._h2d(batch[self._u8_key(batch)])
@@ -479,6 +511,8 @@ class ModelManager:
             raise ValueError("a 'jitter' entry needs MODEL.RES2D_BACKEND = 'engine' (the torch backend has no device kernels)")
         if "mix" in batch:
             raise ValueError("a 'mix' entry needs MODEL.RES2D_BACKEND = 'engine' (the torch backend has no device kernels)")
+        if "warp" in batch:
+            raise ValueError("a 'warp' entry needs MODEL.RES2D_BACKEND = 'engine' (the torch backend has no device kernels)")
         dev = "cpu" if torch.device(self.device).type != "cuda" else self.device
         x = batch[self.cfg.MODEL.R3D_INPUT][:, :, :5].to(dev)
         n, t, c, h, w = x.size()
@@ -599,6 +633,7 @@ class SyntheticChalearn(torch.utils.data.Dataset):
     raw=True: the raw transport's items (input_pipeline.make_raw_item / make_raw_pooled_item) -- every frame a crop of ragged
     (h, w), each side drawn from raw_side = (lo, hi) by a generator of the frame's own; a train item keeps the uint8 item's
     'crop' (and 'jitter'), a test / valid item is one raw pooled video (raw implies pooled there).
+    Under MODEL.AFFINE a uint8 or raw train item carries 'warp' (6,) float32 (input_pipeline.draw_affine) instead of 'crop'.
     An as_uint8 or raw set also offers what ``input_pipeline.ResidentTrainSet`` reads a train set through: ``seq_len(i)``
     (vframes[i], drawn per video from frames_per_video by a generator of its own), ``label(i)`` and ``video_item(i, indices)``,
     whose frame k of video i has the same bytes however it is asked for.  The items above keep their bytes."""
@@ -679,14 +714,14 @@ class SyntheticChalearn(torch.utils.data.Dataset):
         if self.raw:                      # (u8 is drawn all the same: 'crop' and 'jitter' below are the uint8 item's draws)
             from .input_pipeline import make_raw_item
             item = make_raw_item(self.key, [self._raw_frame(i, j, k) for k in range(self.t)], self.labels[i])
-            if self.name == 'train':
-                from .input_pipeline import draw_crop_offsets
-                item['crop'] = draw_crop_offsets(1, self.size // 10, g)[0]
+            if self.name == 'train':                 # 'crop', or 'warp' under MODEL.AFFINE
+                k, row = draw_crop_or_warp(self.cfg, self.size, g)
+                item[k] = row
         elif self.as_uint8:
             item = {self.key + "_u8": u8.permute(0, 2, 3, 1).contiguous(), 'label': self.labels[i]}
-            if self.name == 'train':
-                from .input_pipeline import draw_crop_offsets
-                item['crop'] = draw_crop_offsets(1, self.size // 10, g)[0]
+            if self.name == 'train':                 # 'crop', or 'warp' under MODEL.AFFINE
+                k, row = draw_crop_or_warp(self.cfg, self.size, g)
+                item[k] = row
         else:
             item = {self.key: (u8.float() / 255.0 - 0.45) / 0.225, 'label': self.labels[i]}
         ranges = jitter_ranges(self.cfg) if self.name == 'train' else None
@@ -758,7 +793,8 @@ class ChalearnVideoFramesU8(torch.utils.data.Dataset):
 
     labels: the reference's ``get_labels(name_of_set)`` list of (rgb path, depth path, 1-based label) (default: that call,
     when the reference's utils.chalearn is importable).  'train': one ``random_sampling`` window,
-    {'<R3D_INPUT>_u8': (T, S, S, 21) uint8, 'crop': (2,) int32, 'label': label - 1} (+ 'jitter' under MODEL.COLOR_JITTER).
+    {'<R3D_INPUT>_u8': (T, S, S, 21) uint8, 'crop': (2,) int32, 'label': label - 1} (+ 'jitter' under MODEL.COLOR_JITTER;
+    under MODEL.AFFINE 'warp': (6,) float32, the row of input_pipeline.draw_affine, takes the place of 'crop', here and below).
     'test' / 'valid': {'<R3D_INPUT>_pool': (F, S, S, 21) uint8, 'windows': (K, T) int32, 'label'} -- the frames some uniform
     window references, each read ONCE, a missing frame file as -1 -- or, with pooled=False, the list of
     {'<R3D_INPUT>_u8', 'label'} clips.  read_frame(path, size) -> (size, size, 21) uint8 or None is injectable (default:
@@ -838,8 +874,8 @@ class ChalearnVideoFramesU8(torch.utils.data.Dataset):
         return f
 
     def __getitem__(self, index):
-        from .input_pipeline import (MISSING_BYTE, draw_color_jitter, draw_crop_offsets, make_pooled_item, make_raw_item,
-                                     make_raw_pooled_item, uniform_windows, unpool_item)
+        from .input_pipeline import (MISSING_BYTE, draw_color_jitter, make_pooled_item, make_raw_item, make_raw_pooled_item,
+                                     uniform_windows, unpool_item)
         folder, names, label = self._video(index)
         seq_len = len(names)
         if self.name == "train":
@@ -847,7 +883,8 @@ class ChalearnVideoFramesU8(torch.utils.data.Dataset):
             if self.resize == "device":
                 item = make_raw_item(self.key, [self._read_raw(folder, names[i % seq_len])
                                                 for i in range(start, start + self.clip_len)], label)
-                item["crop"] = draw_crop_offsets(1, self.size // 10)[0]
+                k, row = draw_crop_or_warp(self.cfg, self.size)     # 'crop', or 'warp' under MODEL.AFFINE
+                item[k] = row
                 ranges = jitter_ranges(self.cfg)
                 if ranges is not None:
                     item["jitter"] = draw_color_jitter(1, *ranges)[0]
@@ -856,7 +893,8 @@ class ChalearnVideoFramesU8(torch.utils.data.Dataset):
             for i in range(start, start + self.clip_len):
                 f = self._read(folder, names[i % seq_len])
                 frames.append(torch.full((self.size, self.size, 21), MISSING_BYTE, dtype=torch.uint8) if f is None else f)
-            item = {self.key + "_u8": torch.stack(frames), "crop": draw_crop_offsets(1, self.size // 10)[0], "label": label}
+            k, row = draw_crop_or_warp(self.cfg, self.size)
+            item = {self.key + "_u8": torch.stack(frames), k: row, "label": label}
             ranges = jitter_ranges(self.cfg)
             if ranges is not None:
                 item["jitter"] = draw_color_jitter(1, *ranges)[0]
@@ -1008,7 +1046,8 @@ class Trainer:
         from .input_pipeline import ResidentTrainSet
         return ResidentTrainSet(train_set, self.cfg, self.device, backend, batch_size=self.batch_size,
                                 drop_last=self.train_drop_last, num_workers=self.num_workers, jitter=jitter_ranges(self.cfg),
-                                stem_channels=self.mm.stem_channels() if self.pool_stem else None)
+                                stem_channels=self.mm.stem_channels() if self.pool_stem else None,
+                                affine=affine_ranges(self.cfg))
 
     def _make_resident(self, train_set, backend):
         """MODEL.RESIDENT_TRAIN: the resident set (v1: ResidentTrainSet) train_epoch iterates instead of the train loader"""
