@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void bn_tail_fwd_kernel(const float* __restric
                                                           int64_t* nbt, float* mean, float* invstd, float* scale,
                                                           float* shift, float* __restrict__ t, D* __restrict__ wd) {
   __shared__ float wl[TF_CO][TF_MAXC];
-  __shared__ float gl[TF_MAXC];        // column means g / n
+  __shared__ double gl[TF_MAXC];       // column means g / n, in double: an fp32 mean would put 2^-24 mean^2 into every centred product
   __shared__ double red[4 * TF_CO][2];
   __shared__ float acoef[TF_CO];
   const int co0 = blockIdx.x * TF_CO, tid = threadIdx.x;
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void bn_tail_fwd_kernel(const float* __restric
     const int o = i / c, j = i % c;
     wl[o][j] = co0 + o < cout ? wload<D>(w, (int64_t)(co0 + o) * c + j) : 0.f;
   }
-  for (int j = tid; j < c; j += 256) gl[j] = (float)((double)gvec[j] * inv_n);
+  for (int j = tid; j < c; j += 256) gl[j] = (double)gvec[j] * inv_n;
   __syncthreads();
   constexpr int NR = TF_MAXC / 256;
   // acc = T = W G (the backward's operand).  The VARIANCE is not taken from it: E[y^2] - E[y]^2 cancels mean^2 / var digits of an
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void bn_tail_fwd_kernel(const float* __restric
 #pragma unroll 8                       // 8 rows of G in flight: the loop is bound by the latency of these loads
   for (int j = 0; j < c; ++j) {
     float gj[NR], gc[NR];
-    const double mj = (double)gl[j];
+    const double mj = gl[j];
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
       const int ci = tid + 256 * r;
