@@ -41,8 +41,8 @@ extern "C" {
  * of `a` from it (no constant-1 channel group beside the activation any more); 13 = sfk_conv_pw_dual; 14 = sfk_tuning.igemm_p8 / wgrad_p8,
  * sfk_conv_igemm_family value 4; 15 = sfk_tuning.igemm_halo, family value 5; 16 = sfk_tuning.wgrad_band; 17 = sfk_tuning.stem_v3; 18 = sfk_bn_finalize_apply (19, 20: SFK_BN_SYNC_INTS counters),
  * sfk_bn_bwd_finalize_apply; 21 = the two fused finalize launches, SFK_BN_SYNC_INTS and sfk_tuning.wgrad_target_256 /
- * wgrad_min_stages_256 removed, stem_v3 bit 2 retired. */
-#define SFK_ABI_VERSION 21
+ * wgrad_min_stages_256 removed, stem_v3 bit 2 retired; 22 = sfk_conv_igemm_route / sfk_conv_wgrad_route and the route enums. */
+#define SFK_ABI_VERSION 22
 #define SFK_MAX_TAPS 16
 #define SFK_BN_FOLD_ROWS 64 /* rows of the optional BatchNorm fold workspace */
 
@@ -202,6 +202,72 @@ int sfk_conv_wgrad_dg_supported(const sfk_wgrad_desc* d);        /* the fused da
 /* 1 when d would run one of the 256-column tiles of the MFMA-bound layers, which sum their pixel splits ONLY through `workspace`
  * (sfk_conv_wgrad_workspace_bytes(d) bytes; without it the call still works, on the 128-column tile with atomics) */
 int sfk_conv_wgrad_wants_workspace(const sfk_wgrad_desc* d);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Routes: WHICH kernel instantiation sfk_conv_igemm / sfk_conv_wgrad run for a descriptor (host-only queries for tests and
+ * reports).  Both answers are produced by the launch code itself, run without launching, so they cannot disagree with
+ * the dispatch.  A route is a packed integer:
+ *   sfk_conv_igemm_route: SFK_IGEMM_ROUTE(kernel, bf16, bm, bn, epi, shortk, wide)
+ *     kernel  sfk_igemm_kernel;  bf16 = 1 for SFK_BF16 maps;  bm = pixel rows a tile computes (128 / 224 / 256), bn = output
+ *     channels of a tile (16 .. 256);  epi = the epilogue flavour: 0 plain, 1 BatchNorm-backward reduce (5 its bitmap
+ *     flavour, 6 its += flavour, 7 with a mask source), 2 out_relu_bits, 3 fused output transform (4 with the shortcut
+ *     pre-fetched);  shortk = the exact-count K loop;  wide = 16-byte (8 x bf16) stores are taken.
+ *     The streaming pointwise kernels (conv_pw.hip) report bm = 32 x the K-steps of the resident filter, bn = cout, epi = 0
+ *     (1: the data-gradient flavour with bitmap mask and column sums).
+ *   sfk_conv_wgrad_route: SFK_WGRAD_ROUTE(kernel, bf16, tco, tci, ksnw, gram, dg) in the low 29 bits, then
+ *     SFK_WGRAD_ROUTE_WS(r) = 1 when THIS descriptor's workspace / workspace_bytes select the workspace path (0: float
+ *     atomics, also when the workspace is too small) and SFK_WGRAD_ROUTE_SPLITS(r) = the pixel splits.
+ *     kernel  sfk_wgrad_kernel;  tco x tci = the dW tile;  ksnw = K-steps per stage (CFG) or waves per workgroup (DMA, P8,
+ *     BAND);  gram = one staged tile serves x and dy;  dg = with the fused data gradient.
+ * SFK_IGEMM_ROUTES / SFK_WGRAD_ROUTES list every route reachable with the default tuning table and operands below
+ * 2 GiB (beyond that the bf16 ring kernels hand over to the register-staged 128 x 128 tile, a route outside this list). */
+typedef enum { SFK_IK_REG = 0, SFK_IK_DMA = 1, SFK_IK_PWP = 2, SFK_IK_PWF = 3, SFK_IK_P8 = 4, SFK_IK_HALO = 5, SFK_IK_PWD = 6 } sfk_igemm_kernel;
+/* REG register-staged, DMA LDS-DMA ring, PWP / PWF / PWD streaming pointwise plain / fused output transform / data gradient,
+ * P8 deep-pipelined 256 x 256 tile, HALO LDS-band 3 x 3.  sfk_conv_igemm_family = the kernel, with PWP / PWF / PWD all 3. */
+typedef enum { SFK_WK_CFG = 0, SFK_WK_DMA = 1, SFK_WK_P8 = 2, SFK_WK_BAND = 3 } sfk_wgrad_kernel;
+#define SFK_IGEMM_ROUTE(kernel, bf16, bm, bn, epi, shortk, wide) \
+  (((bf16) << 28) | ((kernel) << 24) | ((bm) << 15) | ((bn) << 5) | ((epi) << 2) | ((shortk) << 1) | (wide))
+#define SFK_IGEMM_ROUTE_KERNEL(r) (((r) >> 24) & 15)
+#define SFK_WGRAD_ROUTE(kernel, bf16, tco, tci, ksnw, gram, dg) \
+  (((bf16) << 28) | ((kernel) << 24) | ((tco) << 15) | ((tci) << 6) | ((ksnw) << 2) | ((gram) << 1) | (dg))
+#define SFK_WGRAD_ROUTE_ID(r) ((int)((r) & 0x1FFFFFFF))
+#define SFK_WGRAD_ROUTE_WS(r) ((int)(((r) >> 29) & 1))
+#define SFK_WGRAD_ROUTE_SPLITS(r) ((int)((r) >> 32))
+/* X(kernel, bf16, bm, bn, epi, shortk, wide) */
+#define SFK_IGEMM_ROUTES(X) \
+  X(REG, 0, 128, 128, 0, 0, 0) X(REG, 0, 256, 64, 0, 0, 0) X(REG, 0, 256, 32, 0, 0, 0) X(REG, 0, 256, 32, 0, 1, 0) \
+  X(REG, 0, 256, 16, 0, 0, 0) X(REG, 0, 256, 16, 0, 1, 0) X(REG, 0, 128, 128, 2, 0, 0) X(REG, 0, 256, 64, 2, 0, 0) \
+  X(REG, 0, 256, 32, 2, 0, 0) X(REG, 0, 256, 16, 2, 0, 0) X(REG, 0, 128, 128, 3, 0, 0) X(REG, 0, 256, 64, 3, 0, 0) \
+  X(REG, 0, 256, 32, 3, 0, 0) X(REG, 0, 256, 16, 3, 0, 0) X(REG, 1, 256, 64, 0, 0, 0) X(REG, 1, 256, 64, 0, 0, 1) \
+  X(REG, 1, 256, 32, 0, 0, 0) X(REG, 1, 256, 32, 0, 0, 1) X(REG, 1, 256, 32, 0, 1, 0) X(REG, 1, 256, 32, 0, 1, 1) \
+  X(REG, 1, 256, 16, 0, 0, 0) X(REG, 1, 256, 16, 0, 1, 0) X(REG, 1, 256, 64, 3, 0, 1) X(REG, 1, 256, 32, 3, 0, 1) \
+  X(REG, 1, 256, 16, 3, 0, 0) X(REG, 1, 256, 64, 1, 0, 1) X(REG, 1, 256, 32, 1, 0, 1) X(REG, 1, 256, 64, 2, 0, 1) \
+  X(REG, 1, 256, 32, 2, 0, 1) X(REG, 1, 256, 64, 5, 0, 1) X(REG, 1, 256, 32, 5, 0, 1) X(REG, 1, 256, 64, 6, 0, 1) \
+  X(REG, 1, 256, 32, 6, 0, 1) X(REG, 1, 256, 64, 7, 0, 1) X(REG, 1, 256, 32, 7, 0, 1) X(DMA, 1, 224, 256, 0, 0, 0) \
+  X(DMA, 1, 224, 256, 0, 0, 1) X(DMA, 1, 256, 256, 0, 0, 0) X(DMA, 1, 256, 256, 0, 0, 1) X(DMA, 1, 128, 128, 0, 0, 0) \
+  X(DMA, 1, 128, 128, 0, 0, 1) X(DMA, 1, 256, 128, 0, 0, 0) X(DMA, 1, 256, 128, 0, 0, 1) X(DMA, 1, 128, 128, 1, 0, 1) \
+  X(DMA, 1, 128, 128, 5, 0, 1) X(DMA, 1, 128, 128, 6, 0, 1) X(DMA, 1, 128, 128, 7, 0, 1) X(DMA, 1, 128, 128, 2, 0, 1) \
+  X(DMA, 1, 256, 128, 2, 0, 1) X(DMA, 1, 128, 128, 3, 0, 1) X(DMA, 1, 256, 128, 3, 0, 1) X(DMA, 1, 128, 128, 4, 0, 1) \
+  X(P8, 1, 256, 256, 0, 0, 1) X(P8, 1, 256, 256, 2, 0, 1) \
+  X(HALO, 1, 224, 64, 0, 0, 1) X(PWF, 1, 32, 32, 0, 0, 1) X(PWF, 1, 32, 64, 0, 0, 1) X(PWF, 1, 64, 64, 0, 0, 1) \
+  X(PWF, 1, 32, 128, 0, 0, 1) X(PWF, 1, 128, 128, 0, 0, 1) X(PWF, 1, 64, 256, 0, 0, 1) X(PWF, 1, 128, 320, 0, 0, 1) \
+  X(PWF, 1, 128, 512, 0, 0, 1) X(PWP, 1, 64, 64, 0, 0, 1) X(PWP, 1, 128, 128, 0, 0, 1) X(PWP, 1, 128, 320, 0, 0, 1) \
+  X(PWD, 1, 64, 256, 1, 0, 1) X(PWD, 1, 128, 512, 1, 0, 1)
+/* X(kernel, bf16, tco, tci, ksnw, gram, dg) */
+#define SFK_WGRAD_ROUTES(X) \
+  X(CFG, 0, 32, 32, 4, 0, 0) X(CFG, 0, 64, 32, 4, 0, 0) X(CFG, 0, 128, 32, 2, 0, 0) X(CFG, 0, 32, 128, 2, 0, 0) \
+  X(CFG, 0, 64, 128, 2, 0, 0) X(CFG, 0, 128, 128, 1, 0, 0) X(CFG, 0, 32, 32, 4, 1, 0) X(CFG, 0, 64, 64, 2, 1, 0) \
+  X(CFG, 0, 128, 128, 1, 1, 0) X(CFG, 1, 32, 32, 4, 0, 0) X(CFG, 1, 64, 32, 4, 0, 0) X(CFG, 1, 128, 32, 2, 0, 0) \
+  X(CFG, 1, 32, 128, 2, 0, 0) X(CFG, 1, 64, 128, 2, 0, 0) X(CFG, 1, 128, 128, 1, 0, 0) X(CFG, 1, 32, 32, 4, 1, 0) \
+  X(CFG, 1, 64, 64, 2, 1, 0) X(CFG, 1, 128, 128, 1, 1, 0) X(CFG, 1, 256, 64, 1, 0, 0) X(DMA, 1, 128, 128, 4, 0, 0) \
+  X(DMA, 1, 256, 128, 8, 0, 0) X(DMA, 1, 256, 128, 8, 0, 1) X(P8, 1, 256, 256, 8, 0, 0) X(BAND, 1, 64, 64, 8, 0, 0) \
+  X(BAND, 1, 128, 128, 8, 0, 0)
+#define SFK_IR_ENUM_(k, b, bm, bn, e, s, w) SFK_IR_##k##_T##b##_##bm##x##bn##_E##e##_S##s##_W##w = SFK_IGEMM_ROUTE(SFK_IK_##k, b, bm, bn, e, s, w),
+#define SFK_WR_ENUM_(k, b, tco, tci, n, g, d) SFK_WR_##k##_T##b##_##tco##x##tci##_N##n##_G##g##_D##d = SFK_WGRAD_ROUTE(SFK_WK_##k, b, tco, tci, n, g, d),
+typedef enum { SFK_IGEMM_ROUTES(SFK_IR_ENUM_) SFK_IR_NONE_ = -1 } sfk_igemm_route;
+typedef enum { SFK_WGRAD_ROUTES(SFK_WR_ENUM_) SFK_WR_NONE_ = -1 } sfk_wgrad_route;
+int sfk_conv_igemm_route(const sfk_conv_desc* d);     /* sfk_igemm_route (or a route outside the list, see above); < 0: sfk_status */
+int64_t sfk_conv_wgrad_route(const sfk_wgrad_desc* d); /* sfk_wgrad_route + WS + SPLITS; < 0: sfk_status */
 
 /* ---------------------------------------------------------------------------------------------------------
  * sfk_stem_conv_fwd / sfk_stem_conv_wgrad -- the stem Conv3d (kt,7,7) stride (1,2,2) padding (kt/2,3,3), bias=False

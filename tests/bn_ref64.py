@@ -32,16 +32,13 @@ SPAN_U = 4                     # pixel rows a thread of the streaming kernels ha
 GRID_CAP = 65535               # blocks of the apply grids (csrc/bn.hip span_blocks)
 
 
-SMALL_MAP = 2048               # elements below which a bf16 map's aggregate ratio says nothing (see compare)
+SMALL_MAP = ref64.SMALL_MAP     # elements below which a bf16 map's aggregate ratio says nothing (ref64.elem_only)
 
 
 def compare(name, y, r, a, k, dtype, kind, alt=None, alt_mask=None):
-    """ref64.compare, unchanged.  Its aggregate bound for a bf16 map (2^-9) is the rms of a rounding error uniform in +- half
-    an ulp -- 0.0016 to 0.0017 for honest rounding -- and is met only once many elements average out: EmuBackend's correctly
-    rounded 8- and 80-element maps come out at 0.0020 to 0.0022.  Below SMALL_MAP elements such a map is therefore judged by
-    its element bound alone (head_ref64.ElemOnly), as a lone scalar is."""
-    v = ref64.compare(name, y, r, a, k, dtype, kind, alt=alt, alt_mask=alt_mask)
-    return ElemOnly(v) if kind == "map_bf16" and v.n < SMALL_MAP else v
+    """ref64.judge: ref64.compare, with a bf16 map that ref64.elem_only names (fewer than SMALL_MAP elements) judged by its
+    element bound alone, as a lone scalar is"""
+    return ref64.judge(name, y, r, a, k, dtype, kind, alt=alt, alt_mask=alt_mask)
 
 
 def vec_of(dtype) -> int:

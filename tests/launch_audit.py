@@ -21,7 +21,7 @@ from typing import Dict
 import torch
 
 import ref64
-from ref64 import F64, compare
+from ref64 import F64
 from video_classification_amd._lib import (BnBwdFuse, ConvEpilogue, ConvPass, FMap, StemSrc, WgradPass, stem_kp)
 
 AUDITED = ("conv_igemm", "conv_wgrad", "conv_pw_dual", "stem_conv_fwd", "stem_conv_wgrad", "stem2d_fwd", "stem2d_wgrad",
@@ -633,9 +633,12 @@ def _prepare_inputs(method, A, gen, be):
 class Replay:
     """the outcome of one replayed signature"""
 
-    def __init__(self, sig, family, verdicts, untouched_ok, untouched_bad):
+    def __init__(self, sig, family, verdicts, untouched_ok, untouched_bad, route=None, ambiguous=0.0, args=None):
         self.sig, self.family, self.verdicts = sig, family, verdicts
         self.untouched_ok, self.untouched_bad = untouched_ok, untouched_bad
+        self.route = route                # what the backend's route query says of the REPLAYED descriptor (None: no query)
+        self.ambiguous = ambiguous        # largest share of a map's elements whose ReLU sign the reference cannot decide
+        self.args = args                  # the decoded arguments after the launch (for a second, bit-compared run)
 
     @property
     def ok(self):
@@ -647,7 +650,7 @@ class Replay:
 
     @property
     def agg(self):
-        return max([v.agg / v.agg_bound for v in self.verdicts] + [0.0])
+        return max([v.agg / v.agg_bound for v in self.verdicts] + [0.0])     # (0 for a map judged by its elements alone)
 
 
 def describe(sig) -> str:
@@ -693,6 +696,11 @@ def replay(sig, be, device, seed: int = 0) -> Replay:
     A = {k: _decode(e, bufs) for k, e in args}
     _prepare_inputs(method, A, gen, be)
     fam = be.conv_family(A["p"]) if method == "conv_igemm" and hasattr(be, "conv_family") else None
+    route = None
+    if method == "conv_igemm" and hasattr(be, "conv_route"):
+        route = be.conv_route(A["p"])
+    elif method == "conv_wgrad" and hasattr(be, "conv_wgrad_route"):
+        route = be.conv_wgrad_route(A["p"])
     before = Buffers(groups, device)
     for b, a in zip(before.views, bufs.views):
         b.copy_(a)
@@ -732,7 +740,7 @@ def replay(sig, be, device, seed: int = 0) -> Replay:
                 where = f"{bad} bad, first {i}: got {int(g.reshape(-1)[i])} want {int(o.ref.reshape(-1)[i])}"
             verdicts.append(ref64.Verdict(o.name, o.kind, 0.0 if bad == 0 else float("inf"), 0.0, 1.0, g.numel(), where))
             continue
-        verdicts.append(compare(o.name, got, o.ref, o.a, o.k, o.dtype, o.kind, alt=o.alt, alt_mask=o.alt_mask))
+        verdicts.append(ref64.judge(o.name, got, o.ref, o.a, o.k, o.dtype, o.kind, alt=o.alt, alt_mask=o.alt_mask))
     # untouched: restore every written region from the snapshot; then the whole allocation must equal the snapshot
     after = Buffers(groups, device)
     for b, a in zip(after.views, bufs.views):
@@ -741,7 +749,9 @@ def replay(sig, be, device, seed: int = 0) -> Replay:
     for o in outs:
         o.view(Aft).copy_(o.view(B))
     bad = [i for i, (x, y) in enumerate(zip(after.views, before.views)) if not torch.equal(x, y)]
-    return Replay(sig, fam, verdicts, not bad, bad)
+    amb = max([float(o.alt_mask.double().mean()) for o in outs
+               if o.alt_mask is not None and o.kind.startswith("map_") and o.alt_mask.numel()] + [0.0])
+    return Replay(sig, fam, verdicts, not bad, bad, route, amb, A)
 
 
 def _check_argmax(o: _ArgmaxOut, arg: torch.Tensor) -> ref64.Verdict:

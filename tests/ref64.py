@@ -84,6 +84,26 @@ def compare(name: str, y: torch.Tensor, r: torch.Tensor, a: torch.Tensor, k: flo
     return Verdict(name, kind, worst, agg, AGG_BOUND[kind], r.numel(), where=worst_i)
 
 
+SMALL_MAP = 2048               # elements below which a bf16 map's aggregate ratio says nothing (see elem_only)
+
+
+def elem_only(kind: str, n: int) -> bool:
+    """The aggregate bound of a bf16 map (2^-9) is the rms of a rounding error uniform in +- half an ulp -- 0.0016 to 0.0017
+    for honest rounding -- and is met only once many elements average out: EmuBackend's correctly rounded 8-, 24- and
+    80-element maps come out at 0.0020 to 0.0022.  Below SMALL_MAP elements such a map is therefore judged by its element
+    bound alone, as a lone scalar is.  The ONE statement of that rule: bn_ref64.compare and launch_audit.replay use it."""
+    return kind == "map_bf16" and n < SMALL_MAP
+
+
+def judge(name, y, r, a, k, dtype, kind, alt=None, alt_mask=None) -> Verdict:
+    """compare(), with a map that elem_only() names judged by its element bound alone (agg is still reported)"""
+    v = compare(name, y, r, a, k, dtype, kind, alt=alt, alt_mask=alt_mask)
+    if elem_only(kind, v.n):
+        v.agg_bound = float("inf")
+        v.ok = v.worst <= 1.0
+    return v
+
+
 def rounded(r: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     return r.to(dtype).double()
 

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFK_LIB") or os.path.join(HERE, "libsfk.so")   # SFK_LIB: experiment builds (tools/gpu_ab_lib.sh)
 SFK_F32, SFK_BF16 = 0, 1
 SFK_MAX_TAPS = 16
-ABI_VERSION = 21       # include/sfk.h SFK_ABI_VERSION
+ABI_VERSION = 22       # include/sfk.h SFK_ABI_VERSION
 BN_FOLD_ROWS = 64      # include/sfk.h SFK_BN_FOLD_ROWS
 _DT = {torch.float32: SFK_F32, torch.bfloat16: SFK_BF16}
 
@@ -365,6 +365,7 @@ SIGNATURES = {
     "sfk_conv_relu_out_supported": [C.POINTER(_ConvDesc)],
     "sfk_conv_epilogue_supported": [C.POINTER(_ConvDesc)],
     "sfk_conv_igemm_family": [C.POINTER(_ConvDesc)],
+    "sfk_conv_igemm_route": [C.POINTER(_ConvDesc)],
     "sfk_bn_tail_fwd": [_PF, _PF, _I32, _I64, _PF, _I32, _PV, _I32, _I32, _PF, _PF, _F, _F, _PF, _PF, _PV, _PF, _PF, _PF, _PF, _PF, _PV, _PV],
     "sfk_bn_tail_bwd": [_PF, _PF, _I32, _PF, _I64, _PF, _I32, _PV, _I32, _I32, _PF, _PF, _PF, _PF, _PF, _PF, _PV, _PF, _PF, _PV],
     "sfk_conv_pw_dual_supported": [_P_FMAP, _P_FMAP, _P_FMAP],
@@ -373,6 +374,7 @@ SIGNATURES = {
     "sfk_conv_wgrad_workspace_bytes": [C.POINTER(_WgradDesc)],
     "sfk_conv_wgrad_dg_supported": [C.POINTER(_WgradDesc)],
     "sfk_conv_wgrad_wants_workspace": [C.POINTER(_WgradDesc)],
+    "sfk_conv_wgrad_route": [C.POINTER(_WgradDesc)],
     "sfk_stem_kp": [_I32, _I32],
     "sfk_stem_conv_tiles": [C.POINTER(_StemSrc), _P_FMAP],
     "sfk_stem_conv_fwd": [C.POINTER(_StemSrc), _PV, _P_FMAP, _PF, _PV],
@@ -549,7 +551,7 @@ SIGNATURES_WARP = {
     "sfk_u8_pool_gather_warp": [C.POINTER(_PoolWarpDesc), _PV],
     "sfk_warp_fallback_tiles": [_I32, _I32, _I32, _I32, _PF],
 }
-_RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_groups_prepare": C.c_int64, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
+_RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_route": C.c_int64, "sfk_groups_prepare": C.c_int64, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
 
@@ -850,6 +852,13 @@ class HipBackend:
         256 x 256 tile (conv_igemm_p8.hip), 5 the LDS-band 3 x 3 kernel (conv_halo.hip)"""
         return int(self.lib.sfk_conv_igemm_family(C.byref(_c_conv(p))))
 
+    def conv_route(self, p: ConvPass) -> int:
+        """the kernel instantiation sfk_conv_igemm runs for p: an sfk_igemm_route of include/sfk.h (the launch code run dry)"""
+        r = int(self.lib.sfk_conv_igemm_route(C.byref(_c_conv(p))))
+        if r < 0:
+            _check(r, "sfk_conv_igemm_route")
+        return r
+
     def conv_igemm(self, p: ConvPass):
         d, fn, keep = _c_conv(p), self.lib.sfk_conv_igemm, p
 
@@ -883,6 +892,16 @@ class HipBackend:
         if r < 0:
             _check(int(r), "sfk_conv_wgrad_workspace_bytes")
         return int(r)
+
+    def conv_wgrad_route(self, p: WgradPass) -> Tuple[int, bool, int]:
+        """(sfk_wgrad_route of include/sfk.h, workspace path taken with p.workspace, pixel splits) of sfk_conv_wgrad(p)"""
+        d = self._wgrad_desc(p)
+        if p.workspace is not None:
+            d.workspace, d.workspace_bytes = p.workspace.data_ptr(), p.workspace.numel() * p.workspace.element_size()
+        r = int(self.lib.sfk_conv_wgrad_route(C.byref(d)))
+        if r < 0:
+            _check(r, "sfk_conv_wgrad_route")
+        return r & 0x1FFFFFFF, bool((r >> 29) & 1), r >> 32
 
     def conv_wgrad(self, p: WgradPass):
         d = self._wgrad_desc(p)

@@ -231,7 +231,12 @@ __attribute__((visibility("hidden"))) bool halo_ok(const sfk_conv_desc* d) {
 
 __attribute__((visibility("hidden"))) int halo_mtiles(const sfk_conv_desc* d) { return d->x.n * d->x.t * (d->x.h / 4); }
 
-__attribute__((visibility("hidden"))) int launch_halo(const ConvK& k, const sfk_conv_desc* d, hipStream_t s) {
+__attribute__((visibility("hidden"))) int launch_halo(const ConvK& k, const sfk_conv_desc* d, hipStream_t s, int* dry) {
+  if (dry) {       // the route (include/sfk.h) instead of the launch: bands of 4 x 56 pixels, all 64 channels
+    const int wide = wide_store_taken<bf16_t, 2>(k) ? 1 : 0;          // (FN = 2: epilogue_plain<T, EPI, 7, 2, ..> above)
+    *dry = SFK_IGEMM_ROUTE(SFK_IK_HALO, 1, 224, 64, 0, 0, wide);
+    return SFK_OK;
+  }
   const int bpf = d->x.h / 4, nbands = d->x.n * d->x.t * bpf;
   const int grid = nbands < 256 ? nbands : 256;
   HaloTaps ht;

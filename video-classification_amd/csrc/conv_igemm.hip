@@ -17,11 +17,11 @@ using namespace sfk_igemm;
 
 namespace sfk_igemm {
 // conv_igemm_p8.hip
-__attribute__((visibility("hidden"))) int launch_p8(const ConvK& k, int bms, dim3 grid, hipStream_t s);
+__attribute__((visibility("hidden"))) int launch_p8(const ConvK& k, int bms, dim3 grid, hipStream_t s, int* dry);
 // conv_halo.hip
 __attribute__((visibility("hidden"))) bool halo_ok(const sfk_conv_desc* d);
 __attribute__((visibility("hidden"))) int halo_mtiles(const sfk_conv_desc* d);
-__attribute__((visibility("hidden"))) int launch_halo(const ConvK& k, const sfk_conv_desc* d, hipStream_t s);
+__attribute__((visibility("hidden"))) int launch_halo(const ConvK& k, const sfk_conv_desc* d, hipStream_t s, int* dry);
 }
 
 namespace {
@@ -33,7 +33,7 @@ template <typename T, int BM, int BN, int WM, int WN, bool SHORTK, int EPI = 0>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 3 : 1)) void conv_igemm_kernel(const ConvK k) {
   using TL = Tile<T>;
   constexpr int VEC = TL::VEC, SEGS = TL::SEGS, ROWB = TL::ROWB;
-  constexpr int FM = BM / WM / 16, FN = BN / WN / 16;
+  constexpr int FM = BM / WM / 16, FN = co_frags(BN, WN);
   constexpr int RPI = 256 / SEGS;              // tile rows covered by one pass of the 256 threads
   constexpr int XL = BM / RPI;                 // gathered-pixel loads per thread per K-step
   constexpr int WL = (BN + RPI - 1) / RPI;     // filter loads per thread per K-step
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(64 * WM * WN, (BN == 256 ? 2 : (WM * WN == 8 ? 4 : 
   using T = bf16_t;
   using TL = Tile<bf16_t>;
   constexpr int VEC = 8, SEGS = 4, ROWB = 64;
-  constexpr int FM = BMS / WM / 16, FN = BN / WN / 16;
+  constexpr int FM = BMS / WM / 16, FN = co_frags(BN, WN);
   static_assert(BMS <= BM && BMS % (16 * WM) == 0, "computed rows");
   constexpr int NW = WM * WN;                  // waves per block (4 or 8)
   constexpr int WROWS = BN < 16 * NW ? 16 * NW : BN;   // every wave issues the same number of filter DMAs (rows >= BN are OOB)
@@ -624,43 +624,53 @@ int validate(const sfk_conv_desc* d) {
   return SFK_OK;
 }
 
-int launch_dma(const ConvK& k, int bm, dim3 grid, hipStream_t s, int bn = 128) {
-  if (bn == 256) {
-    if (bm == 224) hipLaunchKernelGGL((conv_igemm_dma_kernel<256, 256, 2, 4, 0, 224>), grid, dim3(512), 0, s, k);
-    else hipLaunchKernelGGL((conv_igemm_dma_kernel<256, 256, 4, 2>), grid, dim3(512), 0, s, k);
-    SFK_CHECK_LAUNCH();
+// One instantiation = one route (include/sfk.h): with `dry` the launch code reports it instead of launching, so
+// sfk_conv_igemm_route cannot disagree with the dispatch.
+template <typename T, int BM, int BN, int WM, int WN, bool SHORTK, int EPI = 0>
+int run_reg(const ConvK& k, dim3 grid, hipStream_t s, int* dry) {
+  if (dry) {
+    constexpr int FN = co_frags(BN, WN);
+    const int wide = wide_store_taken<T, FN>(k) ? 1 : 0;
+    *dry = SFK_IGEMM_ROUTE(SFK_IK_REG, sizeof(T) == 2 ? 1 : 0, BM, BN, EPI, SHORTK ? 1 : 0, wide);
     return SFK_OK;
   }
-  if (k.bn_parts) {          // (pick_tile: never 256 x 128); 5 = the bitmap flavour (mask = out_relu_bits, sums of dz only)
-    // (6 = with the old values of a += pass, 7 = with a mask source)
-    if (k.bn_y == nullptr) hipLaunchKernelGGL((conv_igemm_dma_kernel<128, 128, 2, 2, 5>), grid, dim3(256), 0, s, k);
-    else if (k.bn_mask) hipLaunchKernelGGL((conv_igemm_dma_kernel<128, 128, 2, 2, 7>), grid, dim3(256), 0, s, k);
-    else if (k.accumulate) hipLaunchKernelGGL((conv_igemm_dma_kernel<128, 128, 2, 2, 6>), grid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL((conv_igemm_dma_kernel<128, 128, 2, 2, 1>), grid, dim3(256), 0, s, k);
-    SFK_CHECK_LAUNCH();
+  hipLaunchKernelGGL((conv_igemm_kernel<T, BM, BN, WM, WN, SHORTK, EPI>), grid, dim3(256), 0, s, k);
+  SFK_CHECK_LAUNCH();
+  return SFK_OK;
+}
+template <int BM, int BN, int WM, int WN, int EPI = 0, int BMS = BM>
+int run_dma(const ConvK& k, dim3 grid, hipStream_t s, int* dry) {
+  if (dry) {
+    constexpr int FN = co_frags(BN, WN);
+    const int wide = wide_store_taken<bf16_t, FN>(k) ? 1 : 0;
+    *dry = SFK_IGEMM_ROUTE(SFK_IK_DMA, 1, BMS, BN, EPI, 0, wide);
     return SFK_OK;
   }
-  if (k.ep_on) {
-    if (bm == 256) hipLaunchKernelGGL((conv_igemm_dma_kernel<256, 128, 4, 2, 3>), grid, dim3(512), 0, s, k);
-    else if (k.ep_res) hipLaunchKernelGGL((conv_igemm_dma_kernel<128, 128, 2, 2, 4>), grid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL((conv_igemm_dma_kernel<128, 128, 2, 2, 3>), grid, dim3(256), 0, s, k);
-    SFK_CHECK_LAUNCH();
-    return SFK_OK;
-  }
-  if (k.obits) {
-    if (bm == 256) hipLaunchKernelGGL((conv_igemm_dma_kernel<256, 128, 4, 2, 2>), grid, dim3(512), 0, s, k);
-    else hipLaunchKernelGGL((conv_igemm_dma_kernel<128, 128, 2, 2, 2>), grid, dim3(256), 0, s, k);
-    SFK_CHECK_LAUNCH();
-    return SFK_OK;
-  }
-  if (bm == 256) hipLaunchKernelGGL((conv_igemm_dma_kernel<256, 128, 4, 2>), grid, dim3(512), 0, s, k);
-  else hipLaunchKernelGGL((conv_igemm_dma_kernel<128, 128, 2, 2>), grid, dim3(256), 0, s, k);
+  hipLaunchKernelGGL((conv_igemm_dma_kernel<BM, BN, WM, WN, EPI, BMS>), grid, dim3(64 * WM * WN), 0, s, k);
   SFK_CHECK_LAUNCH();
   return SFK_OK;
 }
 
+int launch_dma(const ConvK& k, int bm, dim3 grid, hipStream_t s, int bn, int* dry) {
+  if (bn == 256) return bm == 224 ? run_dma<256, 256, 2, 4, 0, 224>(k, grid, s, dry) : run_dma<256, 256, 4, 2>(k, grid, s, dry);
+  if (k.bn_parts) {          // (pick_tile: never 256 x 128); 5 = the bitmap flavour (mask = out_relu_bits, sums of dz only)
+    // (6 = with the old values of a += pass, 7 = with a mask source)
+    if (k.bn_y == nullptr) return run_dma<128, 128, 2, 2, 5>(k, grid, s, dry);
+    if (k.bn_mask) return run_dma<128, 128, 2, 2, 7>(k, grid, s, dry);
+    if (k.accumulate) return run_dma<128, 128, 2, 2, 6>(k, grid, s, dry);
+    return run_dma<128, 128, 2, 2, 1>(k, grid, s, dry);
+  }
+  if (k.ep_on) {
+    if (bm == 256) return run_dma<256, 128, 4, 2, 3>(k, grid, s, dry);
+    if (k.ep_res) return run_dma<128, 128, 2, 2, 4>(k, grid, s, dry);
+    return run_dma<128, 128, 2, 2, 3>(k, grid, s, dry);
+  }
+  if (k.obits) return bm == 256 ? run_dma<256, 128, 4, 2, 2>(k, grid, s, dry) : run_dma<128, 128, 2, 2, 2>(k, grid, s, dry);
+  return bm == 256 ? run_dma<256, 128, 4, 2>(k, grid, s, dry) : run_dma<128, 128, 2, 2>(k, grid, s, dry);
+}
+
 template <typename T>
-int launch(const sfk_conv_desc* d, hipStream_t s) {
+int launch(const sfk_conv_desc* d, hipStream_t s, int* dry = nullptr) {
   ConvK k;
   k.x = d->x.ptr; k.y = d->y.ptr; k.w = d->w; k.stats = d->stats;
   k.xt = d->x.t; k.xh = d->x.h; k.xw = d->x.w; k.xld = d->x.ld; k.xoff = d->x.c_off;
@@ -708,12 +718,12 @@ int launch(const sfk_conv_desc* d, hipStream_t s) {
     if (k.ep_on && (d->ep.res.ptr || d->ep.relu) && !d->accumulate && sfk_tune().igemm_pw_stream && d->ntaps == 1 &&
         d->taps[0].dt == 0 && d->taps[0].dh == 0 && d->taps[0].dw == 0 && d->gs[0] == 1 && d->gs[1] == 1 && d->gs[2] == 1 &&
         k.lin_out && d->x.t == d->y.t && d->x.h == d->y.h && d->x.w == d->y.w) {
-      const int r = sfk_conv_pw_fused(d, s);
+      const int r = sfk_conv_pw_fused(d, s, dry, SFK_IK_PWF);
       if (r != SFK_ERR_UNSUPPORTED) return r;
     }
-    if (pw_dgrad_rows(d) > 0) return sfk_conv_pw_dgrad(d, s);
+    if (pw_dgrad_rows(d) > 0) return sfk_conv_pw_dgrad(d, s, dry);
     if (pw_plain_route(d)) {
-      const int r = sfk_conv_pw_fused(d, s);
+      const int r = sfk_conv_pw_fused(d, s, dry, SFK_IK_PWP);
       if (r != SFK_ERR_UNSUPPORTED) return r;
     }
   }
@@ -721,66 +731,67 @@ int launch(const sfk_conv_desc* d, hipStream_t s) {
     if (halo_ok(d)) {                  // (1,3,3) stride-1 convs of slow res2 / res3: the LDS-band kernel (conv_halo.hip)
       k.mtiles = halo_mtiles(d);
       k.ntiles = 1;
-      return launch_halo(k, d, s);
+      return launch_halo(k, d, s, dry);
     }
   }
   const TileSel ts = pick_tile(d);
   k.mtiles = (k.M + ts.bm - 1) / ts.bm;
   k.ntiles = (d->cout + ts.bn - 1) / ts.bn;
-  const dim3 grid((unsigned)(k.mtiles * k.ntiles)), block(256);
+  const dim3 grid((unsigned)(k.mtiles * k.ntiles));
   // bf16: LDS-DMA ring for the wide tile; narrow outputs keep the register-staged kernel (higher occupancy, tiny K)
-  if (ts.p8) return launch_p8(k, ts.bm, dim3((unsigned)(k.mtiles * k.ntiles)), s);
-  if (ts.dma) return launch_dma(k, ts.bm, grid, s, ts.bn);
+  if (ts.p8) return launch_p8(k, ts.bm, grid, s, dry);
+  if (ts.dma) return launch_dma(k, ts.bm, grid, s, ts.bn, dry);
   if (k.bn_parts) {          // fused BatchNorm-backward reduce (bf16, cout > 16: tiles of 32..128 output channels)
     if constexpr (sizeof(T) == 2) {
       if (k.bn_y == nullptr) {      // the bitmap flavour
-        if (ts.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<T, 128, 128, 2, 2, false, 5>), grid, block, 0, s, k);
-        else if (ts.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 64, 4, 1, false, 5>), grid, block, 0, s, k);
-        else hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 32, 4, 1, false, 5>), grid, block, 0, s, k);
-      } else if (k.bn_mask) {       // with a mask source
-        if (ts.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<T, 128, 128, 2, 2, false, 7>), grid, block, 0, s, k);
-        else if (ts.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 64, 4, 1, false, 7>), grid, block, 0, s, k);
-        else hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 32, 4, 1, false, 7>), grid, block, 0, s, k);
-      } else if (k.accumulate) {    // with the old values of a += pass
-        if (ts.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<T, 128, 128, 2, 2, false, 6>), grid, block, 0, s, k);
-        else if (ts.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 64, 4, 1, false, 6>), grid, block, 0, s, k);
-        else hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 32, 4, 1, false, 6>), grid, block, 0, s, k);
-      } else if (ts.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<T, 128, 128, 2, 2, false, 1>), grid, block, 0, s, k);
-      else if (ts.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 64, 4, 1, false, 1>), grid, block, 0, s, k);
-      else hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 32, 4, 1, false, 1>), grid, block, 0, s, k);
-      SFK_CHECK_LAUNCH();
-      return SFK_OK;
+        if (ts.bn == 128) return run_reg<T, 128, 128, 2, 2, false, 5>(k, grid, s, dry);
+        if (ts.bn == 64) return run_reg<T, 256, 64, 4, 1, false, 5>(k, grid, s, dry);
+        return run_reg<T, 256, 32, 4, 1, false, 5>(k, grid, s, dry);
+      }
+      if (k.bn_mask) {              // with a mask source
+        if (ts.bn == 128) return run_reg<T, 128, 128, 2, 2, false, 7>(k, grid, s, dry);
+        if (ts.bn == 64) return run_reg<T, 256, 64, 4, 1, false, 7>(k, grid, s, dry);
+        return run_reg<T, 256, 32, 4, 1, false, 7>(k, grid, s, dry);
+      }
+      if (k.accumulate) {           // with the old values of a += pass
+        if (ts.bn == 128) return run_reg<T, 128, 128, 2, 2, false, 6>(k, grid, s, dry);
+        if (ts.bn == 64) return run_reg<T, 256, 64, 4, 1, false, 6>(k, grid, s, dry);
+        return run_reg<T, 256, 32, 4, 1, false, 6>(k, grid, s, dry);
+      }
+      if (ts.bn == 128) return run_reg<T, 128, 128, 2, 2, false, 1>(k, grid, s, dry);
+      if (ts.bn == 64) return run_reg<T, 256, 64, 4, 1, false, 1>(k, grid, s, dry);
+      return run_reg<T, 256, 32, 4, 1, false, 1>(k, grid, s, dry);
     }
     return SFK_ERR_UNSUPPORTED;
   }
   if (k.ep_on) {             // fused output transform (look-ahead K loop for every K)
-    if (ts.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<T, 128, 128, 2, 2, false, 3>), grid, block, 0, s, k);
-    else if (ts.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 64, 4, 1, false, 3>), grid, block, 0, s, k);
-    else if (ts.bn == 32) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 32, 4, 1, false, 3>), grid, block, 0, s, k);
-    else hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 16, 4, 1, false, 3>), grid, block, 0, s, k);
-    SFK_CHECK_LAUNCH();
-    return SFK_OK;
+    if (ts.bn == 128) return run_reg<T, 128, 128, 2, 2, false, 3>(k, grid, s, dry);
+    if (ts.bn == 64) return run_reg<T, 256, 64, 4, 1, false, 3>(k, grid, s, dry);
+    if (ts.bn == 32) return run_reg<T, 256, 32, 4, 1, false, 3>(k, grid, s, dry);
+    return run_reg<T, 256, 16, 4, 1, false, 3>(k, grid, s, dry);
   }
   if (k.obits) {             // output ReLU bitmap: the look-ahead K loop also for short K (few launches, one instantiation less)
-    if (ts.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<T, 128, 128, 2, 2, false, 2>), grid, block, 0, s, k);
-    else if (ts.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 64, 4, 1, false, 2>), grid, block, 0, s, k);
-    else if (ts.bn == 32) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 32, 4, 1, false, 2>), grid, block, 0, s, k);
-    else if (sizeof(T) == 4) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 16, 4, 1, false, 2>), grid, block, 0, s, k);
-    else return SFK_ERR_UNSUPPORTED;
-    SFK_CHECK_LAUNCH();
-    return SFK_OK;
+    if (ts.bn == 128) return run_reg<T, 128, 128, 2, 2, false, 2>(k, grid, s, dry);
+    if (ts.bn == 64) return run_reg<T, 256, 64, 4, 1, false, 2>(k, grid, s, dry);
+    if (ts.bn == 32) return run_reg<T, 256, 32, 4, 1, false, 2>(k, grid, s, dry);
+    if constexpr (sizeof(T) == 4) return run_reg<T, 256, 16, 4, 1, false, 2>(k, grid, s, dry);
+    return SFK_ERR_UNSUPPORTED;
   }
   if (k.KC <= k.kshort && ts.bn <= 32) {   // (the wider tiles spill with the exact-count loop: 124..228 B per lane)
-    if (ts.bn == 32) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 32, 4, 1, true>), grid, block, 0, s, k);
-    else hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 16, 4, 1, true>), grid, block, 0, s, k);
-  } else {
-    if (ts.bn == 128) hipLaunchKernelGGL((conv_igemm_kernel<T, 128, 128, 2, 2, false>), grid, block, 0, s, k);
-    else if (ts.bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 64, 4, 1, false>), grid, block, 0, s, k);
-    else if (ts.bn == 32) hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 32, 4, 1, false>), grid, block, 0, s, k);
-    else hipLaunchKernelGGL((conv_igemm_kernel<T, 256, 16, 4, 1, false>), grid, block, 0, s, k);
+    if (ts.bn == 32) return run_reg<T, 256, 32, 4, 1, true>(k, grid, s, dry);
+    return run_reg<T, 256, 16, 4, 1, true>(k, grid, s, dry);
   }
-  SFK_CHECK_LAUNCH();
-  return SFK_OK;
+  if (ts.bn == 128) return run_reg<T, 128, 128, 2, 2, false>(k, grid, s, dry);
+  if (ts.bn == 64) return run_reg<T, 256, 64, 4, 1, false>(k, grid, s, dry);
+  if (ts.bn == 32) return run_reg<T, 256, 32, 4, 1, false>(k, grid, s, dry);
+  return run_reg<T, 256, 16, 4, 1, false>(k, grid, s, dry);
+}
+
+// the route of a validated descriptor: the launch code run dry
+int route_of(const sfk_conv_desc* d) {
+  int route = -1;
+  const int r = d->x.dtype == SFK_BF16 ? launch<bf16_t>(d, nullptr, &route) : launch<float>(d, nullptr, &route);
+  return r != SFK_OK ? r : route;
 }
 
 }  // namespace
@@ -804,20 +815,17 @@ extern "C" int sfk_conv_relu_out_supported(const sfk_conv_desc* d) {
   return relu_out_ok(d) ? 1 : 0;
 }
 
+extern "C" int sfk_conv_igemm_route(const sfk_conv_desc* d) {
+  const int st = validate(d);
+  return st != SFK_OK ? st : route_of(d);
+}
+
 extern "C" int sfk_conv_igemm_family(const sfk_conv_desc* d) {
   if (validate(d) != SFK_OK) return -1;
-  if (d->x.dtype == SFK_BF16) {
-    if (ep_on(d) && (d->ep.res.ptr || d->ep.relu) && !d->accumulate && sfk_tune().igemm_pw_stream && d->ntaps == 1 &&
-        d->taps[0].dt == 0 && d->taps[0].dh == 0 && d->taps[0].dw == 0 && d->gs[0] == 1 && d->gs[1] == 1 && d->gs[2] == 1 &&
-        lin_out_of(d) && d->x.t == d->y.t && d->x.h == d->y.h && d->x.w == d->y.w && d->cin <= 128 &&
-        ((d->cout == 32 || d->cout == 64 || d->cout == 128) ? d->cin <= 32 : (d->cout == 256 ? (d->cin > 32 && d->cin <= 64) : (d->cout == 512 && d->cin > 96))))
-      return 3;
-    if (pw_dgrad_rows(d) > 0) return 3;
-    if (pw_plain_route(d)) return 3;
-  }
-  if (halo_ok(d)) return 5;
-  const TileSel ts = pick_tile(d);
-  return ts.p8 ? 4 : (ts.dma ? 1 : 0);
+  const int r = route_of(d);
+  if (r < 0) return -1;
+  const int kern = SFK_IGEMM_ROUTE_KERNEL(r);
+  return (kern == SFK_IK_PWP || kern == SFK_IK_PWF || kern == SFK_IK_PWD) ? 3 : kern;
 }
 
 extern "C" int sfk_conv_epilogue_supported(const sfk_conv_desc* d) {

@@ -46,6 +46,15 @@ struct ConvK {
   sfk_tap taps[SFK_MAX_TAPS];
 };
 
+// co fragments (16 output channels each) a wave of a BN-channel tile cut over WN wave columns owns
+constexpr int co_frags(int bn, int wn) { return bn / wn / 16; }
+// ONE statement of "the plain epilogue pairs two co fragments into 16-byte (8 x bf16) stores": the epilogue takes the path
+// by it and the route of the launch (include/sfk.h, the `wide` bit) reports it
+template <typename T, int FN>
+__host__ __device__ __forceinline__ bool wide_store_taken(const ConvK& k) {
+  return sizeof(T) == 2 && (FN % 2) == 0 && k.wide_store;
+}
+
 constexpr int BK = 32;
 
 template <typename T> struct Tile;
@@ -618,7 +627,7 @@ __device__ __forceinline__ void epilogue_plain(const ConvK& k, const f32x4 (&acc
   const int l15 = lane & 15, g = lane >> 4;
   T* __restrict__ yp = static_cast<T*>(k.y);
   const int co_w = nt * BN + wn * (BN / WN);
-  const bool wide = sizeof(T) == 2 && (FN % 2) == 0 && k.wide_store;
+  const bool wide = wide_store_taken<T, FN>(k);
   int64_t poffs[FM];
 #pragma unroll
   for (int j = 0; j < FM; ++j) {

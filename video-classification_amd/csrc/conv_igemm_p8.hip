@@ -48,11 +48,13 @@ namespace sfk_igemm {
 
 typedef __attribute__((address_space(3))) void lds_void_p8_t;
 
+constexpr int P8_FN = 4;   // co fragments per wave (the kernel's tile, and the route's store-width report)
+
 template <int BMS, int EPI>
 __global__ __launch_bounds__(512, 2) void conv_igemm_p8_kernel(const ConvK k) {
   using T = bf16_t;
   constexpr int FM = BMS / 32;            // pixel fragments per wave: 8 (256 rows) or 7 (224 rows computed, 256 staged)
-  constexpr int FN = 4;                   // co fragments per wave
+  constexpr int FN = P8_FN;               // co fragments per wave
   constexpr int FX1 = FM - 4;             // fragments of the second pixel half
   constexpr int PAR = 65536, XH = 16384, WB = 32768, ROWB = 128;
   static_assert(BMS == 256 || BMS == 224, "computed rows");
@@ -262,7 +264,12 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_p8_kernel(const ConvK k) {
   epilogue_plain<T, EPI, FM, FN, BMS, 256, 2, 4, false>(k, acc, reinterpret_cast<float*>(smem), mt, nt, g, wc, lane, tid);
 }
 
-__attribute__((visibility("hidden"))) int launch_p8(const ConvK& k, int bms, dim3 grid, hipStream_t s) {
+__attribute__((visibility("hidden"))) int launch_p8(const ConvK& k, int bms, dim3 grid, hipStream_t s, int* dry) {
+  if (dry) {       // the route (include/sfk.h) instead of the launch
+    const int wide = wide_store_taken<bf16_t, P8_FN>(k) ? 1 : 0;
+    *dry = SFK_IGEMM_ROUTE(SFK_IK_P8, 1, bms == 224 ? 224 : 256, 256, k.obits ? 2 : 0, 0, wide);
+    return SFK_OK;
+  }
   if (k.obits) {
     if (bms == 224) hipLaunchKernelGGL((conv_igemm_p8_kernel<224, 2>), grid, dim3(512), 0, s, k);
     else hipLaunchKernelGGL((conv_igemm_p8_kernel<256, 2>), grid, dim3(512), 0, s, k);

@@ -258,7 +258,11 @@ inline int pw_blocks(int M, int CG, int NT) {
 }
 
 template <int NF, int KS, int CG, int NT, bool XDB, int MODE = 0>
-int pw_launch(const PwK& k, hipStream_t s) {
+int pw_launch(const PwK& k, hipStream_t s, int* dry, int kernel) {
+  if (dry) {       // the route (include/sfk.h) instead of the launch
+    *dry = SFK_IGEMM_ROUTE(kernel, 1, 32 * KS, NF * 16 * CG, MODE, 0, 1);
+    return SFK_OK;
+  }
   const size_t lds = (size_t)KS * k.cout * 64 + (size_t)3 * k.cout * 4;
   static bool attr_set = false;             // > 64 KB of dynamic LDS needs the opt-in (idempotent, set once per process)
   if (lds > 64 * 1024 && !attr_set) {
@@ -357,7 +361,7 @@ inline bool pw_dual_map_ok(const sfk_fmap* f) {
 // Called by sfk_conv_igemm's dispatch (conv_igemm.hip) for descriptors it has validated: bf16, one tap at the pixel itself,
 // stride 1, rows = the pixels of y in order, fused output transform with a shortcut or ReLU.  Returns SFK_ERR_UNSUPPORTED
 // for shapes this kernel is not built for (the caller then runs the implicit-GEMM kernel).
-int sfk_conv_pw_fused(const sfk_conv_desc* d, hipStream_t s) {
+int sfk_conv_pw_fused(const sfk_conv_desc* d, hipStream_t s, int* dry, int kernel) {
   const sfk_conv_epilogue& e = d->ep;
   const int K = d->cin, C = d->cout;
   if (K > 128 || (K % 8) != 0) return SFK_ERR_UNSUPPORTED;
@@ -379,19 +383,19 @@ int sfk_conv_pw_fused(const sfk_conv_desc* d, hipStream_t s) {
     k.res = d->y.ptr; k.rld = d->y.ld; k.roff = d->y.c_off; k.rbytes = k.ybytes;
   }
   // plain / += / + bias passes of the block tail's backward with K = C (64.6 -> 45.4 us on slow res2: 6.8 TB/s)
-  if (C == 64 && KS == 2) return pw_launch<4, 2, 1, 256, true>(k, s);
-  if (C == 128 && KS == 4) return pw_launch<8, 4, 1, 256, true>(k, s);
-  if (C == 32 && KS == 1) return pw_launch<2, 1, 1, 256, true>(k, s);
-  if (C == 64 && KS == 1) return pw_launch<4, 1, 1, 256, true>(k, s);
-  if (C == 128 && KS == 1) return pw_launch<8, 1, 1, 256, true>(k, s);
+  if (C == 64 && KS == 2) return pw_launch<4, 2, 1, 256, true>(k, s, dry, kernel);
+  if (C == 128 && KS == 4) return pw_launch<8, 4, 1, 256, true>(k, s, dry, kernel);
+  if (C == 32 && KS == 1) return pw_launch<2, 1, 1, 256, true>(k, s, dry, kernel);
+  if (C == 64 && KS == 1) return pw_launch<4, 1, 1, 256, true>(k, s, dry, kernel);
+  if (C == 128 && KS == 1) return pw_launch<8, 1, 1, 256, true>(k, s, dry, kernel);
   // 128 channels per wave (16 fragments spill at 256 VGPRs): wider outputs are split over co groups of waves, each of
   // which reads the (small) X rows again -- from L1 / L2
-  if (C == 256 && KS == 2) return sfk_tune().igemm_pw_stream == 2 ? pw_launch<4, 2, 4, 256, true>(k, s) : pw_launch<8, 2, 2, 256, true>(k, s);
+  if (C == 256 && KS == 2) return sfk_tune().igemm_pw_stream == 2 ? pw_launch<4, 2, 4, 256, true>(k, s, dry, kernel) : pw_launch<8, 2, 2, 256, true>(k, s, dry, kernel);
   // 134 KB of filter: one 8-wave workgroup per CU; 64 channels per wave (8 fragments at KS = 4 spill), the eight co groups
   // of a workgroup read the same X rows (L1)
-  if (C == 512 && KS == 4) return pw_launch<4, 4, 8, 512, true>(k, s);
+  if (C == 512 && KS == 4) return pw_launch<4, 4, 8, 512, true>(k, s, dry, kernel);
   // 320 = 5 co groups of 64 channels (84 KB of filter: one 8-wave workgroup per CU)
-  if (C == 320 && KS == 4 && !k.res) return pw_launch<4, 4, 5, 512, true>(k, s);
+  if (C == 320 && KS == 4 && !k.res) return pw_launch<4, 4, 5, 512, true>(k, s, dry, kernel);
   return SFK_ERR_UNSUPPORTED;
 }
 
@@ -405,7 +409,7 @@ int sfk_conv_pw_dgrad_rows(const sfk_conv_desc* d) {
   return 0;
 }
 
-int sfk_conv_pw_dgrad(const sfk_conv_desc* d, hipStream_t s) {
+int sfk_conv_pw_dgrad(const sfk_conv_desc* d, hipStream_t s, int* dry) {
   PwK k;
   k.x = d->x.ptr; k.y = d->y.ptr; k.w = d->w; k.res = d->y.ptr;          // in place: old rows + result
   k.scale = k.shift = k.rscale = k.rshift = nullptr;
@@ -413,8 +417,8 @@ int sfk_conv_pw_dgrad(const sfk_conv_desc* d, hipStream_t s) {
   k.xld = d->x.ld; k.xoff = d->x.c_off; k.yld = d->y.ld; k.yoff = d->y.c_off; k.rld = d->y.ld; k.roff = d->y.c_off;
   k.M = (int)sfk_fmap_pixels(&d->y); k.K = d->cin; k.cout = d->cout; k.relu = 0;
   k.xbytes = (uint32_t)sfk_fmap_bytes(&d->x); k.ybytes = (uint32_t)sfk_fmap_bytes(&d->y); k.rbytes = k.ybytes;
-  if (d->cin == 64 && d->cout == 256) return pw_launch<8, 2, 2, 256, true, 1>(k, s);
-  if (d->cin == 128 && d->cout == 512) return pw_launch<4, 4, 8, 512, true, 1>(k, s);
+  if (d->cin == 64 && d->cout == 256) return pw_launch<8, 2, 2, 256, true, 1>(k, s, dry, SFK_IK_PWD);
+  if (d->cin == 128 && d->cout == 512) return pw_launch<4, 4, 8, 512, true, 1>(k, s, dry, SFK_IK_PWD);
   return SFK_ERR_UNSUPPORTED;
 }
 

@@ -15,11 +15,11 @@
 using namespace sfk_wgrad;
 
 namespace sfk_wgrad {
-// conv_wgrad_p8.hip: the deep-pipelined 256 x 256 tile of the MFMA-bound layers (dry != NULL: workspace bytes only)
-__attribute__((visibility("hidden"))) int launch_wgrad_p8(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry);
+// conv_wgrad_p8.hip: the deep-pipelined 256 x 256 tile of the MFMA-bound layers (dry != NULL: workspace bytes or the route, nothing is launched)
+__attribute__((visibility("hidden"))) int launch_wgrad_p8(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, WgradDry* dry);
 __attribute__((visibility("hidden"))) bool wgrad_p8_ok(const sfk_wgrad_desc* d, int M);
 // conv_wgrad_band.hip: the LDS-band kernel of the (1,3,3) 64 -> 64 layer over 56 x 56 frames; workspace only
-__attribute__((visibility("hidden"))) int launch_wgrad_band(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry);
+__attribute__((visibility("hidden"))) int launch_wgrad_band(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, WgradDry* dry);
 __attribute__((visibility("hidden"))) bool wgrad_band_ok(const sfk_wgrad_desc* d);
 }
 
@@ -546,7 +546,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 4 : 3)) void conv_wgrad_dma_ker
 }
 
 template <int TCO, int NW, bool DG = false, int TCI = 128, int NS = 3>
-int launch_dma(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry) {
+int launch_dma(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, WgradDry* dry) {
   const int cols = d->ntaps * d->cin;
   const int cotiles = (d->cout + TCO - 1) / TCO;
   constexpr int FI = TCI / (NW / (TCO / 64)) / 16;
@@ -565,8 +565,9 @@ int launch_dma(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry) 
   splits = (k.nchunks + k.chunks_per_split - 1) / k.chunks_per_split;
   k.ntiles = base;
   const int64_t need = (int64_t)splits * base * NW * (4 * FI) * 64 * 16;
-  if (dry) { *dry = need; return SFK_OK; }
+  if (dry && dry->sizing()) { dry->bytes = need; return SFK_OK; }
   if (k.ws && need > d->workspace_bytes) k.ws = nullptr;
+  if (dry) { dry->report(SFK_WK_DMA, true, TCO, TCI, NW, false, DG, splits, k.ws != nullptr); return SFK_OK; }
   hipLaunchKernelGGL((conv_wgrad_dma_kernel<TCO, NW, DG, TCI, NS>), dim3((unsigned)(base * splits)), dim3(64 * NW), 0, s, k);
   SFK_CHECK_LAUNCH();
   if (k.ws) return launch_reduce<NW, TCO / 64, 4, FI>(k, splits, s);
@@ -603,7 +604,7 @@ int validate(const sfk_wgrad_desc* d) {
 }
 
 template <typename T, int TCO, int TCI, int KS, bool GRAM = false>
-int launch_cfg(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry) {
+int launch_cfg(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, WgradDry* dry) {
   const int cols = d->ntaps * d->cin;
   const int cotiles = (d->cout + TCO - 1) / TCO;
   k.citiles = (cols + TCI - 1) / TCI;
@@ -621,8 +622,12 @@ int launch_cfg(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry) 
   splits = (k.nchunks + k.chunks_per_split - 1) / k.chunks_per_split;
   k.ntiles = base;
   constexpr int FO = TCO / 32, FI = TCI / 32;
-  if (dry) { *dry = (int64_t)splits * base * 4 * FO * FI * 64 * 16; return SFK_OK; }
+  if (dry && dry->sizing()) { dry->bytes = (int64_t)splits * base * 4 * FO * FI * 64 * 16; return SFK_OK; }
   if (k.ws && (int64_t)splits * base * 4 * FO * FI * 64 * 16 > d->workspace_bytes) k.ws = nullptr;
+  if (dry) {
+    dry->report(SFK_WK_CFG, sizeof(T) == 2, TCO, TCI, KS, GRAM, false, splits, k.ws != nullptr);
+    return SFK_OK;
+  }
   hipLaunchKernelGGL((conv_wgrad_kernel<T, TCO, TCI, KS, GRAM>), dim3((unsigned)(base * splits)), dim3(256), 0, s, k);
   SFK_CHECK_LAUNCH();
   if (k.ws) return launch_reduce<4, 2, FO, FI>(k, splits, s);
@@ -630,7 +635,7 @@ int launch_cfg(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry) 
 }
 
 template <typename T>
-int launch(const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry = nullptr) {
+int launch(const sfk_wgrad_desc* d, hipStream_t s, WgradDry* dry = nullptr) {
   WgradK k;
   k.x = d->x.ptr; k.dy = d->dy.ptr; k.dw = d->dw;
   k.xt = d->x.t; k.xh = d->x.h; k.xw = d->x.w; k.xld = d->x.ld; k.xoff = d->x.c_off;
@@ -649,11 +654,11 @@ int launch(const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry = nullptr) {
   k.dgw = nullptr; k.dgy = nullptr; k.dgld = 0; k.dgoff = 0;
   const int cols = d->ntaps * d->cin;
   if constexpr (sizeof(T) == 2) {
-    if ((dry || k.ws) && wgrad_p8_ok(d, k.M)) {      // the deep-pipelined 256 x 256 tile (conv_wgrad_p8.hip); workspace only
+    if (((dry && dry->sizing()) || k.ws) && wgrad_p8_ok(d, k.M)) {      // the deep-pipelined 256 x 256 tile (conv_wgrad_p8.hip); workspace only
       const int r = launch_wgrad_p8(k, d, s, dry);
       if (r != SFK_ERR_UNSUPPORTED) return r;
     }
-    if ((dry || k.ws) && wgrad_band_ok(d)) {
+    if (((dry && dry->sizing()) || k.ws) && wgrad_band_ok(d)) {
       const int r = launch_wgrad_band(k, d, s, dry);
       if (r != SFK_ERR_UNSUPPORTED) return r;
     }
@@ -699,9 +704,19 @@ int launch(const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry = nullptr) {
 extern "C" int64_t sfk_conv_wgrad_workspace_bytes(const sfk_wgrad_desc* d) {
   const int st = validate(d);
   if (st != SFK_OK) return st;
-  int64_t bytes = 0;
-  const int r = d->x.dtype == SFK_BF16 ? launch<bf16_t>(d, nullptr, &bytes) : launch<float>(d, nullptr, &bytes);
-  return r != SFK_OK ? r : bytes;
+  WgradDry dry;
+  const int r = d->x.dtype == SFK_BF16 ? launch<bf16_t>(d, nullptr, &dry) : launch<float>(d, nullptr, &dry);
+  return r != SFK_OK ? r : dry.bytes;
+}
+
+extern "C" int64_t sfk_conv_wgrad_route(const sfk_wgrad_desc* d) {
+  const int st = validate(d);
+  if (st != SFK_OK) return st;
+  int64_t route = -1;
+  WgradDry dry;
+  dry.route = &route;
+  const int r = d->x.dtype == SFK_BF16 ? launch<bf16_t>(d, nullptr, &dry) : launch<float>(d, nullptr, &dry);
+  return r != SFK_OK ? r : route;
 }
 
 extern "C" int sfk_conv_wgrad_wants_workspace(const sfk_wgrad_desc* d) {

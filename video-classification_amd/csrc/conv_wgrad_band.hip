@@ -434,15 +434,16 @@ __attribute__((visibility("hidden"))) bool wgrad_band_ok(const sfk_wgrad_desc* d
 }
 
 template <class Cfg>
-static int launch_band_cfg(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry) {
+static int launch_band_cfg(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, WgradDry* dry) {
   BandK bk;
   bk.bpf = d->x.h / 4;
   bk.nunits = d->x.n * d->x.t * bk.bpf * Cfg::NHALF;
   for (int i = 0; i < 9; ++i) bk.tpos[(d->taps[i].dh + 1) * 3 + d->taps[i].dw + 1] = i;
   const int grid = (bk.nunits < 256 ? bk.nunits : 256) / Cfg::NHALF * Cfg::NHALF;     // (a workgroup keeps its channel half)
   const int64_t need = (int64_t)grid * Cfg::NFRAG * 64 * 16;
-  if (dry) { *dry = need; return SFK_OK; }
+  if (dry && dry->sizing()) { dry->bytes = need; return SFK_OK; }
   if (!k.ws || need > d->workspace_bytes) return SFK_ERR_UNSUPPORTED;      // (the caller falls back to the implicit-GEMM kernels)
+  if (dry) { dry->report(SFK_WK_BAND, true, d->cout, d->cin, 8, false, false, grid / Cfg::NHALF, true); return SFK_OK; }
   hipLaunchKernelGGL((conv_wgrad_band_kernel<Cfg>), dim3((unsigned)grid), dim3(512), 0, s, k, bk);
   SFK_CHECK_LAUNCH();
   const int total = Cfg::NHALF * Cfg::NFRAG * 64, splits = grid / Cfg::NHALF;
@@ -454,7 +455,7 @@ static int launch_band_cfg(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, in
   return SFK_OK;
 }
 
-__attribute__((visibility("hidden"))) int launch_wgrad_band(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry) {
+__attribute__((visibility("hidden"))) int launch_wgrad_band(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, WgradDry* dry) {
   return d->cin == 64 ? launch_band_cfg<BandCfg<56, 64, 64>>(k, d, s, dry) : launch_band_cfg<BandCfg<28, 128, 128>>(k, d, s, dry);
 }
 

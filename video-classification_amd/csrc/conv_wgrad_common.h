@@ -31,6 +31,19 @@ struct WgradK {
 
 constexpr int MK = 32;  // pixels per K-step
 
+// The launch code run dry (no kernel is launched).  route == NULL: `bytes` = the workspace the descriptor's best route
+// would use (sfk_conv_wgrad_workspace_bytes: every route is offered, whatever workspace the descriptor has).  route != NULL:
+// the route THIS descriptor takes with the workspace it carries (sfk_conv_wgrad_route, include/sfk.h).
+struct WgradDry {
+  int64_t bytes = 0;
+  int64_t* route = nullptr;
+  bool sizing() const { return route == nullptr; }
+  void report(int kernel, bool bf16, int tco, int tci, int ksnw, bool gram, bool dg, int splits, bool ws) {
+    *route = (int64_t)SFK_WGRAD_ROUTE(kernel, bf16 ? 1 : 0, tco, tci, ksnw, gram ? 1 : 0, dg ? 1 : 0) | ((int64_t)(ws ? 1 : 0) << 29) |
+             ((int64_t)splits << 32);
+  }
+};
+
 // XCD-aware block order (as conv_igemm): blocks b, b+8, ... share an L2, so consecutive LOGICAL ids go to one XCD and the
 // tiles of one pixel split (which read the same dY rows and overlapping X rows) are neighbours there.
 __device__ __forceinline__ void wg_block(int ntiles, int& tile, int& split) {

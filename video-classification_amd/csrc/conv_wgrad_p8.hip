@@ -240,7 +240,7 @@ __attribute__((visibility("hidden"))) bool wgrad_p8_ok(const sfk_wgrad_desc* d, 
   return nkt / splits >= sfk_tune().wgrad_p8;            // (the knob is the minimum K-tile count per workgroup)
 }
 
-__attribute__((visibility("hidden"))) int launch_wgrad_p8(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, int64_t* dry) {
+__attribute__((visibility("hidden"))) int launch_wgrad_p8(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, WgradDry* dry) {
   const int cols = d->ntaps * d->cin;
   k.citiles = (cols + 255) / 256;
   k.ntiles = ((d->cout + 255) / 256) * k.citiles;
@@ -250,8 +250,9 @@ __attribute__((visibility("hidden"))) int launch_wgrad_p8(WgradK& k, const sfk_w
   k.chunks_per_split = (k.nchunks + splits - 1) / splits;
   splits = (k.nchunks + k.chunks_per_split - 1) / k.chunks_per_split;
   const int64_t need = (int64_t)splits * k.ntiles * 8 * 32 * 64 * 16;
-  if (dry) { *dry = need; return SFK_OK; }
+  if (dry && dry->sizing()) { dry->bytes = need; return SFK_OK; }
   if (!k.ws || need > d->workspace_bytes) return SFK_ERR_UNSUPPORTED;      // (the caller falls back to the ring kernels)
+  if (dry) { dry->report(SFK_WK_P8, true, 256, 256, 8, false, false, splits, true); return SFK_OK; }
   hipLaunchKernelGGL(conv_wgrad_p8_kernel, dim3((unsigned)(k.ntiles * splits)), dim3(512), 0, s, k);
   SFK_CHECK_LAUNCH();
   return launch_reduce<8, 2, 8, 4>(k, splits, s);
