@@ -41,8 +41,9 @@ extern "C" {
  * of `a` from it (no constant-1 channel group beside the activation any more); 13 = sfk_conv_pw_dual; 14 = sfk_tuning.igemm_p8 / wgrad_p8,
  * sfk_conv_igemm_family value 4; 15 = sfk_tuning.igemm_halo, family value 5; 16 = sfk_tuning.wgrad_band; 17 = sfk_tuning.stem_v3; 18 = sfk_bn_finalize_apply (19, 20: SFK_BN_SYNC_INTS counters),
  * sfk_bn_bwd_finalize_apply; 21 = the two fused finalize launches, SFK_BN_SYNC_INTS and sfk_tuning.wgrad_target_256 /
- * wgrad_min_stages_256 removed, stem_v3 bit 2 retired; 22 = sfk_conv_igemm_route / sfk_conv_wgrad_route and the route enums. */
-#define SFK_ABI_VERSION 22
+ * wgrad_min_stages_256 removed, stem_v3 bit 2 retired; 22 = sfk_conv_igemm_route / sfk_conv_wgrad_route and the route enums;
+ * 23 = sfk_stem_conv_fwd_route / sfk_stem_conv_wgrad_route and sfk_stem_route. */
+#define SFK_ABI_VERSION 23
 #define SFK_MAX_TAPS 16
 #define SFK_BN_FOLD_ROWS 64 /* rows of the optional BatchNorm fold workspace */
 
@@ -296,6 +297,40 @@ int sfk_stem_kp(int32_t cin, int32_t kt);
 int sfk_stem_conv_tiles(const sfk_stem_src* s, const sfk_fmap* y);
 int sfk_stem_conv_fwd(const sfk_stem_src* s, const void* w, const sfk_fmap* y, float* stats, sfk_stream_t stream);
 int sfk_stem_conv_wgrad(const sfk_stem_src* s, const sfk_fmap* dy, float* dw, sfk_stream_t stream);
+
+/* Routes of the two stem entry points (host-only queries for tests and reports, as sfk_conv_igemm_route): WHICH kernel
+ * instantiation the call runs for (source, map), answered by the launch code itself run without launching.  Neither needs
+ * the filter / dw pointer; the source and map pointers are read for their alignment only.
+ *   SFK_STEM_ROUTE(kernel, map_bf16, src_bf16, n):  kernel sfk_stem_kernel;  map_bf16 / src_bf16 = 1 for SFK_BF16;  n = the
+ *   kernel's own template argument: KT of the pair kernels (V4, V2), 1 for S4 (kt 1), FN = 16-channel fragments per tile
+ *   (1, 2, 4) of the generic kernels, 0 for WGV2 (kt is a runtime argument there).
+ * The answer carries the route in its low 16 bits, then
+ *   SFK_STEM_ROUTE_GRID(r)  = workgroups launched (forward) / blocks = pixel splits of a plane (WG_GENERIC: the grid is
+ *                             planes x splits) or workgroups incl. the surplus ones of the 8-aligned grid (WGV2), and
+ *   SFK_STEM_ROUTE_UNITS(r) = the work items they share: (clip, half tile, pair chunk) units of V4 / S4, (clip, tile, pair
+ *                             chunk) units of V2, 16 x 16 tiles of the generic kernels and of WGV2 (saturates at 2^27 - 1).
+ * SFK_STEM_ROUTES lists every route reachable with the default tuning table (stem_v3 == 3) and a source below 2 GiB. */
+typedef enum { SFK_SK_V4 = 0, SFK_SK_V2 = 1, SFK_SK_S4 = 2, SFK_SK_GENERIC = 3, SFK_SK_WGV2 = 4, SFK_SK_WG_GENERIC = 5 } sfk_stem_kernel;
+/* V4 half-tile pair kernel of the fast stem, V2 its whole-tile predecessor (one frame, or stem_v3 bit 0 off), S4 the
+ * register-filter kernel of the slow stem, GENERIC any cin / kt / source; WGV2 the input-frame-stationary filter gradient of
+ * the fast stem, WG_GENERIC the plane x split one. */
+#define SFK_STEM_ROUTE(kernel, map_bf16, src_bf16, n) (((kernel) << 8) | ((map_bf16) << 5) | ((src_bf16) << 4) | (n))
+#define SFK_STEM_ROUTE_ID(r) ((int)((r) & 0xFFFF))
+#define SFK_STEM_ROUTE_GRID(r) ((int)(((r) >> 16) & 0xFFFFF))
+#define SFK_STEM_ROUTE_UNITS(r) ((int)(((r) >> 36) & 0x7FFFFFF))
+/* X(kernel, map_bf16, src_bf16, n) */
+#define SFK_STEM_ROUTES(X) \
+  X(V4, 1, 1, 5) X(V4, 1, 1, 3) X(V2, 1, 1, 5) X(V2, 1, 1, 3) X(S4, 1, 1, 1) \
+  X(GENERIC, 1, 1, 1) X(GENERIC, 1, 1, 2) X(GENERIC, 1, 1, 4) X(GENERIC, 1, 0, 1) X(GENERIC, 1, 0, 2) X(GENERIC, 1, 0, 4) \
+  X(GENERIC, 0, 1, 1) X(GENERIC, 0, 1, 2) X(GENERIC, 0, 1, 4) X(GENERIC, 0, 0, 1) X(GENERIC, 0, 0, 2) X(GENERIC, 0, 0, 4) \
+  X(WGV2, 1, 1, 0) \
+  X(WG_GENERIC, 1, 1, 1) X(WG_GENERIC, 1, 1, 2) X(WG_GENERIC, 1, 1, 4) X(WG_GENERIC, 1, 0, 1) X(WG_GENERIC, 1, 0, 2) \
+  X(WG_GENERIC, 1, 0, 4) X(WG_GENERIC, 0, 1, 1) X(WG_GENERIC, 0, 1, 2) X(WG_GENERIC, 0, 1, 4) X(WG_GENERIC, 0, 0, 1) \
+  X(WG_GENERIC, 0, 0, 2) X(WG_GENERIC, 0, 0, 4)
+#define SFK_SR_ENUM_(k, m, s, n) SFK_SR_##k##_M##m##_S##s##_N##n = SFK_STEM_ROUTE(SFK_SK_##k, m, s, n),
+typedef enum { SFK_STEM_ROUTES(SFK_SR_ENUM_) SFK_SR_NONE_ = -1 } sfk_stem_route;
+int64_t sfk_stem_conv_fwd_route(const sfk_stem_src* s, const sfk_fmap* y);     /* sfk_stem_route + GRID + UNITS; < 0: sfk_status */
+int64_t sfk_stem_conv_wgrad_route(const sfk_stem_src* s, const sfk_fmap* dy);  /* likewise (GRID = blocks, UNITS = items) */
 
 /* ---------------------------------------------------------------------------------------------------------
  * BatchNorm3d (eps, momentum; affine; running stats) -- nn.BatchNorm3d after every conv

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFK_LIB") or os.path.join(HERE, "libsfk.so")   # SFK_LIB: experiment builds (tools/gpu_ab_lib.sh)
 SFK_F32, SFK_BF16 = 0, 1
 SFK_MAX_TAPS = 16
-ABI_VERSION = 22       # include/sfk.h SFK_ABI_VERSION
+ABI_VERSION = 23       # include/sfk.h SFK_ABI_VERSION
 BN_FOLD_ROWS = 64      # include/sfk.h SFK_BN_FOLD_ROWS
 _DT = {torch.float32: SFK_F32, torch.bfloat16: SFK_BF16}
 
@@ -379,6 +379,8 @@ SIGNATURES = {
     "sfk_stem_conv_tiles": [C.POINTER(_StemSrc), _P_FMAP],
     "sfk_stem_conv_fwd": [C.POINTER(_StemSrc), _PV, _P_FMAP, _PF, _PV],
     "sfk_stem_conv_wgrad": [C.POINTER(_StemSrc), _P_FMAP, _PF, _PV],
+    "sfk_stem_conv_fwd_route": [C.POINTER(_StemSrc), _P_FMAP],
+    "sfk_stem_conv_wgrad_route": [C.POINTER(_StemSrc), _P_FMAP],
     "sfk_bn_finalize": [_PF, _I32, _I32, _I64, _PF, _PF, _F, _F, _PF, _PF, _PV, _PF, _PF, _PF, _PF, _PF, _PV],
     "sfk_bn_eval_coeffs": [_PF, _PF, _PF, _PF, _F, _I32, _PF, _PF, _PV],
     "sfk_bn_stats": [_P_FMAP, _PF, _I32, C.POINTER(C.c_int32), _PV],
@@ -551,7 +553,7 @@ SIGNATURES_WARP = {
     "sfk_u8_pool_gather_warp": [C.POINTER(_PoolWarpDesc), _PV],
     "sfk_warp_fallback_tiles": [_I32, _I32, _I32, _I32, _PF],
 }
-_RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_route": C.c_int64, "sfk_groups_prepare": C.c_int64, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
+_RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_route": C.c_int64, "sfk_stem_conv_fwd_route": C.c_int64, "sfk_stem_conv_wgrad_route": C.c_int64, "sfk_groups_prepare": C.c_int64, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
 
@@ -942,6 +944,16 @@ class HipBackend:
     def stem_conv_wgrad(self, p: StemSrc, dy: FMap, dw: torch.Tensor):
         d, fy = self._c_stem(p), _c_fmap(dy)
         return self._plain("sfk_stem_conv_wgrad", C.byref(d), C.byref(fy), _ptr(dw), keep=(d, fy, p, dy, dw))
+
+    def stem_route(self, p: StemSrc, m: FMap, wgrad: bool = False) -> Tuple[int, int, int]:
+        """(sfk_stem_route of include/sfk.h, work items, workgroups / blocks) of sfk_stem_conv_fwd(p, ., m) or, with wgrad,
+        of sfk_stem_conv_wgrad(p, m, .): the launch code run dry"""
+        name = "sfk_stem_conv_wgrad_route" if wgrad else "sfk_stem_conv_fwd_route"
+        d, fm = self._c_stem(p), _c_fmap(m)
+        r = int(getattr(self.lib, name)(C.byref(d), C.byref(fm)))
+        if r < 0:
+            _check(r, name)
+        return r & 0xFFFF, (r >> 36) & 0x7FFFFFF, (r >> 16) & 0xFFFFF
 
     # -- the frames-as-channels stem of res2d (include/sfk_stem2d.h); `src` of the StemSrc is indexed (n, c, t, h, w), kt = T
     @staticmethod

@@ -12,6 +12,8 @@
 // f32 table with a per-clip crop shift (S = U8Lut, include/sfk_u8stem.h).  The tile / patch geometry, ldsrc, plane_store, the
 // MFMA operand fragments (Frag, store4) and the host's view of a uint8 source are stem_src.h's, shared with stem2d.hip; the
 // source offsets of a tile and the loads of a plane (PatchSlots, plane_fetch) are this file's own -- see stem_src.h for why.
+#include <type_traits>
+
 #include "sfk_common.h"
 #include "stem_src.h"
 
@@ -1293,9 +1295,70 @@ int fill_src(const X* x, const int32_t* t_index, int32_t t_len, int32_t kt, cons
   return st;
 }
 
+// The launch code run dry (sfk_stem_conv_fwd_route / _wgrad_route, include/sfk.h): every launch of a stem kernel goes through
+// one of the launch_* functions below, which with `dry` write their own template arguments, the work items and the grid
+// instead of launching -- so the route queries cannot disagree with the dispatch.
+inline int64_t stem_route_pack(int kernel, int map_bf16, int src_bf16, int n, int64_t units, int64_t grid) {
+  if (units > 0x7FFFFFF) units = 0x7FFFFFF;
+  return (int64_t)SFK_STEM_ROUTE(kernel, map_bf16, src_bf16, n) | (grid << 16) | (units << 36);
+}
+template <typename S>
+constexpr int stem_src_bf16() { return std::is_same<S, bf16_t>::value ? 1 : 0; }
+
+template <typename T, typename S, int FN>
+int launch_fwd_generic(const StemK& k, dim3 grid, size_t lds, hipStream_t hs, int64_t* dry) {
+  if (dry) { *dry = stem_route_pack(SFK_SK_GENERIC, sizeof(T) == 2, stem_src_bf16<S>(), FN, k.ntiles, grid.x); return SFK_OK; }
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_kernel<T, S, FN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((stem_fwd_kernel<T, S, FN>), grid, dim3(256), lds, hs, k);
+  SFK_CHECK_LAUNCH();
+  return SFK_OK;
+}
+
+template <typename T, typename S, int FN>
+int launch_wgrad_generic(const StemK& k, dim3 grid, hipStream_t hs, int64_t* dry) {
+  if (dry) { *dry = stem_route_pack(SFK_SK_WG_GENERIC, sizeof(T) == 2, stem_src_bf16<S>(), FN, k.ntiles, grid.y); return SFK_OK; }
+  hipLaunchKernelGGL((stem_wgrad_kernel<T, S, FN>), grid, dim3(256), 0, hs, k);
+  SFK_CHECK_LAUNCH();
+  return SFK_OK;
+}
+
+template <int KT>
+int launch_fwd_v4(const StemK& k, int grid, int lds, hipStream_t hs, int ppu, int nu, int tch, int64_t* dry) {
+  if (dry) { *dry = stem_route_pack(SFK_SK_V4, 1, 1, KT, nu, grid); return SFK_OK; }
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_v4_kernel<3, KT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL((stem_fwd_v4_kernel<3, KT>), dim3((unsigned)grid), dim3(256), lds, hs, k, ppu, nu, tch);
+  SFK_CHECK_LAUNCH();
+  return SFK_OK;
+}
+
+template <int KT>
+int launch_fwd_v2(const StemK& k, int grid, int lds, hipStream_t hs, int ppu, int nunits, int64_t* dry) {
+  if (dry) { *dry = stem_route_pack(SFK_SK_V2, 1, 1, KT, nunits, grid); return SFK_OK; }
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_v2_kernel<3, KT>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL((stem_fwd_v2_kernel<3, KT>), dim3((unsigned)grid), dim3(512), lds, hs, k, ppu, nunits);
+  SFK_CHECK_LAUNCH();
+  return SFK_OK;
+}
+
+int launch_fwd_s4(const StemK& k, int grid, int lds, hipStream_t hs, int ppu, int nu, int tch, int64_t* dry) {
+  if (dry) { *dry = stem_route_pack(SFK_SK_S4, 1, 1, 1, nu, grid); return SFK_OK; }
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_s4_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  hipLaunchKernelGGL((stem_fwd_s4_kernel<3>), dim3((unsigned)grid), dim3(256), lds, hs, k, ppu, nu, tch);
+  SFK_CHECK_LAUNCH();
+  return SFK_OK;
+}
+
+int launch_wgrad_v2(const StemK& k, int blocks, hipStream_t hs, int64_t* dry) {
+  if (dry) { *dry = stem_route_pack(SFK_SK_WGV2, 1, 1, 0, k.ntiles, blocks); return SFK_OK; }
+  hipLaunchKernelGGL((stem_wgrad_v2_kernel<3>), dim3((unsigned)blocks), dim3(256), 0, hs, k);
+  SFK_CHECK_LAUNCH();
+  return SFK_OK;
+}
+
 // the generic forward (any cin / kt / source type): one 16x16 tile per block iteration, filters and patches in LDS
 template <typename S>
-int stem_fwd_generic(StemK& k, const sfk_fmap* y, hipStream_t hs) {
+int stem_fwd_generic(StemK& k, const sfk_fmap* y, hipStream_t hs, int64_t* dry = nullptr) {
   const int fn = (y->c + 15) / 16;
   const size_t esz = y->dtype == SFK_BF16 ? 2 : 4;
   const size_t lds = esz * ((size_t)16 * fn * (k.kp + 8) + (size_t)k.planes * PR * PC) + 4 * 16 * fn * 2 * sizeof(float) +
@@ -1303,32 +1366,18 @@ int stem_fwd_generic(StemK& k, const sfk_fmap* y, hipStream_t hs) {
   if (lds > 160 * 1024) return SFK_ERR_UNSUPPORTED;
   k.ntiles = y->n * y->t * k.tiles_h * k.tiles_w;
   const int resident = 256 * (int)((160 * 1024) / lds < 1 ? 1 : ((160 * 1024) / lds > 4 ? 4 : (160 * 1024) / lds));
-  const dim3 grid((unsigned)(k.ntiles < 4 * resident ? k.ntiles : 4 * resident)), blk(256);
-#define SFK_STEM_FWD(T, FN)                                                                                 \
-  do {                                                                                                      \
-    if (lds > 64 * 1024)                                                                                    \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_kernel<T, S, FN>),                      \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                            \
-    hipLaunchKernelGGL((stem_fwd_kernel<T, S, FN>), grid, blk, lds, hs, k);                                 \
-  } while (0)
-#define SFK_STEM_FWD_FN(T)                                          \
-  do {                                                              \
-    if (fn == 1) SFK_STEM_FWD(T, 1);                                \
-    else if (fn == 2) SFK_STEM_FWD(T, 2);                           \
-    else SFK_STEM_FWD(T, 4);                                        \
-  } while (0)
+  const dim3 grid((unsigned)(k.ntiles < 4 * resident ? k.ntiles : 4 * resident));
   if (fn == 3) return SFK_ERR_UNSUPPORTED;
-  if (y->dtype == SFK_BF16) SFK_STEM_FWD_FN(bf16_t);
-  else SFK_STEM_FWD_FN(float);
-#undef SFK_STEM_FWD_FN
-#undef SFK_STEM_FWD
-  SFK_CHECK_LAUNCH();
-  return SFK_OK;
+  if (y->dtype == SFK_BF16)
+    return fn == 1 ? launch_fwd_generic<bf16_t, S, 1>(k, grid, lds, hs, dry)
+           : fn == 2 ? launch_fwd_generic<bf16_t, S, 2>(k, grid, lds, hs, dry) : launch_fwd_generic<bf16_t, S, 4>(k, grid, lds, hs, dry);
+  return fn == 1 ? launch_fwd_generic<float, S, 1>(k, grid, lds, hs, dry)
+         : fn == 2 ? launch_fwd_generic<float, S, 2>(k, grid, lds, hs, dry) : launch_fwd_generic<float, S, 4>(k, grid, lds, hs, dry);
 }
 
 // the generic filter gradient: grid = (plane, tile split), split sums added to dw with fp32 atomics
 template <typename S>
-int stem_wgrad_generic(StemK& k, const sfk_fmap* dy, hipStream_t hs) {
+int stem_wgrad_generic(StemK& k, const sfk_fmap* dy, hipStream_t hs, int64_t* dry = nullptr) {
   int splits = (2048 + k.planes - 1) / k.planes;
   if (splits > k.ntiles) splits = k.ntiles;
   if (splits > 65535) splits = 65535;
@@ -1336,25 +1385,19 @@ int stem_wgrad_generic(StemK& k, const sfk_fmap* dy, hipStream_t hs) {
   splits = (k.ntiles + k.tiles_per_block - 1) / k.tiles_per_block;
   const int fn = (dy->c + 15) / 16;
   if (fn == 3) return SFK_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)k.planes, (unsigned)splits), blk(256);
-#define SFK_STEM_WG(T)                                                                      \
-  do {                                                                                      \
-    if (fn == 1) hipLaunchKernelGGL((stem_wgrad_kernel<T, S, 1>), grid, blk, 0, hs, k);     \
-    else if (fn == 2) hipLaunchKernelGGL((stem_wgrad_kernel<T, S, 2>), grid, blk, 0, hs, k); \
-    else hipLaunchKernelGGL((stem_wgrad_kernel<T, S, 4>), grid, blk, 0, hs, k);             \
-  } while (0)
-  if (dy->dtype == SFK_BF16) SFK_STEM_WG(bf16_t);
-  else SFK_STEM_WG(float);
-#undef SFK_STEM_WG
-  SFK_CHECK_LAUNCH();
-  return SFK_OK;
+  const dim3 grid((unsigned)k.planes, (unsigned)splits);
+  if (dy->dtype == SFK_BF16)
+    return fn == 1 ? launch_wgrad_generic<bf16_t, S, 1>(k, grid, hs, dry)
+           : fn == 2 ? launch_wgrad_generic<bf16_t, S, 2>(k, grid, hs, dry) : launch_wgrad_generic<bf16_t, S, 4>(k, grid, hs, dry);
+  return fn == 1 ? launch_wgrad_generic<float, S, 1>(k, grid, hs, dry)
+         : fn == 2 ? launch_wgrad_generic<float, S, 2>(k, grid, hs, dry) : launch_wgrad_generic<float, S, 4>(k, grid, hs, dry);
 }
 
 // What the forward entry points share: the argument checks in their order, and the StemK of (source, filter, map)
 template <typename X>
 int fwd_args(const X* x, const int32_t* t_index, int32_t t_len, int32_t kt, const void* w, const sfk_fmap* y, float* stats,
-             StemK& k) {
-  if (!w || !sfk_fmap_ok(y)) return SFK_ERR_INVALID;
+             StemK& k, bool dry = false) {      // dry (the route query): no filter is given, none is checked
+  if ((!w && !dry) || !sfk_fmap_ok(y)) return SFK_ERR_INVALID;
   const int st = fill_src(x, t_index, t_len, kt, y, k);
   if (st != SFK_OK) return st;
   if ((y->ld % 4) || (y->c_off % 4) || (((uintptr_t)y->ptr) & 15) || (((uintptr_t)w) & 15)) return SFK_ERR_UNSUPPORTED;
@@ -1365,8 +1408,9 @@ int fwd_args(const X* x, const int32_t* t_index, int32_t t_len, int32_t kt, cons
 
 // ... and the filter-gradient ones
 template <typename X>
-int wgrad_args(const X* x, const int32_t* t_index, int32_t t_len, int32_t kt, const sfk_fmap* dy, float* dw, StemK& k) {
-  if (!dw || !sfk_fmap_ok(dy)) return SFK_ERR_INVALID;
+int wgrad_args(const X* x, const int32_t* t_index, int32_t t_len, int32_t kt, const sfk_fmap* dy, float* dw, StemK& k,
+               bool dry = false) {                // dry (the route query): no dw is given, none is checked
+  if ((!dw && !dry) || !sfk_fmap_ok(dy)) return SFK_ERR_INVALID;
   const int st = fill_src(x, t_index, t_len, kt, dy, k);
   if (st != SFK_OK) return st;
   if (!sfk_fmap_vec_ok(dy)) return SFK_ERR_UNSUPPORTED;
@@ -1405,10 +1449,12 @@ extern "C" int sfk_stem_conv_tiles(const sfk_stem_src* s, const sfk_fmap* y) {
   return y->n * y->t * ((y->h + TS - 1) / TS) * ((y->w + TS - 1) / TS);
 }
 
-extern "C" int sfk_stem_conv_fwd(const sfk_stem_src* s, const void* w, const sfk_fmap* y, float* stats,
-                                 sfk_stream_t stream) {
+namespace {
+
+// sfk_stem_conv_fwd, and with `dry` its route (include/sfk.h)
+int stem_conv_fwd_run(const sfk_stem_src* s, const void* w, const sfk_fmap* y, float* stats, hipStream_t hs, int64_t* dry) {
   StemK k;
-  const int st = fwd_args(s, nullptr, 0, 0, w, y, stats, k);
+  const int st = fwd_args(s, nullptr, 0, 0, w, y, stats, k, dry != nullptr);
   if (st != SFK_OK) return st;
   // canonical fast stem geometry in bf16 with 16-byte addressable rows: temporal pairs over a rolling frame ring
   if (y->dtype == SFK_BF16 && s->src_dtype == SFK_BF16 && s->cin == 3 && (s->kt == 5 || s->kt == 3) && y->c <= 8 &&
@@ -1416,7 +1462,6 @@ extern "C" int sfk_stem_conv_fwd(const sfk_stem_src* s, const void* w, const sfk
       stem_src_extent(s, y->n) < (1ll << 32) - 64) {
     k.src_bytes = (uint32_t)stem_src_extent(s, y->n);
     k.y_bytes = 0;
-    hipStream_t hs2 = static_cast<hipStream_t>(stream);
     const int nf = s->kt + 1;
     const int lds2 = nf * 3 * F2_PLANE + nf * 6 * 1024 + 8 * 16 * 2 * 4;
     const int tpairs = (k.t_log + 1) / 2;
@@ -1429,22 +1474,9 @@ extern "C" int sfk_stem_conv_fwd(const sfk_stem_src* s, const void* w, const sfk
       const int nu = y->n * ((y->h + H2_ROWS - 1) / H2_ROWS) * k.tiles_w * tch;
       const int grid4 = nu < 512 ? nu : 512;
       const int lds4 = 4 * 3 * H2_PLANE + nf * 6 * 1024 + 4 * 16 * 2 * 4 + 32 * 4;
-      if (s->kt == 5) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_v4_kernel<3, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
-        hipLaunchKernelGGL((stem_fwd_v4_kernel<3, 5>), dim3((unsigned)grid4), dim3(256), lds4, hs2, k, ppu, nu, tch);
-      } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_v4_kernel<3, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
-        hipLaunchKernelGGL((stem_fwd_v4_kernel<3, 3>), dim3((unsigned)grid4), dim3(256), lds4, hs2, k, ppu, nu, tch);
-      }
-    } else if (s->kt == 5) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_v2_kernel<3, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-      hipLaunchKernelGGL((stem_fwd_v2_kernel<3, 5>), dim3((unsigned)grid2), dim3(512), lds2, hs2, k, ppu, nunits);
-    } else {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_v2_kernel<3, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-      hipLaunchKernelGGL((stem_fwd_v2_kernel<3, 3>), dim3((unsigned)grid2), dim3(512), lds2, hs2, k, ppu, nunits);
+      return s->kt == 5 ? launch_fwd_v4<5>(k, grid4, lds4, hs, ppu, nu, tch, dry) : launch_fwd_v4<3>(k, grid4, lds4, hs, ppu, nu, tch, dry);
     }
-    SFK_CHECK_LAUNCH();
-    return SFK_OK;
+    return s->kt == 5 ? launch_fwd_v2<5>(k, grid2, lds2, hs, ppu, nunits, dry) : launch_fwd_v2<3>(k, grid2, lds2, hs, ppu, nunits, dry);
   }
   // canonical slow stem geometry in bf16: the register-filter kernel above
   if ((sfk_tune().stem_v3 & 2) && y->dtype == SFK_BF16 && s->src_dtype == SFK_BF16 && s->cin == 3 && s->kt == 1 && y->c == 64 &&
@@ -1452,26 +1484,21 @@ extern "C" int sfk_stem_conv_fwd(const sfk_stem_src* s, const void* w, const sfk
       !(y->ld % 8) && !(y->c_off % 8) && stem_src_extent(s, y->n) < (1ll << 31) && k.t_log >= 2) {
     k.src_bytes = (uint32_t)stem_src_extent(s, y->n);
     k.y_bytes = 0;
-    hipStream_t hs3 = static_cast<hipStream_t>(stream);
     const int ppu = 2;
     const int nfull = k.t_log / 2, tch = nfull <= ppu ? 1 : (nfull + ppu - 1) / ppu;
     const int nu = y->n * ((y->h + H2_ROWS - 1) / H2_ROWS) * k.tiles_w * tch;
     const int grid4 = nu < 512 ? nu : 512;
     const int lds4 = 4 * 3 * H2_PLANE + 24 * 1024 + 4 * 64 * 2 * 4 + 32 * 4;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_fwd_s4_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds4);
-    hipLaunchKernelGGL((stem_fwd_s4_kernel<3>), dim3((unsigned)grid4), dim3(256), lds4, hs3, k, ppu, nu, tch);
-    SFK_CHECK_LAUNCH();
-    return SFK_OK;
+    return launch_fwd_s4(k, grid4, lds4, hs, ppu, nu, tch, dry);
   }
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  return s->src_dtype == SFK_BF16 ? stem_fwd_generic<bf16_t>(k, y, hs) : stem_fwd_generic<float>(k, y, hs);
+  return s->src_dtype == SFK_BF16 ? stem_fwd_generic<bf16_t>(k, y, hs, dry) : stem_fwd_generic<float>(k, y, hs, dry);
 }
 
-extern "C" int sfk_stem_conv_wgrad(const sfk_stem_src* s, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
+// sfk_stem_conv_wgrad, and with `dry` its route
+int stem_conv_wgrad_run(const sfk_stem_src* s, const sfk_fmap* dy, float* dw, hipStream_t hs, int64_t* dry) {
   StemK k;
-  const int st = wgrad_args(s, nullptr, 0, 0, dy, dw, k);
+  const int st = wgrad_args(s, nullptr, 0, 0, dy, dw, k, dry != nullptr);
   if (st != SFK_OK) return st;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
   // canonical fast stem geometry in bf16 with 16-byte addressable rows: the input-frame-stationary kernel
   if (dy->dtype == SFK_BF16 && s->src_dtype == SFK_BF16 && s->cin == 3 && s->kt <= 5 && dy->c <= 8 && s->sw == 1 &&
       (s->w_in % 8) == 0 && !((s->sn | s->sc | s->st | s->sh) & 7) && !(((uintptr_t)s->src) & 15) &&
@@ -1483,11 +1510,32 @@ extern "C" int sfk_stem_conv_wgrad(const sfk_stem_src* s, const sfk_fmap* dy, fl
     k.tiles_per_block = (k.ntiles + blocks - 1) / blocks;
     blocks = (k.ntiles + k.tiles_per_block - 1) / k.tiles_per_block;
     blocks = (blocks + 7) & ~7;                 // a multiple of 8 for the XCD-aware range order (surplus workgroups find no items)
-    hipLaunchKernelGGL((stem_wgrad_v2_kernel<3>), dim3((unsigned)blocks), dim3(256), 0, hs, k);
-    SFK_CHECK_LAUNCH();
-    return SFK_OK;
+    return launch_wgrad_v2(k, blocks, hs, dry);
   }
-  return s->src_dtype == SFK_BF16 ? stem_wgrad_generic<bf16_t>(k, dy, hs) : stem_wgrad_generic<float>(k, dy, hs);
+  return s->src_dtype == SFK_BF16 ? stem_wgrad_generic<bf16_t>(k, dy, hs, dry) : stem_wgrad_generic<float>(k, dy, hs, dry);
+}
+
+}  // namespace
+
+extern "C" int sfk_stem_conv_fwd(const sfk_stem_src* s, const void* w, const sfk_fmap* y, float* stats,
+                                 sfk_stream_t stream) {
+  return stem_conv_fwd_run(s, w, y, stats, static_cast<hipStream_t>(stream), nullptr);
+}
+
+extern "C" int64_t sfk_stem_conv_fwd_route(const sfk_stem_src* s, const sfk_fmap* y) {
+  int64_t route = SFK_ERR_INVALID;
+  const int st = stem_conv_fwd_run(s, nullptr, y, nullptr, nullptr, &route);
+  return st != SFK_OK ? st : route;
+}
+
+extern "C" int sfk_stem_conv_wgrad(const sfk_stem_src* s, const sfk_fmap* dy, float* dw, sfk_stream_t stream) {
+  return stem_conv_wgrad_run(s, dy, dw, static_cast<hipStream_t>(stream), nullptr);
+}
+
+extern "C" int64_t sfk_stem_conv_wgrad_route(const sfk_stem_src* s, const sfk_fmap* dy) {
+  int64_t route = SFK_ERR_INVALID;
+  const int st = stem_conv_wgrad_run(s, dy, nullptr, nullptr, &route);
+  return st != SFK_OK ? st : route;
 }
 
 // ------------------------------------------------------------------------------------------ uint8 frames (sfk_u8stem.h)
