@@ -42,8 +42,9 @@ extern "C" {
  * sfk_conv_igemm_family value 4; 15 = sfk_tuning.igemm_halo, family value 5; 16 = sfk_tuning.wgrad_band; 17 = sfk_tuning.stem_v3; 18 = sfk_bn_finalize_apply (19, 20: SFK_BN_SYNC_INTS counters),
  * sfk_bn_bwd_finalize_apply; 21 = the two fused finalize launches, SFK_BN_SYNC_INTS and sfk_tuning.wgrad_target_256 /
  * wgrad_min_stages_256 removed, stem_v3 bit 2 retired; 22 = sfk_conv_igemm_route / sfk_conv_wgrad_route and the route enums;
- * 23 = sfk_stem_conv_fwd_route / sfk_stem_conv_wgrad_route and sfk_stem_route. */
-#define SFK_ABI_VERSION 23
+ * 23 = sfk_stem_conv_fwd_route / sfk_stem_conv_wgrad_route and sfk_stem_route; 24 = route bits SFK_IGEMM_ROUTE_COGROUPS4 /
+ * SFK_WGRAD_ROUTE_RING5 (every earlier route value unchanged) and the SFK_*_ROUTES_TUNED lists. */
+#define SFK_ABI_VERSION 24
 #define SFK_MAX_TAPS 16
 #define SFK_BN_FOLD_ROWS 64 /* rows of the optional BatchNorm fold workspace */
 
@@ -212,16 +213,23 @@ int sfk_conv_wgrad_wants_workspace(const sfk_wgrad_desc* d);
  *     kernel  sfk_igemm_kernel;  bf16 = 1 for SFK_BF16 maps;  bm = pixel rows a tile computes (128 / 224 / 256), bn = output
  *     channels of a tile (16 .. 256);  epi = the epilogue flavour: 0 plain, 1 BatchNorm-backward reduce (5 its bitmap
  *     flavour, 6 its += flavour, 7 with a mask source), 2 out_relu_bits, 3 fused output transform (4 with the shortcut
- *     pre-fetched);  shortk = the exact-count K loop;  wide = 16-byte (8 x bf16) stores are taken.
+ *     pre-fetched);  shortk = the exact-count K loop;  wide = 16-byte (8 x bf16) stores are taken (the fused epilogues 1, 3 .. 7
+ *     of a bf16 tile of 32 or more output channels take them whatever igemm_wide_store says; the plain epilogue follows it).
  *     The streaming pointwise kernels (conv_pw.hip) report bm = 32 x the K-steps of the resident filter, bn = cout, epi = 0
- *     (1: the data-gradient flavour with bitmap mask and column sums).
+ *     (1: the data-gradient flavour with bitmap mask and column sums).  SFK_IGEMM_ROUTE_COGROUPS4 (bit 29) is set for the one
+ *     shape with two instantiations, cout = 256 over a 64-channel K: four co groups of 64 channels per workgroup
+ *     (igemm_pw_stream == 2) instead of two of 128.
  *   sfk_conv_wgrad_route: SFK_WGRAD_ROUTE(kernel, bf16, tco, tci, ksnw, gram, dg) in the low 29 bits, then
  *     SFK_WGRAD_ROUTE_WS(r) = 1 when THIS descriptor's workspace / workspace_bytes select the workspace path (0: float
  *     atomics, also when the workspace is too small) and SFK_WGRAD_ROUTE_SPLITS(r) = the pixel splits.
  *     kernel  sfk_wgrad_kernel;  tco x tci = the dW tile;  ksnw = K-steps per stage (CFG) or waves per workgroup (DMA, P8,
- *     BAND);  gram = one staged tile serves x and dy;  dg = with the fused data gradient.
+ *     BAND);  gram = one staged tile serves x and dy;  dg = with the fused data gradient.  SFK_WGRAD_ROUTE_RING5 (bit 30, part of
+ *     SFK_WGRAD_ROUTE_ID) is set when the LDS-DMA kernel runs its 5-slot ring (wgrad_wide_co bit 3) instead of the 3-slot one:
+ *     SFK_WGRAD_ROUTE_RING(r) = the slots.
  * SFK_IGEMM_ROUTES / SFK_WGRAD_ROUTES list every route reachable with the default tuning table and operands below
- * 2 GiB (beyond that the bf16 ring kernels hand over to the register-staged 128 x 128 tile, a route outside this list). */
+ * 2 GiB (beyond that the bf16 ring kernels hand over to the register-staged 128 x 128 tile, a route outside this list).
+ * SFK_IGEMM_ROUTES_TUNED / SFK_WGRAD_ROUTES_TUNED list the further routes that only a non-default sfk_tuning table reaches, as
+ * far as tests/tuned_tables.py holds them (three tables; other knob values can reach more). */
 typedef enum { SFK_IK_REG = 0, SFK_IK_DMA = 1, SFK_IK_PWP = 2, SFK_IK_PWF = 3, SFK_IK_P8 = 4, SFK_IK_HALO = 5, SFK_IK_PWD = 6 } sfk_igemm_kernel;
 /* REG register-staged, DMA LDS-DMA ring, PWP / PWF / PWD streaming pointwise plain / fused output transform / data gradient,
  * P8 deep-pipelined 256 x 256 tile, HALO LDS-band 3 x 3.  sfk_conv_igemm_family = the kernel, with PWP / PWF / PWD all 3. */
@@ -229,9 +237,12 @@ typedef enum { SFK_WK_CFG = 0, SFK_WK_DMA = 1, SFK_WK_P8 = 2, SFK_WK_BAND = 3 } 
 #define SFK_IGEMM_ROUTE(kernel, bf16, bm, bn, epi, shortk, wide) \
   (((bf16) << 28) | ((kernel) << 24) | ((bm) << 15) | ((bn) << 5) | ((epi) << 2) | ((shortk) << 1) | (wide))
 #define SFK_IGEMM_ROUTE_KERNEL(r) (((r) >> 24) & 15)
+#define SFK_IGEMM_ROUTE_COGROUPS4 (1 << 29)
 #define SFK_WGRAD_ROUTE(kernel, bf16, tco, tci, ksnw, gram, dg) \
   (((bf16) << 28) | ((kernel) << 24) | ((tco) << 15) | ((tci) << 6) | ((ksnw) << 2) | ((gram) << 1) | (dg))
-#define SFK_WGRAD_ROUTE_ID(r) ((int)((r) & 0x1FFFFFFF))
+#define SFK_WGRAD_ROUTE_RING5 (1 << 30)
+#define SFK_WGRAD_ROUTE_ID(r) ((int)((r) & 0x5FFFFFFF))
+#define SFK_WGRAD_ROUTE_RING(r) (((r) & SFK_WGRAD_ROUTE_RING5) ? 5 : 3)
 #define SFK_WGRAD_ROUTE_WS(r) ((int)(((r) >> 29) & 1))
 #define SFK_WGRAD_ROUTE_SPLITS(r) ((int)((r) >> 32))
 /* X(kernel, bf16, bm, bn, epi, shortk, wide) */
@@ -265,8 +276,18 @@ typedef enum { SFK_WK_CFG = 0, SFK_WK_DMA = 1, SFK_WK_P8 = 2, SFK_WK_BAND = 3 } 
   X(BAND, 1, 128, 128, 8, 0, 0)
 #define SFK_IR_ENUM_(k, b, bm, bn, e, s, w) SFK_IR_##k##_T##b##_##bm##x##bn##_E##e##_S##s##_W##w = SFK_IGEMM_ROUTE(SFK_IK_##k, b, bm, bn, e, s, w),
 #define SFK_WR_ENUM_(k, b, tco, tci, n, g, d) SFK_WR_##k##_T##b##_##tco##x##tci##_N##n##_G##g##_D##d = SFK_WGRAD_ROUTE(SFK_WK_##k, b, tco, tci, n, g, d),
-typedef enum { SFK_IGEMM_ROUTES(SFK_IR_ENUM_) SFK_IR_NONE_ = -1 } sfk_igemm_route;
-typedef enum { SFK_WGRAD_ROUTES(SFK_WR_ENUM_) SFK_WR_NONE_ = -1 } sfk_wgrad_route;
+/* X(kernel, bf16, bm, bn, epi, shortk, wide, cogroups4): igemm_p8 bit 1 (the 224-row P8 tile), igemm_pw_stream == 2 */
+#define SFK_IGEMM_ROUTES_TUNED(X) \
+  X(P8, 1, 224, 256, 0, 0, 1, 0) X(P8, 1, 224, 256, 2, 0, 1, 0) X(PWF, 1, 64, 256, 0, 0, 1, 1)
+/* X(kernel, bf16, tco, tci, ksnw, gram, dg, ring5): wgrad_wide_co bit 3 */
+#define SFK_WGRAD_ROUTES_TUNED(X) \
+  X(DMA, 1, 128, 128, 4, 0, 0, 1) X(DMA, 1, 256, 128, 8, 0, 0, 1)
+#define SFK_IRT_ENUM_(k, b, bm, bn, e, s, w, c) \
+  SFK_IR_##k##_T##b##_##bm##x##bn##_E##e##_S##s##_W##w##_C##c = SFK_IGEMM_ROUTE(SFK_IK_##k, b, bm, bn, e, s, w) | ((c) ? SFK_IGEMM_ROUTE_COGROUPS4 : 0),
+#define SFK_WRT_ENUM_(k, b, tco, tci, n, g, d, r) \
+  SFK_WR_##k##_T##b##_##tco##x##tci##_N##n##_G##g##_D##d##_R##r = SFK_WGRAD_ROUTE(SFK_WK_##k, b, tco, tci, n, g, d) | ((r) ? SFK_WGRAD_ROUTE_RING5 : 0),
+typedef enum { SFK_IGEMM_ROUTES(SFK_IR_ENUM_) SFK_IGEMM_ROUTES_TUNED(SFK_IRT_ENUM_) SFK_IR_NONE_ = -1 } sfk_igemm_route;
+typedef enum { SFK_WGRAD_ROUTES(SFK_WR_ENUM_) SFK_WGRAD_ROUTES_TUNED(SFK_WRT_ENUM_) SFK_WR_NONE_ = -1 } sfk_wgrad_route;
 int sfk_conv_igemm_route(const sfk_conv_desc* d);     /* sfk_igemm_route (or a route outside the list, see above); < 0: sfk_status */
 int64_t sfk_conv_wgrad_route(const sfk_wgrad_desc* d); /* sfk_wgrad_route + WS + SPLITS; < 0: sfk_status */
 
@@ -581,12 +602,17 @@ typedef struct {
   int32_t wgrad_use_workspace;/* 1:    use sfk_wgrad_desc.workspace when given                                    */
   int32_t wgrad_wide_co;      /* 7:    bit 0: one 256 x 64 tile for wide-output / narrow-input layers; bit 1: the LDS-DMA
                                          256 x 128 tile (half idle) when cout = 256 and taps x cin = 64; bit 2: Gram
-                                         matrices (x and dy the same map) stage ONE tile for both operands              */
+                                         matrices (x and dy the same map) stage ONE tile for both operands; bit 3 (off): the
+                                         LDS-DMA kernels run a 5-slot ring instead of the 3-slot one (not the fused-data-gradient
+                                         tile, which keeps 3 slots)                                                     */
   int32_t bn_parts;           /* 1024: partial rows of the BatchNorm reductions (one resident generation)         */
   int32_t nt_apply_mb;        /* 0:    non-temporal loads+stores in sfk_bn_apply for maps >= this many MB (-1 off) */
   int32_t nt_reduce_mb;       /* 48:   non-temporal loads in sfk_bn_bwd_reduce                                    */
   int32_t nt_bwd_apply_mb;    /* 150:  non-temporal loads+stores in sfk_bn_bwd_apply                              */
-  int32_t igemm_pw_stream;    /* 1:    streaming kernel for small-filter pointwise convs with a fused shortcut / ReLU     */
+  int32_t igemm_pw_stream;    /* 1:    streaming kernel for small-filter pointwise convs with a fused shortcut / ReLU (any non-zero
+                                         value); exactly 2: cout = 256 over a 64-channel K runs four co groups of 64 channels per
+                                         workgroup instead of two of 128; bit 2 (value 4): the streaming data-gradient flavour
+                                         (PWD) is off; bit 3 (value 8): the plain / += flavour (PWP) is off                  */
   int64_t pool_blocks;        /* 1<<20: grid cap of the pooling kernels (one pass per thread below it)            */
   int32_t igemm_tile256;      /* 3:    bit 0: 256 x 256 tile (one workgroup per CU) for MFMA-bound layers with 256 outputs;
                                          bit 1: 224 computed rows per tile where that fills the CUs better (M = 50,176)   */

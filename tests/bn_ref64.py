@@ -605,7 +605,7 @@ def torch_pool(x5: torch.Tensor, k: int, s: int, p: int):
 
 def pool_input(case, gen) -> torch.Tensor:
     """(N,T,H,W,C) float64 values on a few levels, so that ties are common; both signs unless the case says otherwise"""
-    n, t, c = 2, 2, 3 * vec_of(case["dtype"])
+    n, t, c = case.get("n", 2), case.get("t", 2), case.get("cg", 3) * vec_of(case["dtype"])     # (tests/tuned_tables.py sets them)
     q = (1.5 * torch.randn(n, t, case["h"], case["w"], c, generator=gen, dtype=F64)).round().clamp(-4, 4)
     if case["fill"] == "negative":
         q = -1.0 - q.abs()

@@ -227,4 +227,4 @@ def test_stem2d_rejects_bad_descriptors_on_the_host(lib):
 
 def test_main_abi_lock_matches_header():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "abi_lock.py")], capture_output=True, text=True)
-    assert out.returncode == 0 and "ABI 23 matches" in out.stdout, out.stdout + out.stderr
+    assert out.returncode == 0 and "ABI 24 matches" in out.stdout, out.stdout + out.stderr

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFK_LIB") or os.path.join(HERE, "libsfk.so")   # SFK_LIB: experiment builds (tools/gpu_ab_lib.sh)
 SFK_F32, SFK_BF16 = 0, 1
 SFK_MAX_TAPS = 16
-ABI_VERSION = 23       # include/sfk.h SFK_ABI_VERSION
+ABI_VERSION = 24       # include/sfk.h SFK_ABI_VERSION
 BN_FOLD_ROWS = 64      # include/sfk.h SFK_BN_FOLD_ROWS
 _DT = {torch.float32: SFK_F32, torch.bfloat16: SFK_BF16}
 
@@ -903,7 +903,7 @@ class HipBackend:
         r = int(self.lib.sfk_conv_wgrad_route(C.byref(d)))
         if r < 0:
             _check(r, "sfk_conv_wgrad_route")
-        return r & 0x1FFFFFFF, bool((r >> 29) & 1), r >> 32
+        return r & 0x5FFFFFFF, bool((r >> 29) & 1), r >> 32     # (the id keeps bit 30: SFK_WGRAD_ROUTE_RING5)
 
     def conv_wgrad(self, p: WgradPass):
         d = self._wgrad_desc(p)

@@ -630,7 +630,7 @@ template <typename T, int BM, int BN, int WM, int WN, bool SHORTK, int EPI = 0>
 int run_reg(const ConvK& k, dim3 grid, hipStream_t s, int* dry) {
   if (dry) {
     constexpr int FN = co_frags(BN, WN);
-    const int wide = wide_store_taken<T, FN>(k) ? 1 : 0;
+    const int wide = route_wide<T, FN, EPI>(k) ? 1 : 0;
     *dry = SFK_IGEMM_ROUTE(SFK_IK_REG, sizeof(T) == 2 ? 1 : 0, BM, BN, EPI, SHORTK ? 1 : 0, wide);
     return SFK_OK;
   }
@@ -642,7 +642,7 @@ template <int BM, int BN, int WM, int WN, int EPI = 0, int BMS = BM>
 int run_dma(const ConvK& k, dim3 grid, hipStream_t s, int* dry) {
   if (dry) {
     constexpr int FN = co_frags(BN, WN);
-    const int wide = wide_store_taken<bf16_t, FN>(k) ? 1 : 0;
+    const int wide = route_wide<bf16_t, FN, EPI>(k) ? 1 : 0;
     *dry = SFK_IGEMM_ROUTE(SFK_IK_DMA, 1, BMS, BN, EPI, 0, wide);
     return SFK_OK;
   }

@@ -55,6 +55,16 @@ __host__ __device__ __forceinline__ bool wide_store_taken(const ConvK& k) {
   return sizeof(T) == 2 && (FN % 2) == 0 && k.wide_store;
 }
 
+// ... and of "the fused epilogues (EPI 1, 5, 6, 7: BatchNorm-backward reduce; 3, 4: output transform) of a bf16 tile with an
+// even number of co fragments store 8-channel groups WHATEVER igemm_wide_store says": they never read k.wide_store (validate()
+// admits them only where those groups are 16-byte addressable: bnb_ok), so the route reports `wide` for them by this.  EPI 2
+// (the bitmap on the plain epilogue) forces k.wide_store on in launch() and is covered by wide_store_taken.
+template <typename T, int FN, int EPI>
+__host__ __device__ __forceinline__ bool route_wide(const ConvK& k) {
+  if (sizeof(T) == 2 && (FN % 2) == 0 && (EPI == 1 || EPI >= 3)) return true;
+  return wide_store_taken<T, FN>(k);
+}
+
 constexpr int BK = 32;
 
 template <typename T> struct Tile;

@@ -260,7 +260,7 @@ inline int pw_blocks(int M, int CG, int NT) {
 template <int NF, int KS, int CG, int NT, bool XDB, int MODE = 0>
 int pw_launch(const PwK& k, hipStream_t s, int* dry, int kernel) {
   if (dry) {       // the route (include/sfk.h) instead of the launch
-    *dry = SFK_IGEMM_ROUTE(kernel, 1, 32 * KS, NF * 16 * CG, MODE, 0, 1);
+    *dry = SFK_IGEMM_ROUTE(kernel, 1, 32 * KS, NF * 16 * CG, MODE, 0, 1) | (NF * 16 * CG == 256 && CG == 4 ? SFK_IGEMM_ROUTE_COGROUPS4 : 0);
     return SFK_OK;
   }
   const size_t lds = (size_t)KS * k.cout * 64 + (size_t)3 * k.cout * 4;

@@ -567,7 +567,7 @@ int launch_dma(WgradK& k, const sfk_wgrad_desc* d, hipStream_t s, WgradDry* dry)
   const int64_t need = (int64_t)splits * base * NW * (4 * FI) * 64 * 16;
   if (dry && dry->sizing()) { dry->bytes = need; return SFK_OK; }
   if (k.ws && need > d->workspace_bytes) k.ws = nullptr;
-  if (dry) { dry->report(SFK_WK_DMA, true, TCO, TCI, NW, false, DG, splits, k.ws != nullptr); return SFK_OK; }
+  if (dry) { dry->report(SFK_WK_DMA, true, TCO, TCI, NW, false, DG, splits, k.ws != nullptr, NS); return SFK_OK; }
   hipLaunchKernelGGL((conv_wgrad_dma_kernel<TCO, NW, DG, TCI, NS>), dim3((unsigned)(base * splits)), dim3(64 * NW), 0, s, k);
   SFK_CHECK_LAUNCH();
   if (k.ws) return launch_reduce<NW, TCO / 64, 4, FI>(k, splits, s);

@@ -38,9 +38,9 @@ struct WgradDry {
   int64_t bytes = 0;
   int64_t* route = nullptr;
   bool sizing() const { return route == nullptr; }
-  void report(int kernel, bool bf16, int tco, int tci, int ksnw, bool gram, bool dg, int splits, bool ws) {
+  void report(int kernel, bool bf16, int tco, int tci, int ksnw, bool gram, bool dg, int splits, bool ws, int ring = 3) {
     *route = (int64_t)SFK_WGRAD_ROUTE(kernel, bf16 ? 1 : 0, tco, tci, ksnw, gram ? 1 : 0, dg ? 1 : 0) | ((int64_t)(ws ? 1 : 0) << 29) |
-             ((int64_t)splits << 32);
+             (ring == 5 ? (int64_t)SFK_WGRAD_ROUTE_RING5 : 0) | ((int64_t)splits << 32);
   }
 };
 
