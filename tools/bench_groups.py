@@ -3,7 +3,15 @@ classes, bf16): sfk_adam_hp, sfk_adam_groups with one all-covering group, and sf
 covered (Engine.param_segments with blocks.0 .. blocks.3 frozen), next to the covered bytes.  One process; after a warm-up the
 variants alternate; every launch is timed on its own with events; median [min, max] over `--launches` launches each.  One JSON
 line per variant (kept in profiles/groups_bench.jsonl).
-Usage: python tools/bench_groups.py [--launches 60] [--warmup 3] [--parent-lib LIB]
+
+`--mode step`: whole eager TrainSteps at the benchmark geometry (32 clips of 32 x 224 x 224, bf16, one process; no step is
+captured): the hp step with a constant lr_table and no groups (the same-build baseline), one all-covering group,
+freeze=['blocks.0.'] (the stems and fusion 0), freeze=['blocks.0.', 'blocks.1.'], and everything frozen but blocks.4. and the
+head.  The variants share one engine and alternate over `--rounds` rounds: each window sets its frozen set (the train plan is
+rebuilt into the engine's buffers), warms up, then times `--steps` steps between two device events around synchronised
+windows.  One JSON line per variant: ms per step (median [min, max] of the rounds' windows), kernel launches per step by
+`kind` counted from the plan's meta, and the covered elements (kept in profiles/groups_step_bench.jsonl).
+Usage: python tools/bench_groups.py [--mode launch|step] [--launches 60] [--warmup 3] [--parent-lib LIB] [--rounds 3] [--steps 8]
 --parent-lib: a shared library with the parent commit's sfk_adam_hp -- that commit's csrc/optim_sched.hip compiled alone
 (hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Iinclude -Ivideo-classification_amd/csrc -shared) -- timed first, beside this
 build's, in the same process."""
@@ -83,14 +91,80 @@ def launch_part(eng, args):
                           "hbm_fraction": round(nbytes / (med * 1e-3) / HBM_PEAK, 3)}), flush=True)
 
 
+def step_part(model, args):
+    from collections import Counter
+
+    from video_classification_amd.slowfast import pack_pathway_index
+    from video_classification_amd.train import TrainStep
+    eng, dev = model.engine, model.engine.device
+    model.train()
+    gen = torch.Generator().manual_seed(1234)
+    frames = torch.randn(args.batch, 3, 32, 224, 224, generator=gen).to(torch.bfloat16).to(dev)
+    labels = torch.randint(0, 400, (args.batch,), generator=gen).to(dev)
+    idx = pack_pathway_index(32, 4, dev)
+    table = [2e-4] * 1000
+    top = [k for k, _, _ in eng.param_tensors() if not k.startswith(("blocks.4.", eng.wiring.head_key))]
+    variants = {
+        "hp step (lr_table, no groups)": {},
+        "one all-covering group": dict(param_groups=[("blocks.", 1.0)]),
+        "freeze blocks.0.": dict(freeze=["blocks.0."]),
+        "freeze blocks.0. blocks.1.": dict(freeze=["blocks.0.", "blocks.1."]),
+        "train blocks.4. + head only": dict(freeze=["blocks.0.", "blocks.1.", "blocks.2.", "blocks.3."]),
+    }
+    assert eng.frozen_param_keys(variants["train blocks.4. + head only"]["freeze"]) == frozenset(top)
+    ms, info = {k: [] for k in variants}, {}
+    # one TrainStep per variant, built once, all on ONE trunk stream (TrainStep(trunk=)): with a new high-priority stream per
+    # window some windows of EVERY variant, the baseline included, ran about 10 ms a step slower than the others (27.6 against
+    # 38 .. 41.5 ms for the hp step: profiles/groups_step_bench.jsonl, part "step-new-stream-per-window")
+    steps = {}
+    for name, kw in variants.items():
+        steps[name] = TrainStep(eng, lr=2e-4, lr_table=table, trunk=next(iter(steps.values())).trunk if steps else None, **kw)
+    for _ in range(args.rounds):
+        for name, kw in variants.items():
+            step = steps[name]                                          # its first call puts its frozen set back: the warm-up rebuilds the plan
+            for _ in range(args.warmup):
+                step(frames, frames, labels, slow_t_index=idx)
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(args.steps):
+                step(frames, frames, labels, slow_t_index=idx)
+            b.record()
+            torch.cuda.synchronize()
+            ms[name].append(a.elapsed_time(b) / args.steps)
+            if name not in info:
+                pl = eng._plan_for(frames, frames, idx, True)
+                ops = next(iter(step._cache.values()))["ops"]
+                kinds = Counter(m["kind"] for ol in (pl.fwd, pl.bwd) for m in ol.meta if m is not None)
+                info[name] = dict(launches_by_kind=dict(sorted(kinds.items())), described_launches=sum(kinds.values()),
+                                  fwd_ops=len(pl.fwd), bwd_ops=len(pl.bwd), step_ops=sorted(ops),
+                                  covered=sum(e - b_ for b_, e, _, _ in step.opt.segments) if step.opt.grouped else eng.arena_numel,
+                                  segments=len(step.opt.segments) if step.opt.grouped else 1, loss=round(float(step.loss[0]), 4))
+    base, allc = statistics.median(ms["hp step (lr_table, no groups)"]), statistics.median(ms["one all-covering group"])
+    for name in variants:
+        med = statistics.median(ms[name])
+        print(json.dumps(dict({"part": "step", "variant": name, "batch": args.batch, "numel": eng.arena_numel, "rounds": args.rounds,
+                               "steps_per_window": args.steps, "ms_per_step_median": round(med, 3),
+                               "ms_per_step_min": round(min(ms[name]), 3), "ms_per_step_max": round(max(ms[name]), 3),
+                               "ms_per_step_windows": [round(x, 3) for x in ms[name]],
+                               "vs_hp_step": round(med / base, 4), "vs_all_covering": round(med / allc, 4)}, **info[name])),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=("launch", "step"), default="launch")
+    ap.add_argument("--rounds", type=int, default=3, help="step mode: windows per variant")
+    ap.add_argument("--steps", type=int, default=8, help="step mode: timed steps per window")
+    ap.add_argument("--batch", type=int, default=32, help="step mode: clips")
     ap.add_argument("--launches", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--parent-lib", default="", help="a shared library holding the parent commit's sfk_adam_hp, timed beside this build's")
     args = ap.parse_args()
     from video_classification_amd.slowfast import slowfast_r50_8x8
     model = slowfast_r50_8x8(400, dtype=torch.bfloat16, device="cuda", seed=0)
+    if args.mode == "step":
+        return step_part(model, args)
     launch_part(model.engine, args)
 
 

@@ -134,6 +134,9 @@ _C.MODEL.WEIGHT_DECAY = 0.0
 _C.MODEL.WEIGHT_DECAY_MODE = 'decoupled'   # 'decoupled' (AdamW; Adam only) | 'l2' (torch's Adam / SGD weight_decay)
 _C.MODEL.WEIGHT_DECAY_SCOPE = 'weights'    # 'weights' (conv filters and the FC weight) | 'all' (biases and BatchNorm too)
 _C.MODEL.CLIP_GRAD_NORM = 0.0       # clip_grad_norm_(max_norm) before the optimizer launch; 0 = off
+# ---- parameter groups and frozen layers (include/sfk_groups.h, schedule.group_kwargs); both empty keeps the launches above
+_C.MODEL.PARAM_GROUPS = []          # [selector, lr_mult] or [selector, lr_mult, wd_mult] in priority order; a selector is a state_dict() key prefix ('blocks.1.'), '@fresh' or '@pretrained' (what load_pretrained left untouched / filled)
+_C.MODEL.FREEZE = []                # selectors of the tensors that do not train (freeze beats groups); eager steps only
 _C.DIST = CfgNode()
 _C.DIST.BUCKET_MB = 32         # gradient all-reduce bucket size
 

@@ -197,6 +197,8 @@ class Engine:
         self._bufs: Dict[str, torch.Tensor] = {}
         self._plans: Dict[tuple, Plan] = {}
         self.fresh_keys = None                      # keys a pretrained load left untouched (ModelManager.load_pretrained); None = all of them
+        self.frozen_keys = frozenset()              # parameter keys the train plans are built without (set_frozen)
+        self._trainable_ranges = None               # arena ranges of the other parameters, made when a plan first asks (_mark)
         self._build_params(seed)
         self.max_parts = _max_parts() if getattr(self.be, "name", "") == "hip" else 1024
         self.two_streams = True           # slow / fast pathway on two HIP streams (see OpList)
@@ -531,7 +533,7 @@ class Engine:
         pl.bwd.append(self.be.bn_bwd_finalize(parts, np_, L.c, rec.y.pixels, self._pslice(L.g_off, L.c), rec.invstd,
                                               self._gslice(L.g_off, L.c), self._gslice(L.b_off, L.c), coef,
                                               self._fold_ws(tag, L.c)), kind="bn_finalize")
-        pl.grad_marks.append((len(pl.bwd), (L.g_off, L.b_off + round_up(L.c, self.vec) - L.g_off)))
+        self._mark(pl, L.g_off, L.b_off + round_up(L.c, self.vec) - L.g_off)
         if dz_inplace:   # the mask is already applied to da
             pl.bwd.append(self.be.bn_bwd_apply(da, rec.y, None, rec.mean, rec.invstd, rec.scale, rec.shift, False,
                                                coef, dy), kind="bn_bwd_apply", layer=L.cb.norm_key, bytes=el * 3)
@@ -542,6 +544,8 @@ class Engine:
 
     def _wgrad(self, pl: Plan, rec: _UnitRec, dy: FMap):
         L = rec.L
+        if self._w_frozen(L):         # its only output is a frozen filter's gradient: no launch, and no Wait for its lane
+            return
         esz = 2 if self.dtype == torch.bfloat16 else 4
         wp = WgradPass(rec.x, dy, L.eg.s, list(wgrad_taps(L.eg)), self._gslice(L.w_off, L.w_numel), L.eg.wtaps,
                        L.eg.cin, L.eg.cout)
@@ -565,7 +569,7 @@ class Engine:
                       kind="conv_wgrad", layer=L.cb.conv_key, cout=L.eg.cout,
                       flops=2.0 * dy.pixels * L.eg.cout * L.eg.cin * L.eg.wtaps,
                       bytes=float(esz * (rec.x.pixels * L.eg.cin + dy.pixels * L.eg.cout) + 4 * L.w_numel))
-        pl.grad_marks.append((len(pl.bwd), (L.w_off, round_up(L.w_numel, self.vec))))
+        self._mark(pl, L.w_off, round_up(L.w_numel, self.vec))
         pl.bwd.cur_lane = home
 
     def _dgrad(self, pl: Plan, rec: _UnitRec, dy: FMap, dx: FMap, accumulate: bool, fuse=None, out_bits=None,
@@ -655,7 +659,7 @@ class Engine:
             pl.fwd.append(fwd, **meta)
         else:
             pl.fwd[st["fwd_slot"]] = fwd
-        if st.get("da") is not None:
+        if st.get("da") is not None and not self._w_frozen(L):       # (a frozen stem filter: no filter-gradient op, no tail_cut)
             bwd = wgrad_fn(src, st["da"], self._gslice(L.w_off, L.w_numel))
             if st["bwd_slot"] is None:
                 st["bwd_slot"] = len(pl.bwd)
@@ -666,7 +670,7 @@ class Engine:
                     if all(M.w_off >= cut or M.cb.is_stem for M in self.layers):
                         pl.tail_cut = (len(pl.bwd), cut)
                 pl.bwd.append(bwd, kind="stem_wgrad", layer=L.cb.conv_key, cout=L.c, flops=flops, bytes=meta["bytes"])
-                pl.grad_marks.append((len(pl.bwd), (L.w_off, round_up(L.w_numel, self.vec))))
+                self._mark(pl, L.w_off, round_up(L.w_numel, self.vec))
             else:
                 pl.bwd[st["bwd_slot"]] = bwd
 
@@ -730,7 +734,7 @@ class Engine:
             pl.bwd.append(self.be.bn_bwd_finalize(parts, np_, L.c, y.pixels, self._pslice(L.g_off, L.c), rec.invstd,
                                                   self._gslice(L.g_off, L.c), self._gslice(L.b_off, L.c), coef,
                                                   self._fold_ws(tag, L.c)), kind="bn_finalize")
-            pl.grad_marks.append((len(pl.bwd), (L.g_off, L.b_off + round_up(L.c, self.vec) - L.g_off)))
+            self._mark(pl, L.g_off, L.b_off + round_up(L.c, self.vec) - L.g_off)
             pl.bwd.append(self.be.bn_maxpool_bwd_apply(d_out, argmax, y, rec.mean, rec.invstd, rec.scale, rec.shift, coef, da),
                           kind="bn_bwd_apply", layer=L.cb.norm_key, bytes=rd + float(esz * y.pixels * L.c))
         else:
@@ -874,8 +878,8 @@ class Engine:
         pl.bwd.append(self.be.bn_tail_bwd(r, dz_parts[0], dz_parts[1], tail["g"], tail["count"], tail["t"], c4, w, C, self._pslice(Lc.g_off, C), tail["mean"],
                                           tail["invstd"], self._gslice(Lc.g_off, C), self._gslice(Lc.b_off, C),
                                           self._gslice(Lc.w_off, Lc.w_numel), m, bias, coef))
-        pl.grad_marks.append((len(pl.bwd), (Lc.g_off, Lc.b_off + round_up(C, self.vec) - Lc.g_off)))
-        pl.grad_marks.append((len(pl.bwd), (Lc.w_off, round_up(Lc.w_numel, self.vec))))
+        self._mark(pl, Lc.g_off, Lc.b_off + round_up(C, self.vec) - Lc.g_off)
+        self._mark(pl, Lc.w_off, round_up(Lc.w_numel, self.vec))
         if dual:
             pl.bwd.append(self.be.conv_pw_dual(d_out, tail["wd"], ab, m, bias, dab),
                           kind="conv_dgrad", layer=Lc.cb.conv_key + ":dual", cout=c4, flops=2.0 * d_out.pixels * (C + c4) * c4,
@@ -986,11 +990,13 @@ class Engine:
         self._dgrad(pl, rec1, d_out, dx, accumulate=True)
         return dx, None
 
-    def _stage_bwd(self, pl, brecs, d: FMap) -> FMap:
+    def _stage_bwd(self, pl, brecs, d: FMap, take: Optional[int] = None) -> FMap:
         """backward of one pathway's stage, last block first; each block's final data-gradient pass also reduces the
-        previous block's last BatchNorm (identity shortcuts only: the first block of a stage ends in its projection)"""
+        previous block's last BatchNorm (identity shortcuts only: the first block of a stage ends in its projection).
+        take: only the last `take` blocks (nothing below them is trainable, _build_plan)"""
         reduced = None
-        for i in range(len(brecs) - 1, -1, -1):
+        first = 0 if take is None else len(brecs) - take
+        for i in range(len(brecs) - 1, first - 1, -1):
             prev = brecs[i - 1] if i > 0 else None
             d, reduced = self._block_bwd(pl, brecs[i], d, reduced_c=reduced, prev=prev)
         return d
@@ -1155,34 +1161,57 @@ class Engine:
         else:
             pl.bwd.append(be.fc_bwd(pl.dlogits, feat, fcw, dfeat, self._gslice(self.fc_w_off, F * K),
                                     self._gslice(self.fc_b_off, K), n, F, K))
-        pl.grad_marks.append((len(pl.bwd), (self.fc_w_off, self.layers[0].g_off - self.fc_w_off)))
+        self._mark(pl, self.fc_w_off, self.layers[0].g_off - self.fc_w_off)
+        # The units below the head in the order they are emitted -- per stage the slow pathway's blocks, the fast pathway's,
+        # the lateral fusion; then the stems.  That order is a topological one of the backward, so nothing after the LAST unit
+        # with a trainable parameter (set_frozen) feeds a gradient anyone reads: `left` units are emitted, the rest is not --
+        # no data gradient, no BatchNorm, pool or fusion backward.  Nothing frozen: all of them, as ever.
+        units = []
+        for si in range(3, -1, -1):
+            for p in range(NP):
+                units += [W.stages[si][p][i] for i in range(len(W.stages[si][p]) - 1, -1, -1)]
+            if fuse:
+                units.append(W.fusions[si])
+        units += list(W.stems[:NP])
+        left = max((k + 1 for k, u in enumerate(units) if self._unit_trainable(u)), default=0)
         d_xs = self._fmap("d.cat.4", n, xs_out.t, xs_out.h, xs_out.w, xs_out.c)
         d_xf = None
-        if NP == 2:                                     # fork: the fast pathway un-pools its own gradient on its own lane
+        if NP == 2 and left > 0:                        # fork: the fast pathway un-pools its own gradient on its own lane
             d_xf = self._fmap("d.xf.4", n, xf_out.t, xf_out.h, xf_out.w, xf_out.c)
             B_.sync(1, 0)
             B_.cur_lane = 1
             pl.bwd.append(be.head_pool_bwd(dfeat, F, xs_out.c, kf, rate, self.drop_seed, d_xf))
             B_.cur_lane = 0
-        pl.bwd.append(be.head_pool_bwd(dfeat, F, 0, ks, rate, self.drop_seed, d_xs))
+        if left > 0:
+            pl.bwd.append(be.head_pool_bwd(dfeat, F, 0, ks, rate, self.drop_seed, d_xs))
         for si in range(3, -1, -1):
+            if left <= 0:
+                break
             # slow pathway of this stage: d_xs is the gradient of its last block's output
             B_.cur_lane = 0
-            d = self._stage_bwd(pl, stage_recs[si][0], d_xs)
+            take = min(left, len(stage_recs[si][0]))
+            d = self._stage_bwd(pl, stage_recs[si][0], d_xs, take)
+            left -= take
             d_cat = d                                   # gradient of the (concatenated) slow input of this stage
-            if NP == 2:
+            if NP == 2 and left > 0:
                 B_.cur_lane = 1
-                d_xf = self._stage_bwd(pl, stage_recs[si][1], d_xf)
+                take = min(left, len(stage_recs[si][1]))
+                d_xf = self._stage_bwd(pl, stage_recs[si][1], d_xf, take)
+                left -= take
             c_prev = xs_fulls[si].c - (W.fusions[si].geom.cout if fuse else 0)
-            if fuse:
+            if fuse and left > 0:
                 B_.sync(1, 0)                           # the fusion's gradient comes out of the slow pathway's d_cat
                 self._fusion_bwd(pl, si, fusion_recs[si], d_cat.channels(c_prev, d_cat.c - c_prev), d_xf)
+                left -= 1
             d_xs = d_cat.channels(0, c_prev)
         B_.cur_lane = 0
-        self._stem_bwd(pl, 0, stem_recs[0], d_xs)
+        if left > 0:
+            self._stem_bwd(pl, 0, stem_recs[0], d_xs)
+            left -= 1
         if NP == 2:
-            B_.cur_lane = 1
-            self._stem_bwd(pl, 1, stem_recs[1], d_xf)
+            if left > 0:
+                B_.cur_lane = 1
+                self._stem_bwd(pl, 1, stem_recs[1], d_xf)
             B_.sync(0, 1)                               # join before the optimiser
         if self.wgrad_lanes:
             B_.sync(0, 2)
@@ -1375,7 +1404,37 @@ class Engine:
         return self.fc_b_off if scope == "weights" else self.arena_numel
 
     # ---- parameter groups and frozen layers: selectors -> the arena segments of include/sfk_groups.h (HipBackend.group_table,
-    #      adam_groups / sgd_groups / grad_norm_groups).  Nothing above uses them: TrainStep knows no groups yet.
+    #      adam_groups / sgd_groups / grad_norm_groups: optim.Optimizer's grouped route) and the frozen set of the train plans
+    def set_frozen(self, freeze=()):
+        """The parameters (selectors as in param_segments) the train plans are built without: no stem or stand-alone
+        filter-gradient launch whose only output is a frozen filter's gradient, no backward below the last unit that holds a
+        trainable parameter, a grad_marks entry only for an emitted writer with a trainable element (_build_plan).  Cached
+        train plans are dropped; eval plans do not depend on the set and stay."""
+        self.frozen_keys = self.frozen_param_keys(freeze)
+        self._trainable_ranges = None
+        for key in [k for k in self._plans if k[3]]:
+            del self._plans[key]
+
+    def _w_frozen(self, L: _Layer) -> bool:
+        return bool(self.frozen_keys) and L.cb.conv_key + ".weight" in self.frozen_keys
+
+    def _unit_trainable(self, unit) -> bool:
+        """a bottleneck block, a lateral fusion or a stem of the wiring: does it hold a parameter outside the frozen set?"""
+        cbs = [unit] if isinstance(unit, arch.ConvBN) else [cb for cb in (unit.branch1, unit.conv_a, unit.conv_b, unit.conv_c)
+                                                             if cb is not None]
+        return any(k not in self.frozen_keys for cb in cbs
+                   for k in (cb.conv_key + ".weight", cb.norm_key + ".weight", cb.norm_key + ".bias"))
+
+    def _mark(self, pl: Plan, off: int, numel: int):
+        """the backward op just appended finishes gradient range [off, off + numel): recorded (Plan.grad_marks) unless every
+        element of it is frozen"""
+        if self.frozen_keys:
+            if self._trainable_ranges is None:
+                self._trainable_ranges = [(o, o + n) for k, o, n in self.param_tensors() if k not in self.frozen_keys]
+            if not any(b < off + numel and e > off for b, e in self._trainable_ranges):
+                return
+        pl.grad_marks.append((len(pl.bwd), (off, numel)))
+
     def param_tensors(self) -> List[Tuple[str, int, int]]:
         """(state_dict key, arena offset, elements with the alignment padding behind the tensor) of every parameter, in
         arena order: conv filters | FC weight | FC bias | per-layer gamma, beta (_build_params).  The ranges tile the arena."""

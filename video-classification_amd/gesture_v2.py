@@ -386,7 +386,7 @@ class Trainer(_train.Trainer):
             raise ValueError("MODEL.WEIGHT_DECAY_MODE: decoupled needs Adam; the v2 trainer runs SGD (torch has no decoupled "
                              "SGD): set WEIGHT_DECAY_MODE: l2")
         return _train.TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer, optimizer="sgd",
-                                momentum=self.momentum, **kw, **self._mix_kwargs(), **self._ema_kwargs())
+                                momentum=self.momentum, **kw, **self._mix_kwargs(), **self._ema_kwargs(), **self._group_kwargs())
 
     def mix_frame(self) -> int:
         return int(self.cfg.MODEL.INPUT_SIZE)

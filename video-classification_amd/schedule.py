@@ -94,3 +94,31 @@ def optim_kwargs(cfg, steps_per_epoch) -> dict:
     if clip > 0:
         kw["clip_grad_norm"] = clip
     return kw
+
+
+def group_kwargs(cfg) -> dict:
+    """MODEL.PARAM_GROUPS ([selector, lr_mult] or [selector, lr_mult, wd_mult] entries) and MODEL.FREEZE (selectors) as
+    TrainStep's `param_groups` / `freeze` keywords; both empty gives {}.  Only the entries' shape is checked here: the
+    selectors resolve against the engine (Engine._matcher), the multipliers' range is optim.Optimizer's to refuse."""
+    m = cfg.MODEL
+    groups, freeze = m.get("PARAM_GROUPS", []), m.get("FREEZE", [])
+    if isinstance(groups, str) or not isinstance(groups, (list, tuple)):
+        raise ValueError(f"MODEL.PARAM_GROUPS={groups!r}: a list of [selector, lr_mult] or [selector, lr_mult, wd_mult]")
+    if isinstance(freeze, str) or not isinstance(freeze, (list, tuple)):
+        raise ValueError(f"MODEL.FREEZE={freeze!r}: a list of selectors")
+    out = []
+    for g in groups:
+        ok = isinstance(g, (list, tuple)) and len(g) in (2, 3) and isinstance(g[0], str)
+        ok = ok and all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in g[1:])
+        if not ok:
+            raise ValueError(f"MODEL.PARAM_GROUPS entry {g!r}: [selector, lr_mult] or [selector, lr_mult, wd_mult]")
+        out.append((g[0],) + tuple(float(x) for x in g[1:]))
+    for s in freeze:
+        if not isinstance(s, str):
+            raise ValueError(f"MODEL.FREEZE entry {s!r}: a selector (a state_dict() key prefix, '@fresh' or '@pretrained')")
+    kw = {}
+    if out:
+        kw["param_groups"] = out
+    if freeze:
+        kw["freeze"] = [str(s) for s in freeze]
+    return kw

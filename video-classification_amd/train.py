@@ -48,7 +48,8 @@ class TrainStep:
                  reducer: Optional[sdist.GradReducer] = None, overlap_segments: int = 6, optimizer: str = "adam",
                  momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False, lr_table=None,
                  weight_decay: float = 0.0, decay_mode: str = "none", decay_scope: str = "weights",
-                 clip_grad_norm: float = 0.0, label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = False):
+                 clip_grad_norm: float = 0.0, label_smoothing: float = 0.0, ema_decay: float = 0.0, ema_warmup: bool = False,
+                 param_groups=(), freeze=(), trunk: Optional["torch.cuda.Stream"] = None):
         """optimizer 'adam' (train.py:182: lr, betas, eps) or 'sgd' (the v2 trainer, new_feature_test.py:832: lr, momentum,
         dampening, nesterov; one sfk_sgd launch over the arena, never split beside the last kernel).
 
@@ -72,7 +73,22 @@ class TrainStep:
         1 every rank averages its own identical copy; nothing is communicated.  The average is not checkpointed separately:
         self.ema.applied() evaluates and saves it.  Eager steps only: with use_graph the keyword is refused (DESIGN.md
         section 20 -- the captured step with the launch in it ended its capture in a host segmentation fault on the GPU, the
-        cause is not known, and the captured route was taken out)."""
+        cause is not known, and the captured route was taken out).
+
+        param_groups, freeze (include/sfk_groups.h): both empty, the step issues exactly the launches
+        above.  param_groups is a sequence of (selector, lr_mult) or (selector, lr_mult, wd_mult) in priority order, freeze a
+        sequence of selectors; a selector is a state_dict() key prefix ('blocks.1.'), '@fresh' or '@pretrained' (the keys a
+        pretrained load left untouched / filled); the first match wins and freeze beats groups.  The optimizer launch is then
+        sfk_adam_groups / sfk_sgd_groups: group j's rate at step s is lr_table[s] * lr_mult_j, its decay weight_decay *
+        wd_mult_j, a frozen tensor keeps its bits (moments included) and its gradient does not count in the clipped norm.  The
+        engine's train plans are built for the frozen set (Engine.set_frozen): no filter-gradient launch whose only output
+        is a frozen filter's gradient, and no backward below the last unit that holds a trainable parameter.  The forward is
+        not pruned: frozen BatchNorm layers still normalise with batch statistics and update their running ones, as torch does
+        for requires_grad = False under .train().  The frozen set is the ENGINE's: a TrainStep with another set on the same
+        engine re-sets it, and a step that finds another step's set when it is called puts its own back first (the train plan
+        is rebuilt, so alternating two such steps rebuilds a plan per switch) -- a step never runs on plans pruned for another
+        set.  Eager steps only: with use_graph the keywords are refused, as ema_decay is
+        and for the same reason (the captured grouped step ended its capture in the same host segmentation fault)."""
         self.eng = engine
         ema_decay = float(ema_decay)
         if not 0.0 <= ema_decay < 1.0:
@@ -80,8 +96,20 @@ class TrainStep:
         self.label_smoothing = float(label_smoothing)
         if not 0.0 <= self.label_smoothing < 1.0:
             raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+        param_groups, freeze = tuple(param_groups), tuple(freeze)
+        captured = use_graph and not (reducer is not None and reducer.active) and engine.device.type == "cuda"
+        if captured and (param_groups or freeze):        # before any state, table or plan exists
+            raise ValueError("param_groups / freeze need an eager step: the captured step (use_graph=True) with the "
+                             "sfk_adam_groups / sfk_sgd_groups launch in it is not offered (DESIGN.md section 18)")
         opt = self.opt = Optimizer(engine, optimizer, lr, betas, eps, momentum, dampening, nesterov, lr_table, weight_decay,
-                                   decay_mode, decay_scope, clip_grad_norm)      # validates the keywords; allocates no state
+                                   decay_mode, decay_scope, clip_grad_norm, param_groups, freeze)   # validates; allocates no state
+        self.last_lrs = opt.last_lrs
+        # the train plans are built for this step's frozen set (no launch for a frozen filter's gradient, no backward below the
+        # last trainable unit); a step with another set on the same engine re-sets it, which drops the cached train plans
+        self.freeze = freeze
+        self._frozen = engine.frozen_param_keys(freeze) if (freeze or engine.frozen_keys) else frozenset()
+        if self._frozen != engine.frozen_keys:
+            engine.set_frozen(freeze)
         self.optimizer, self.momentum, self.hp, self.lr_table = opt.optimizer, opt.momentum, opt.hp, opt.lr_table
         self.decay_mode, self.clip_grad_norm, self.last_lr = opt.decay_mode, opt.clip_grad_norm, opt.last_lr
         self.reducer = reducer
@@ -111,8 +139,11 @@ class TrainStep:
         # HIGH-priority stream of its own so that its next kernel gets CUs ahead of the filter-gradient lanes' backlog
         # (measured +0.8 % clips/s).  The caller's stream waits for the step as before.
         self._trunk = None
+        # trunk: a stream to use for it instead of a new one (steps that take turns on one engine share one: every new stream
+        # takes another of the process's few hardware queues, and a trunk that shares a queue with a lane serialises with it)
         if dev.type == "cuda" and not self.use_graph and engine.options.trunk_priority:
-            self._trunk = torch.cuda.Stream(dev, priority=-1)
+            self._trunk = trunk if trunk is not None else torch.cuda.Stream(dev, priority=-1)
+        self.trunk = self._trunk
 
     def reset_meters(self):
         self.loss_sum.zero_()
@@ -191,6 +222,8 @@ class TrainStep:
         """mix: None, or the (N, 8) float32 device table of the batch's mix rows (input_pipeline.ClipMix.load): the loss takes
         its soft target from it.  Its CONTENTS are read when the launch runs; its address is part of the cache key."""
         eng = self.eng
+        if eng.frozen_keys != self._frozen:  # another TrainStep set the engine's frozen set since: this step's plans are gone
+            eng.set_frozen(self.freeze)
         x_slow = eng.input_view(x_slow)      # res2d: the (N, C, T, H, W) view of its stacked-frames input; else x as it is
         pl = eng._plan_for(x_slow, x_fast, slow_t_index, True)
         if mix is not None:
@@ -950,6 +983,10 @@ class Trainer:
             if self.ema_decay > 0:
                 raise ValueError("MODEL.EMA_DECAY needs the engine's parameter arena and its sfk_ema_update launch: MODEL.NAME res2d "
                                  "with the torch backend is host plumbing (torch.optim.Adam); use RES2D_BACKEND = 'engine'")
+            if self._group_kwargs():
+                raise ValueError("MODEL.PARAM_GROUPS / FREEZE need the engine's parameter arena and its sfk_adam_groups launch: "
+                                 "MODEL.NAME res2d with the torch backend is host plumbing (torch.optim.Adam); use RES2D_BACKEND = "
+                                 "'engine'")
             self.step = TorchStep(self.model, lr=cfg.MODEL.LR)
         else:
             reducer = sdist.GradReducer(eng.G, bucket_mb=cfg.DIST.BUCKET_MB) if self.world > 1 else None
@@ -981,6 +1018,12 @@ class Trainer:
         from .schedule import optim_kwargs
         return optim_kwargs(self.cfg, self.steps_per_epoch)
 
+    def _group_kwargs(self) -> dict:
+        """MODEL.PARAM_GROUPS / FREEZE as TrainStep keywords ({} at the defaults).  The step is built after init_model's
+        load_pretrained, so '@fresh' and '@pretrained' resolve against that load"""
+        from .schedule import group_kwargs
+        return group_kwargs(self.cfg)
+
     def _mix_kwargs(self) -> dict:
         """MODEL.LABEL_SMOOTHING as a TrainStep keyword ({} at the default)"""
         return {"label_smoothing": self.label_smoothing} if self.label_smoothing > 0 else {}
@@ -1008,7 +1051,7 @@ class Trainer:
 
     def _make_step(self, eng, use_graph, reducer):
         return TrainStep(eng, lr=self.cfg.MODEL.LR, use_graph=use_graph, reducer=reducer, **self._optim_kwargs(),
-                         **self._mix_kwargs(), **self._ema_kwargs())
+                         **self._mix_kwargs(), **self._ema_kwargs(), **self._group_kwargs())
 
     def _reference_datasets(self):
         try:
@@ -1145,7 +1188,11 @@ class Trainer:
         print(f'Train Accuracy: {round(correct / max(seen, 1), 3)}. ({correct} / {seen})')
         if getattr(self.step, "hp", False):              # the scheduled step: its last rate and gradient norm, read once an epoch
             gn = self.step.grad_norm
-            print(f'lr: {self.step.last_lr():.6g}' + ('' if gn is None else f', grad_norm: {float(gn[0]):.4g}'))
+            if getattr(self.step.opt, "grouped", False):     # one rate per group: the unmatched rest, then PARAM_GROUPS' order
+                rates = 'lr: [' + ', '.join(f'{r:.6g}' for r in self.step.last_lrs()) + ']'
+            else:
+                rates = f'lr: {self.step.last_lr():.6g}'
+            print(rates + ('' if gn is None else f', grad_norm: {float(gn[0]):.4g}'))
         return loss_avg, correct / max(seen, 1)
 
     def _evaluates_average(self) -> bool:
