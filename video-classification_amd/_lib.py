@@ -325,6 +325,37 @@ class _RoiRaggedDesc(C.Structure):
                 ("dc", C.c_int64), ("dh", C.c_int64), ("c_off", C.c_int32)]
 
 
+class _RoiWarpDesc(C.Structure):
+    """include/sfk_roi_warp.h sfk_roi_warp_desc: sfk_roi_desc with the per-clip matrix table (n, 6) float32 in place of crop and
+    pad"""
+    _fields_ = [("struct_size", C.c_uint32), ("antialias", C.c_int32), ("src", C.c_void_p), ("sn", C.c_int64),
+                ("st", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64), ("sc", C.c_int64), ("n", C.c_int32),
+                ("t", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("out_h", C.c_int32),
+                ("out_w", C.c_int32), ("lut", C.c_void_p), ("box", C.c_void_p), ("warp", C.c_void_p),
+                ("dst_dtype", C.c_int32), ("reserved0", C.c_int32), ("dst", C.c_void_p), ("dn", C.c_int64), ("dt", C.c_int64),
+                ("dc", C.c_int64), ("dh", C.c_int64), ("c_off", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class _RoiPoolWarpDesc(C.Structure):
+    """include/sfk_roi_warp.h sfk_roi_pool_warp_desc: sfk_roi_pool_desc with warp (n, 6) float32 in place of crop and pad"""
+    _fields_ = [("struct_size", C.c_uint32), ("antialias", C.c_int32), ("pool", C.c_void_p), ("frame_stride", C.c_int64),
+                ("row_stride", C.c_int64), ("pixel_pitch", C.c_int32), ("frames", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("c0", C.c_int32), ("c", C.c_int32), ("n", C.c_int32), ("t", C.c_int32), ("index", C.c_void_p),
+                ("lut", C.c_void_p), ("box", C.c_void_p), ("warp", C.c_void_p), ("fill", C.c_int32),
+                ("out_h", C.c_int32), ("out_w", C.c_int32), ("dst_dtype", C.c_int32), ("dst", C.c_void_p), ("dn", C.c_int64),
+                ("dt", C.c_int64), ("dc", C.c_int64), ("dh", C.c_int64), ("c_off", C.c_int32)]
+
+
+class _RoiRaggedWarpDesc(C.Structure):
+    """include/sfk_roi_warp.h sfk_roi_ragged_warp_desc: sfk_roi_ragged_desc with warp (n, 6) float32 in place of crop and pad"""
+    _fields_ = [("struct_size", C.c_uint32), ("antialias", C.c_int32), ("arena", C.c_void_p), ("arena_bytes", C.c_int64),
+                ("pixel_pitch", C.c_int32), ("c0", C.c_int32), ("c", C.c_int32), ("n", C.c_int32), ("t", C.c_int32),
+                ("max_h", C.c_int32), ("max_w", C.c_int32), ("offset", C.c_void_p), ("hw", C.c_void_p), ("lut", C.c_void_p),
+                ("box", C.c_void_p), ("warp", C.c_void_p), ("fill", C.c_int32), ("out_h", C.c_int32),
+                ("out_w", C.c_int32), ("dst_dtype", C.c_int32), ("dst", C.c_void_p), ("dn", C.c_int64), ("dt", C.c_int64),
+                ("dc", C.c_int64), ("dh", C.c_int64), ("c_off", C.c_int32)]
+
+
 class _ResizeDesc(C.Structure):
     """include/sfk_resize.h sfk_resize_desc: frame f is the contiguous HWC bytes src[offset[f] ...] of hw[f] = (h, w) pixels
     and c channels; its padded, cubic-resized (size, size, c) frame lands at out + f*out_frame_stride"""
@@ -553,6 +584,17 @@ SIGNATURES_WARP = {
     "sfk_u8_pool_gather_warp": [C.POINTER(_PoolWarpDesc), _PV],
     "sfk_warp_fallback_tiles": [_I32, _I32, _I32, _I32, _PF],
 }
+# include/sfk_roi_warp.h: the v2 part-box resize sampled through a per-clip affine matrix (the three sources of sfk_roi_resize*),
+# same library, its own header and version
+ROI_WARP_ABI_VERSION = 1   # include/sfk_roi_warp.h SFK_ROI_WARP_ABI_VERSION
+ROI_WARP_TILE_H, ROI_WARP_TILE_W = 16, 32   # include/sfk_roi_warp.h SFK_ROI_WARP_TILE_H / _W: the output tile of one workgroup
+ROI_WARP_LDS_BYTES = 24 * 1024              # include/sfk_roi_warp.h SFK_ROI_WARP_LDS_BYTES
+SIGNATURES_ROI_WARP = {
+    "sfk_roi_warp_abi_version": [],
+    "sfk_roi_resize_warp": [C.POINTER(_RoiWarpDesc), _PV],
+    "sfk_roi_resize_pool_warp": [C.POINTER(_RoiPoolWarpDesc), _PV],
+    "sfk_roi_resize_ragged_warp": [C.POINTER(_RoiRaggedWarpDesc), _PV],
+}
 _RESTYPE = {"sfk_status_string": C.c_char_p, "sfk_conv_wgrad_route": C.c_int64, "sfk_stem_conv_fwd_route": C.c_int64, "sfk_stem_conv_wgrad_route": C.c_int64, "sfk_groups_prepare": C.c_int64, "sfk_conv_wgrad_workspace_bytes": C.c_int64,
             "sfk_color_jitter_workspace_bytes": C.c_int64}
 
@@ -654,6 +696,24 @@ def new_roi_ragged_desc() -> "_RoiRaggedDesc":
     return d
 
 
+def new_roi_warp_desc() -> "_RoiWarpDesc":
+    d = _RoiWarpDesc()
+    d.struct_size = C.sizeof(_RoiWarpDesc)
+    return d
+
+
+def new_roi_pool_warp_desc() -> "_RoiPoolWarpDesc":
+    d = _RoiPoolWarpDesc()
+    d.struct_size = C.sizeof(_RoiPoolWarpDesc)
+    return d
+
+
+def new_roi_ragged_warp_desc() -> "_RoiRaggedWarpDesc":
+    d = _RoiRaggedWarpDesc()
+    d.struct_size = C.sizeof(_RoiRaggedWarpDesc)
+    return d
+
+
 def new_optim_hp() -> "_OptimHp":
     d = _OptimHp()
     d.struct_size = C.sizeof(_OptimHp)
@@ -698,7 +758,7 @@ def load(path: str = LIB_PATH) -> C.CDLL:
     lib = C.CDLL(path)
     for table in (SIGNATURES, SIGNATURES_STEM2D, SIGNATURES_U8STEM, SIGNATURES_V2, SIGNATURES_AUG, SIGNATURES_POOL,
                   SIGNATURES_RESIZE, SIGNATURES_RESIDENT, SIGNATURES_ROI_POOL, SIGNATURES_ROI_RAGGED, SIGNATURES_U8STEM_POOL,
-                  SIGNATURES_OPTIM, SIGNATURES_GROUPS, SIGNATURES_MIX, SIGNATURES_EMA, SIGNATURES_WARP):
+                  SIGNATURES_OPTIM, SIGNATURES_GROUPS, SIGNATURES_MIX, SIGNATURES_EMA, SIGNATURES_WARP, SIGNATURES_ROI_WARP):
         for name, argtypes in table.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is not exported
             fn.argtypes = argtypes
@@ -735,6 +795,8 @@ def load(path: str = LIB_PATH) -> C.CDLL:
         raise SfkError(f"libsfk ema ABI version mismatch: library {lib.sfk_ema_abi_version()}, binding {EMA_ABI_VERSION}")
     if lib.sfk_warp_abi_version() != WARP_ABI_VERSION:
         raise SfkError(f"libsfk warp ABI version mismatch: library {lib.sfk_warp_abi_version()}, binding {WARP_ABI_VERSION}")
+    if lib.sfk_roi_warp_abi_version() != ROI_WARP_ABI_VERSION:
+        raise SfkError(f"libsfk roi_warp ABI version mismatch: library {lib.sfk_roi_warp_abi_version()}, binding {ROI_WARP_ABI_VERSION}")
     t = new_tuning()
     if lib.sfk_default_tuning(C.byref(t)) != 0:
         raise SfkError("sfk_default_tuning refused this binding's sfk_tuning layout")
@@ -1576,6 +1638,64 @@ class HipBackend:
         d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
         d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
         return self._plain("sfk_roi_resize_ragged", C.byref(d), keep=(d, arena, offset, hw, lut, box, out, crop))
+
+    @staticmethod
+    def _roi_warp_common(d, n, t, c, lut, box, warp, out, antialias, c_off):
+        """what the three sfk_roi_warp descriptors share: the assertions on lut, box, warp and out, and those fields of d"""
+        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
+        assert box.dtype == torch.int32 and box.is_contiguous() and tuple(box.shape) == (n, 4)
+        assert warp.dtype == torch.float32 and warp.is_contiguous() and tuple(warp.shape) == (n, WARP_ROW_FLOATS)
+        assert warp.device == out.device
+        assert out.dim() == 5 and out.stride(4) == 1 and out.shape[0] == n and out.shape[1] == t and 0 <= c_off and c_off + c <= out.shape[2]
+        d.antialias, d.lut, d.box, d.warp = 1 if antialias else 0, lut.data_ptr(), box.data_ptr(), warp.data_ptr()
+        d.out_h, d.out_w = out.shape[3], out.shape[4]
+        d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
+        d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
+        return d
+
+    def roi_resize_warp(self, src, lut, box, warp, out, antialias: bool, c_off: int = 0):
+        """sfk_roi_resize_warp (include/sfk_roi_warp.h): ``roi_resize`` sampled through a matrix per clip -- warp (N,6) float32
+        (a, b, c, d, e, f) on the device, read when the launch runs: out[n,t,ch,y,x] is the resize's own interpolant at the
+        position (a x + b y + c, d x + e y + f) of the resized image, zero outside it."""
+        n, t, h, w, c = src.shape
+        assert src.dtype == torch.uint8
+        d = self._roi_warp_common(new_roi_warp_desc(), n, t, c, lut, box, warp, out, antialias, c_off)
+        d.src = src.data_ptr()
+        d.sn, d.st, d.sh, d.sw, d.sc = src.stride()
+        d.n, d.t, d.h, d.w, d.c = n, t, h, w, c
+        return self._plain("sfk_roi_resize_warp", C.byref(d), keep=(d, src, lut, box, warp, out))
+
+    def roi_resize_pool_warp(self, pool, index, lut, fill: int, box, warp, out, antialias: bool, c0: int = 0,
+                             c: Optional[int] = None, c_off: int = 0):
+        """sfk_roi_resize_pool_warp (include/sfk_roi_warp.h): ``roi_resize_pool`` sampled through warp (N,6) float32 as
+        ``roi_resize_warp`` samples; a frame whose index is outside [0, F) is the constant image of byte fill."""
+        f, h, w, p = pool.shape
+        c = p - c0 if c is None else c
+        assert pool.dtype == torch.uint8 and pool.stride(3) == 1 and 0 <= c0 and 0 < c and c0 + c <= p
+        assert index.dtype == torch.int32 and index.dim() == 2 and index.is_contiguous()
+        n, t = index.shape
+        d = self._roi_warp_common(new_roi_pool_warp_desc(), n, t, c, lut, box, warp, out, antialias, c_off)
+        d.pool, d.index = pool.data_ptr(), index.data_ptr()
+        d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
+        d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
+        return self._plain("sfk_roi_resize_pool_warp", C.byref(d), keep=(d, pool, index, lut, box, warp, out))
+
+    def roi_resize_ragged_warp(self, arena, offset, hw, lut, fill: int, box, warp, out, antialias: bool, pitch: int = 7,
+                               c0: int = 0, c: Optional[int] = None, c_off: int = 0, max_hw=None):
+        """sfk_roi_resize_ragged_warp (include/sfk_roi_warp.h): ``roi_resize_ragged`` sampled through warp (N,6) float32 as
+        ``roi_resize_warp`` samples; a frame that does not lie in the arena whole is the constant image of byte fill."""
+        c = pitch - c0 if c is None else c
+        assert arena.dtype == torch.uint8 and arena.dim() == 1 and arena.is_contiguous() and 0 <= c0 and 0 < c and c0 + c <= pitch
+        assert offset.dtype == torch.int64 and offset.dim() == 2 and offset.is_contiguous()
+        n, t = offset.shape
+        assert hw.dtype == torch.int32 and hw.is_contiguous() and tuple(hw.shape) == (n, 2)
+        if max_hw is None:
+            max_hw = tuple(max(int(v), 1) for v in hw.max(0).values.tolist())
+        d = self._roi_warp_common(new_roi_ragged_warp_desc(), n, t, c, lut, box, warp, out, antialias, c_off)
+        d.arena, d.arena_bytes, d.offset, d.hw = arena.data_ptr(), arena.numel(), offset.data_ptr(), hw.data_ptr()
+        d.pixel_pitch, d.c0, d.c, d.n, d.t, d.fill = int(pitch), c0, c, n, t, int(fill)
+        d.max_h, d.max_w = int(max_hw[0]), int(max_hw[1])
+        return self._plain("sfk_roi_resize_ragged_warp", C.byref(d), keep=(d, arena, offset, hw, lut, box, warp, out))
 
     def u8_pad_resize_cubic(self, src, offset, hw, out, size: int, max_side: int, fill: int):
         """sfk_u8_pad_resize_cubic (include/sfk_resize.h): src 1-D uint8, the frames' HWC bytes; offset (F,) int64 and hw (F, 2)

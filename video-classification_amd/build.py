@@ -8,7 +8,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsfk.so")
 SOURCES = ["conv_igemm.hip", "conv_igemm_p8.hip", "conv_halo.hip", "conv_pw.hip", "conv_wgrad.hip", "conv_wgrad_p8.hip", "conv_wgrad_band.hip", "stem_conv.hip", "bn.hip", "bn_tail.hip", "pool_head.hip",
-           "optim_misc.hip", "eval_input.hip", "stem2d.hip", "roi_resize.hip", "sgd.hip", "color_jitter.hip", "u8_pool_gather.hip", "pad_resize.hip", "optim_sched.hip", "optim_groups.hip", "clip_mix.hip", "loss_mix.hip", "ema.hip", "u8_pool_warp.hip"]
+           "optim_misc.hip", "eval_input.hip", "stem2d.hip", "roi_resize.hip", "sgd.hip", "color_jitter.hip", "u8_pool_gather.hip", "pad_resize.hip", "optim_sched.hip", "optim_groups.hip", "clip_mix.hip", "loss_mix.hip", "ema.hip", "u8_pool_warp.hip", "roi_warp.hip"]
 
 
 def _newer(a, b):
@@ -29,7 +29,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
             os.path.join(ROOT, "include", "sfk_roi_ragged.h"), os.path.join(ROOT, "include", "sfk_u8stem_pool.h"),
             os.path.join(ROOT, "include", "sfk_optim.h"), os.path.join(ROOT, "include", "sfk_groups.h"),
             os.path.join(ROOT, "include", "sfk_mix.h"), os.path.join(ROOT, "include", "sfk_ema.h"),
-            os.path.join(ROOT, "include", "sfk_warp.h"), os.path.join(CSRC, "optim_elem.h"), os.path.join(CSRC, "stem_src.h")]
+            os.path.join(ROOT, "include", "sfk_warp.h"), os.path.join(ROOT, "include", "sfk_roi_warp.h"),
+            os.path.join(CSRC, "roi_common.h"), os.path.join(CSRC, "optim_elem.h"), os.path.join(CSRC, "stem_src.h")]
     flags = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
     flags += os.environ.get("SFK_EXTRA_FLAGS", "").split()          # experiment builds (tools/), with SFK_LIB_OUT
 

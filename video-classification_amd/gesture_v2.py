@@ -125,7 +125,8 @@ class ChalearnGestureFrames(torch.utils.data.Dataset):
     labels: the reference's ``Labels(cfg).from_set(name_of_set)`` list of (rgb path, depth path, 1-based label).  Items:
     {'frames_u8': (T, H, W, 7) uint8 [R, G, B, U, V, F0, F1], 'box': int32 (x1, y1, x2, y2) clamped to the frame,
     'label': label - 1}; a list of them for sampling='uniform'.  read_video(path, channels, indices, format) -> (T, C, H, W)
-    uint8 is injectable (default: decord, as the reference)."""
+    uint8 is injectable (default: decord, as the reference).  Under MODEL.AFFINE a random train clip also carries 'warp':
+    (6,) float32, the row of ``input_pipeline.draw_affine`` on the resized S x S clip (``train.draw_crop_or_warp``)."""
 
     def __init__(self, cfg, name_of_set: str, parts, sampling: str, labels, read_video: Optional[Callable] = None):
         assert name_of_set in ("train", "test", "valid")
@@ -141,6 +142,8 @@ class ChalearnGestureFrames(torch.utils.data.Dataset):
         self.rng = random
         # MODEL.COLOR_JITTER: the train set's random clips carry their ColorJitter draws (input_pipeline.draw_color_jitter)
         self.jitter = _train.jitter_ranges(cfg) if name_of_set == "train" else None
+        # MODEL.AFFINE: they carry their warp row too, drawn before the jitter row
+        self.affine_cfg = cfg if name_of_set == "train" and _train.affine_ranges(cfg) is not None else None
 
     def __len__(self):
         return len(self.label_list)
@@ -163,6 +166,8 @@ class ChalearnGestureFrames(torch.utils.data.Dataset):
         _, _, h, w = x.shape
         box = self.clip_box(boxes, clip_indices, h, w)
         item = {"frames_u8": x.permute(0, 2, 3, 1).contiguous(), "box": box, "label": label - 1}
+        if self.affine_cfg is not None and self.sampling == "random":
+            item["warp"] = _train.draw_crop_or_warp(self.affine_cfg, int(self.affine_cfg.MODEL.INPUT_SIZE))[1]
         if self.jitter is not None and self.sampling == "random":
             from .input_pipeline import draw_color_jitter
             item["jitter"] = draw_color_jitter(1, *self.jitter)[0]
@@ -272,6 +277,8 @@ class SyntheticGesture(torch.utils.data.Dataset):
         b = self._frame_boxes(i)[idx]
         box = torch.stack([b[:, 0].min(), b[:, 1].min(), b[:, 2].max(), b[:, 3].max()])
         item = {"frames_u8": self._video_item(i, idx)["frames_pool"], "box": box, "label": self.labels[i]}
+        if _train.affine_ranges(self.cfg) is not None:           # MODEL.AFFINE: the warp row, drawn before the jitter row
+            item["warp"] = _train.draw_crop_or_warp(self.cfg, int(self.cfg.MODEL.INPUT_SIZE))[1]
         ranges = _train.jitter_ranges(self.cfg)
         if ranges is not None:
             from .input_pipeline import draw_color_jitter
@@ -286,6 +293,8 @@ class SyntheticGesture(torch.utils.data.Dataset):
         x2 = int(torch.randint(x1 + self.min_box, self.w + 1, (1,), generator=g))
         y2 = int(torch.randint(y1 + self.min_box, self.h + 1, (1,), generator=g))
         item = {"frames_u8": frames, "box": torch.tensor([x1, y1, x2, y2], dtype=torch.int32), "label": self.labels[i]}
+        if self.name == "train" and _train.affine_ranges(self.cfg) is not None:
+            item["warp"] = _train.draw_crop_or_warp(self.cfg, int(self.cfg.MODEL.INPUT_SIZE), generator=g)[1]
         ranges = _train.jitter_ranges(self.cfg) if self.name == "train" else None
         if ranges is not None:
             from .input_pipeline import draw_color_jitter
@@ -311,6 +320,7 @@ class ModelManager(_train.ModelManager):
         self._roi = None
         self._jit = None
         self._mix = None
+        self.train_affine = False                        # Trainer.train_epoch under MODEL.AFFINE: a float TRAIN batch is refused
         self.arch = "ref"
         self.init_model = self._init_v2_model
         self.prepare_data = self._prepare_v2_data
@@ -338,8 +348,10 @@ class ModelManager(_train.ModelManager):
         return self._roi
 
     def _prepare_v2_data(self, batch):
-        """-> [slow (N, 5, T, S, S), fast (N, 2, T, S, S)], labels.  The uint8 batch {'frames_u8', 'box'[, 'crop']} is
-        resized on the device into one (N, T, 7, S, S) tensor whose channel slices are the two pathways (no copy); a
+        """-> [slow (N, 5, T, S, S), fast (N, 2, T, S, S)], labels.  The uint8 batch {'frames_u8', 'box'[, 'crop' | 'warp']} is
+        resized on the device into one (N, T, 7, S, S) tensor whose channel slices are the two pathways (no copy) -- with
+        'warp' (MODEL.AFFINE) the resize is sampled through each clip's matrix in that same single launch
+        (include/sfk_roi_warp.h), then jittered, then mixed; the float batch with 'warp' is refused: it has no uint8 frames; a
         'clip_v2' batch (input_pipeline.ResidentGestureSet, MODEL.RESIDENT_TRAIN) already is that tensor; the
         float batch {'rgb', 'uv', 'flow'} is the reference's permute + cat (:761-769).  An optional 'jitter' (N, 8) entry
         (input_pipeline.draw_color_jitter) applies ColorJitter to the R, G, B planes on the device: after the resize and
@@ -348,12 +360,17 @@ class ModelManager(_train.ModelManager):
         input_pipeline.ClipMix.load) then mixes the finished float clip with its partner clip (_mix_clip)."""
         y = self._h2d(batch["label"])
         if "clip_v2" in batch or "frames_u8" in batch:
-            x = batch["clip_v2"] if "clip_v2" in batch else self.roi_resize()(batch["frames_u8"], batch["box"], batch.get("crop"))
+            x = (batch["clip_v2"] if "clip_v2" in batch else
+                 self.roi_resize()(batch["frames_u8"], batch["box"], batch.get("crop"), warp=batch.get("warp")))
             if "jitter" in batch:
                 self.color_jitter()(x, batch["jitter"])
             x = self._mix_clip(x, batch)
             x = torch.permute(x, [0, 2, 1, 3, 4])
             return [x[:, 0:5], x[:, 5:7]], y
+        if "warp" in batch or self.train_affine:
+            raise ValueError("the float batch {'rgb', 'uv', 'flow'} is already resized on the host: there are no uint8 frames for "
+                             "the device-side affine sampling (MODEL.AFFINE) to read; feed 'frames_u8' and 'box', use "
+                             "MODEL.RESIDENT_TRAIN, or turn MODEL.AFFINE off")
         rgb, uv, flow = (self._h2d(batch[k]) for k in ("rgb", "uv", "flow"))
         if "jitter" in batch:
             rgb = self.color_jitter()(self._own(rgb, batch["rgb"]), batch["jitter"])
@@ -391,6 +408,15 @@ class Trainer(_train.Trainer):
     def mix_frame(self) -> int:
         return int(self.cfg.MODEL.INPUT_SIZE)
 
+    def train_epoch(self):
+        """MODEL.AFFINE: the train batches must be ones the device can sample (uint8 frames or the resident set); evaluation
+        is unchanged"""
+        self.mm.train_affine = _train.affine_ranges(self.cfg) is not None
+        try:
+            return super().train_epoch()
+        finally:
+            self.mm.train_affine = False
+
     def _offers_resident(self, train_set) -> bool:
         from .input_pipeline import GESTURE_METHODS, offers_resident
         return offers_resident(train_set, GESTURE_METHODS)
@@ -402,7 +428,8 @@ class Trainer(_train.Trainer):
         return ResidentGestureSet(train_set, self.cfg, self.device, backend, batch_size=self.batch_size,
                                   drop_last=self.train_drop_last, num_workers=self.num_workers,
                                   jitter=_train.jitter_ranges(self.cfg),
-                                  store=str(self.cfg.MODEL.get("RESIDENT_STORE", "frame")))
+                                  store=str(self.cfg.MODEL.get("RESIDENT_STORE", "frame")),
+                                  affine=_train.affine_ranges(self.cfg))
 
     def _reference_datasets(self):
         try:

@@ -432,7 +432,7 @@ class FramePool:
         self.bytes_uploaded = 0
         self._resize = {}                       # (size, channels) -> the PadResize of add_raw
         self._byte_lut = None                   # roi_gather's table, made at its first call
-        self._tables = {}                       # persistent device tables: clip's 'index' / 'crop' (int32), gather's 'warp' (float32) -> flat buffer
+        self._tables = {}                       # persistent device tables: clip's 'index' / 'crop' (int32), gather's 'warp' and roi_gather's 'roi_warp' (float32) -> flat buffer
         self.capacity = None if capacity is None else int(capacity)
         if self.capacity is not None and self.capacity <= 0:
             raise ValueError(f"FramePool: capacity {capacity} frames")
@@ -612,12 +612,16 @@ class FramePool:
 
     def roi_gather(self, index_rows: torch.Tensor, box: torch.Tensor, size: int, out_dtype: torch.dtype = torch.float32,
                    antialias: bool = True, crop: Optional[torch.Tensor] = None, padding: Optional[int] = None,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, warp: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(N, T) arena slots (or -1) and boxes (N, 4) = (x1, y1, x2, y2) -> the (N, T, c, size, size) clips ``RoiResize``
         would write from the materialised frames (a -1 frame materialised as bytes of ``fill``), through ``byte_lut()``; crop
         (N, 2) int32 (top, left): with RandomCrop(size, padding) after the resize (padding defaults to size // 10, as
         RoiResize's).  The same liveness check of every index as ``gather``; ONE ``sfk_roi_resize_pool`` launch on the
-        current stream; the H2D of the index, box and crop tables only."""
+        current stream; the H2D of the index, box and crop tables only.  warp (N, 6) float32 (``draw_affine``) instead of
+        crop: ONE ``sfk_roi_resize_pool_warp`` launch (include/sfk_roi_warp.h) instead, the validated rows written into the
+        pool's persistent 'roi_warp' table; crop and warp together is a ValueError."""
+        if crop is not None and warp is not None:
+            raise ValueError("roi_gather: crop and warp together (a warp row carries RandomCrop's translation itself)")
         idx = torch.as_tensor(index_rows, dtype=torch.int32).contiguous()
         assert idx.dim() == 2 and idx.numel() > 0 and self.arena is not None
         ok = torch.zeros(self.arena.shape[0] + 1, dtype=torch.bool)      # the last entry stands for -1
@@ -640,6 +644,12 @@ class FramePool:
         if out is None:
             out = torch.empty(n, idx.shape[1], self.arena.shape[3], size, size, dtype=out_dtype, device=self.device)
         stream = stream_of(self.device)
+        if warp is not None:
+            rows = validate_warp_rows(warp)
+            assert tuple(rows.shape) == (n, 6), tuple(rows.shape)
+            self.be.roi_resize_pool_warp(self.arena, h2d(idx, self.device), self._byte_lut, self.fill, h2d(box, self.device),
+                                         self._table("roi_warp", rows), out, bool(antialias))(stream)
+            return out
         self.be.roi_resize_pool(self.arena, h2d(idx, self.device), self._byte_lut, self.fill, h2d(box, self.device), out,
                                 bool(antialias), crop, pad)(stream)
         return out
@@ -668,6 +678,7 @@ class BoxArena:
         self.pitch: Optional[int] = None        # P: that of the first block, and of every block after it
         self.bytes_uploaded = 0
         self._byte_lut = None                   # roi_gather's table, made at its first call
+        self._warp_table = None                 # roi_gather's persistent device table of warp rows, grown to the largest seen
 
     @classmethod
     def _span(cls, shape) -> int:
@@ -741,12 +752,18 @@ class BoxArena:
 
     def roi_gather(self, offset_rows: torch.Tensor, hw: torch.Tensor, box: torch.Tensor, size: int,
                    out_dtype: torch.dtype = torch.float32, antialias: bool = True, crop: Optional[torch.Tensor] = None,
-                   padding: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   padding: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                   warp: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(N, T) byte offsets (or -1), the clips' stored rectangles hw (N, 2) = (h_n, w_n) and their boxes (N, 4) =
         (x1, y1, x2, y2) IN those rectangles -> the (N, T, P, size, size) clips ``RoiResize`` would write from those frames (a
         -1 frame as bytes of ``fill``), through ``byte_lut()``; crop and padding as ``FramePool.roi_gather``'s.  The host
         checks of ``_check_table`` first; then ONE ``sfk_roi_resize_ragged`` launch on the current stream, its tile sized from
-        the largest rectangle of THIS batch, and the H2D of the offset, hw, box and crop tables only."""
+        the largest rectangle of THIS batch, and the H2D of the offset, hw, box and crop tables only.  warp (N, 6) float32
+        (``draw_affine``) instead of crop: ONE ``sfk_roi_resize_ragged_warp`` launch (include/sfk_roi_warp.h) instead, the
+        validated rows written into the arena's persistent warp table; crop and warp together is a ValueError.  The matrix
+        lives in the coordinates of the RESIZED image, so the rectangle's origin, which translates the box, does not touch it."""
+        if crop is not None and warp is not None:
+            raise ValueError("roi_gather: crop and warp together (a warp row carries RandomCrop's translation itself)")
         off = torch.as_tensor(offset_rows, dtype=torch.int64).contiguous()
         assert off.dim() == 2 and off.numel() > 0 and self.arena is not None
         n, size = off.shape[0], int(size)
@@ -765,6 +782,19 @@ class BoxArena:
         if out is None:
             out = torch.empty(n, off.shape[1], pitch, size, size, dtype=out_dtype, device=self.device)
         stream = stream_of(self.device)
+        if warp is not None:
+            rows = validate_warp_rows(warp)
+            assert tuple(rows.shape) == (n, 6), tuple(rows.shape)
+            if self._warp_table is None or self._warp_table.numel() < rows.numel():
+                self._warp_table = torch.empty(rows.numel(), dtype=torch.float32, device=self.device)
+            table = self._warp_table[:rows.numel()].view(rows.shape)
+            if self.device.type == "cuda" and not rows.is_pinned():
+                rows = rows.pin_memory()
+            table.copy_(rows, non_blocking=True)
+            self.be.roi_resize_ragged_warp(self.arena, h2d(off, self.device), h2d(hw, self.device), self._byte_lut, self.fill,
+                                           h2d(box, self.device), table, out, bool(antialias), pitch=pitch,
+                                           max_hw=(int(hw[:, 0].max()), int(hw[:, 1].max())))(stream)
+            return out
         self.be.roi_resize_ragged(self.arena, h2d(off, self.device), h2d(hw, self.device), self._byte_lut, self.fill,
                                   h2d(box, self.device), out, bool(antialias), crop, pad, pitch=pitch,
                                   max_hw=(int(hw[:, 0].max()), int(hw[:, 1].max())))(stream)
@@ -1056,7 +1086,10 @@ class RoiResize:
     ``sfk_roi_resize`` launch (include/sfk_v2.h).  The resize is ``F.interpolate(bilinear, align_corners=False,
     antialias=antialias)``, what torchvision's tensor ``Resize`` calls: pinned to torch, torchvision itself unpinned (it
     is not installed here; it antialiases tensors by default from 0.17 on and did not before).  crop (N, 2) int32
-    (top, left) applies RandomCrop(S, padding) after the resize (``do_augment``), zeros outside."""
+    (top, left) applies RandomCrop(S, padding) after the resize (``do_augment``), zeros outside.  warp (N, 6) float32
+    (``draw_affine`` on S x S) instead of crop: every clip is the resize's own interpolant sampled through its matrix, by ONE
+    ``sfk_roi_resize_warp`` launch (include/sfk_roi_warp.h) in place of the ``sfk_roi_resize`` one; the rows are validated on
+    the host first (``validate_warp_rows``).  crop and warp together is a ValueError."""
 
     def __init__(self, size: int, device="cuda", backend=None, out_dtype: torch.dtype = torch.float32,
                  antialias: bool = True):
@@ -1065,8 +1098,11 @@ class RoiResize:
         self.lut = byte_lut().to(self.device)
 
     def __call__(self, frames_u8: torch.Tensor, box: torch.Tensor, crop: Optional[torch.Tensor] = None,
-                 padding: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 padding: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                 warp: Optional[torch.Tensor] = None) -> torch.Tensor:
         assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 5
+        if crop is not None and warp is not None:
+            raise ValueError("RoiResize: crop and warp together (a warp row carries RandomCrop's translation itself)")
         n, t, h, w, c = frames_u8.shape
         x = h2d(frames_u8, self.device)
         box = h2d(box.to(torch.int32), self.device).contiguous()
@@ -1078,6 +1114,11 @@ class RoiResize:
         if out is None:
             out = torch.empty(n, t, c, self.size, self.size, dtype=self.out_dtype, device=self.device)
         stream = stream_of(self.device)
+        if warp is not None:
+            rows = validate_warp_rows(warp)
+            assert tuple(rows.shape) == (n, 6), tuple(rows.shape)
+            self.be.roi_resize_warp(x, self.lut, box, h2d(rows, self.device), out, self.antialias)(stream)
+            return out
         self.be.roi_resize(x, self.lut, box, out, self.antialias, crop, pad)(stream)
         return out
 
@@ -1376,7 +1417,11 @@ class ResidentGestureSet(_ResidentSet):
     (default floor(MODEL.RESIDENT_GB * 2^30 / (H*W*7))), the last batch_size * CLIP_LEN of them the spill region.
     Plan: ``plan(e)`` batches are (videos, indices (N, T), box (N, 4), crop (N, 2) | None, jitter (N, 8) | None); per clip the
     start exactly as v1 draws it, the crop row (``draw_crop_offsets``, padding S // 10) only with augment=True (the reference
-    trains with do_augment=False, new_feature_test.py:814), then the jitter row.  A clip's box is the min / max over the
+    trains with do_augment=False, new_feature_test.py:814), then the jitter row.  affine = (degrees, (lo, hi), shear, flip)
+    (MODEL.AFFINE): the crop column holds the (6,) float32 warp row of ``draw_affine(1, S, S // 10, ...)`` instead, drawn at
+    the crop row's stream position (its first two draws ARE the crop's), told from the int32 crop rows by its dtype; a batch
+    is then one ``sfk_roi_resize_pool_warp`` / ``sfk_roi_resize_ragged_warp`` launch (include/sfk_roi_warp.h).  The matrix
+    lives in the resized image's coordinates, so both stores give the same batches.  A clip's box is the min / max over the
     frame_boxes rows of its indices, clamped as ``ChalearnGestureFrames.clip_box`` clamps it; an empty one is a ValueError
     naming the video, raised by ``plan``.
     ``epoch(e)`` yields {'clip_v2': (N, T, 7, S, S) on the device in MODEL.DTYPE, 'label': (N,), optionally 'jitter': (N, 8)},
@@ -1396,8 +1441,11 @@ class ResidentGestureSet(_ResidentSet):
 
     def __init__(self, train_set, cfg, device="cuda", backend=None, batch_size: int = 1, drop_last: bool = False, seed: int = 0,
                  capacity_frames: Optional[int] = None, num_workers: int = 0, jitter=None, augment: bool = False,
-                 store: Optional[str] = None, capacity_bytes: Optional[int] = None):
+                 store: Optional[str] = None, capacity_bytes: Optional[int] = None, affine=None):
         super().__init__(train_set, cfg, device, backend, batch_size, drop_last, seed, num_workers, jitter)
+        # MODEL.AFFINE: (degrees, (scale lo, hi), shear, flip) -- the plan's crop column is then the warp row
+        self.affine = None if affine is None else (float(affine[0]), tuple(float(v) for v in affine[1]), float(affine[2]),
+                                                   float(affine[3]))
         self.store = str(cfg.MODEL.get("RESIDENT_STORE", "frame") if store is None else store)
         if self.store not in ("frame", "box"):
             raise ValueError(f"ResidentGestureSet: store {self.store!r} is neither 'frame' nor 'box'")
@@ -1502,17 +1550,21 @@ class ResidentGestureSet(_ResidentSet):
         return torch.tensor([x1, y1, x2, y2], dtype=torch.int32)
 
     def _clip_rows(self, g, video, indices) -> tuple:
+        if self.affine is not None:             # the same stream position for (top, left) as the crop row's
+            return (self.clip_box(video, indices), draw_affine(1, self.size, self.size // 10, *self.affine, generator=g)[0])
         return (self.clip_box(video, indices), draw_crop_offsets(1, self.size // 10, g)[0] if self.augment else None)
 
     def _upload(self, item, windows) -> int:
         return self.pool.add(item[pool_key(self.key)], windows)
 
     def _batch(self, table, entry) -> dict:
+        # (N, 6) float32 warp rows (MODEL.AFFINE); the crop rows are (N, 2) int32
+        aug = dict(warp=entry[3]) if entry[3] is not None and entry[3].dtype == torch.float32 else dict(crop=entry[3])
         if self.store == "box":
             # a resident video's frames lie in R_v, a spilled clip's in its own box: translate each box by that origin
             rect = torch.tensor([self.video_rect(v) if self._resident[v] else entry[2][n].tolist() for n, v in enumerate(entry[0])],
                                 dtype=torch.int32)
             hw = torch.stack([rect[:, 3] - rect[:, 1], rect[:, 2] - rect[:, 0]], 1)
             box = entry[2] - torch.cat([rect[:, :2], rect[:, :2]], 1)
-            return {"clip_v2": self.pool.roi_gather(table, hw, box, self.size, self.out_dtype, self.antialias, crop=entry[3])}
-        return {"clip_v2": self.pool.roi_gather(table, entry[2], self.size, self.out_dtype, self.antialias, crop=entry[3])}
+            return {"clip_v2": self.pool.roi_gather(table, hw, box, self.size, self.out_dtype, self.antialias, **aug)}
+        return {"clip_v2": self.pool.roi_gather(table, entry[2], self.size, self.out_dtype, self.antialias, **aug)}
