@@ -1423,21 +1423,71 @@ class HipBackend:
                            C.addressof(table.host) if table.nsegs else None, table.nsegs, gscale, max_norm, _ptr(partials),
                            _ptr(out), keep=(table, g, partials, out))
 
+    @staticmethod
+    def _roi_strided_src(d, src):
+        """the strided source of sfk_roi_resize and sfk_roi_resize_warp: its assertion and those fields of d; (n, t, c)"""
+        n, t, h, w, c = src.shape
+        assert src.dtype == torch.uint8
+        d.src = src.data_ptr()
+        d.sn, d.st, d.sh, d.sw, d.sc = src.stride()
+        d.n, d.t, d.h, d.w, d.c = n, t, h, w, c
+        return n, t, c
+
+    @staticmethod
+    def _roi_pool_src(d, pool, index, fill, c0, c):
+        """the pool source of sfk_roi_resize_pool and sfk_roi_resize_pool_warp: its assertions and those fields of d; (n, t, c)"""
+        f, h, w, p = pool.shape
+        c = p - c0 if c is None else c
+        assert pool.dtype == torch.uint8 and pool.stride(3) == 1 and 0 <= c0 and 0 < c and c0 + c <= p
+        assert index.dtype == torch.int32 and index.dim() == 2 and index.is_contiguous()
+        n, t = index.shape
+        d.pool, d.index = pool.data_ptr(), index.data_ptr()
+        d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
+        d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
+        return n, t, c
+
+    @staticmethod
+    def _roi_ragged_src(d, arena, offset, hw, fill, pitch, c0, c, max_hw):
+        """the arena source of sfk_roi_resize_ragged and sfk_roi_resize_ragged_warp: its assertions and those fields of d
+        (max_hw None: read from hw, which synchronises); (n, t, c)"""
+        c = pitch - c0 if c is None else c
+        assert arena.dtype == torch.uint8 and arena.dim() == 1 and arena.is_contiguous() and 0 <= c0 and 0 < c and c0 + c <= pitch
+        assert offset.dtype == torch.int64 and offset.dim() == 2 and offset.is_contiguous()
+        n, t = offset.shape
+        assert hw.dtype == torch.int32 and hw.is_contiguous() and tuple(hw.shape) == (n, 2)
+        if max_hw is None:
+            max_hw = tuple(max(int(v), 1) for v in hw.max(0).values.tolist())
+        d.arena, d.arena_bytes, d.offset, d.hw = arena.data_ptr(), arena.numel(), offset.data_ptr(), hw.data_ptr()
+        d.pixel_pitch, d.c0, d.c, d.n, d.t, d.fill = int(pitch), c0, c, n, t, int(fill)
+        d.max_h, d.max_w = int(max_hw[0]), int(max_hw[1])
+        return n, t, c
+
+    @staticmethod
+    def _roi_dst(d, n, t, c, lut, box, out, antialias, c_off, crop=None, pad=0, warp=None):
+        """what the six sfk_roi_resize* descriptors share: the assertions on lut, box, out and on warp (the three _warp
+        descriptors) or crop (the other three), and those fields of d"""
+        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
+        assert box.dtype == torch.int32 and box.is_contiguous() and tuple(box.shape) == (n, 4)
+        assert out.dim() == 5 and out.stride(4) == 1 and out.shape[0] == n and out.shape[1] == t and 0 <= c_off and c_off + c <= out.shape[2]
+        if warp is not None:
+            assert warp.dtype == torch.float32 and warp.is_contiguous() and tuple(warp.shape) == (n, WARP_ROW_FLOATS)
+            assert warp.device == out.device
+            d.warp = warp.data_ptr()
+        else:
+            assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (n, 2))
+            d.crop, d.pad = _ptr(crop), int(pad)
+        d.antialias, d.lut, d.box = 1 if antialias else 0, lut.data_ptr(), box.data_ptr()
+        d.out_h, d.out_w = out.shape[3], out.shape[4]
+        d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
+        d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
+        return d
+
     def roi_resize(self, src, lut, box, out, antialias: bool, crop=None, pad: int = 0, c_off: int = 0):
         """sfk_roi_resize (include/sfk_v2.h): src (N,T,H,W,C) uint8, any byte strides (HWC or a permuted planar view);
         box (N,4) int32 (x1, y1, x2, y2); out (N,T,C',S,S') f32|bf16 with unit W stride, channels c_off .. c_off+C-1 written;
         crop (N,2) int32 (top, left) or None."""
-        n, t, h, w, c = src.shape
-        assert src.dtype == torch.uint8 and box.dtype == torch.int32 and box.is_contiguous() and tuple(box.shape) == (n, 4)
-        assert out.dim() == 5 and out.stride(4) == 1 and out.shape[0] == n and out.shape[1] == t and c_off + c <= out.shape[2]
-        assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (n, 2))
         d = new_roi_desc()
-        d.antialias, d.src, d.lut, d.box, d.crop, d.pad = 1 if antialias else 0, src.data_ptr(), lut.data_ptr(), box.data_ptr(), _ptr(crop), pad
-        d.sn, d.st, d.sh, d.sw, d.sc = src.stride()
-        d.n, d.t, d.h, d.w, d.c = n, t, h, w, c
-        d.out_h, d.out_w = out.shape[3], out.shape[4]
-        d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
-        d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
+        d = self._roi_dst(d, *self._roi_strided_src(d, src), lut, box, out, antialias, c_off, crop, pad)
         return self._plain("sfk_roi_resize", C.byref(d), keep=(d, src, lut, box, out, crop))
 
     def color_jitter_workspace_bytes(self, n: int, t: int, h: int, w: int) -> int:
@@ -1520,16 +1570,20 @@ class HipBackend:
         return self._plain("sfk_ema_swap", C.byref(d), keep=(d, p, e, table))
 
     @staticmethod
-    def _fill_pool_desc(d, pool, index, lut, fill, out, c0, c):
-        """what sfk_pool_desc and sfk_pool_crop_desc share: the assertions on pool, index, lut and out, and those fields of d"""
+    def _fill_pool_desc(d, pool, index, lut, fill, out, c0, c, nt=None):
+        """what sfk_pool_desc, sfk_pool_crop_desc and sfk_pool_warp_desc share: the assertions on pool, index, lut and out, and
+        those fields of d.  index None (sfk_pool_warp_desc only): pool is the stacked batch, already viewed as (N*T,H,W,P),
+        and nt its (N, T)"""
         f, h, w, p = pool.shape
         c = p - c0 if c is None else c
         assert pool.dtype == torch.uint8 and pool.stride(3) == 1 and 0 <= c0 and 0 < c and c0 + c <= p
-        assert index.dtype == torch.int32 and index.dim() == 2 and index.is_contiguous()
-        n, t = index.shape
+        if index is not None:
+            assert index.dtype == torch.int32 and index.dim() == 2 and index.is_contiguous()
+            nt = index.shape
+        n, t = nt
         assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
         assert out.is_contiguous() and tuple(out.shape) == (n, t, c, h, w), (tuple(out.shape), (n, t, c, h, w))
-        d.out_dtype, d.pool, d.index, d.lut, d.out = _DT[out.dtype], pool.data_ptr(), index.data_ptr(), lut.data_ptr(), out.data_ptr()
+        d.out_dtype, d.pool, d.index, d.lut, d.out = _DT[out.dtype], pool.data_ptr(), _ptr(index), lut.data_ptr(), out.data_ptr()
         d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
         d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
         return d
@@ -1557,21 +1611,12 @@ class HipBackend:
         (N,6) float32 (a, b, c, d, e, f) on the device, read when the launch runs: out[n,t,ch,y,x] is the bilinear sample of the
         normalised frame at (a x + b y + c, d x + e y + f), zeros outside the frame (lut[fill] for a missing frame).  index
         (N,T) int32, or None: pool is then the stacked batch (N,T,H,W,P) itself and clip n, time t reads frame n*T + t."""
+        nt = None
         if index is None:
             assert pool.dim() == 5 and pool.is_contiguous(), "index=None: pool is the stacked (N,T,H,W,P) batch"
-            n, t = int(pool.shape[0]), int(pool.shape[1])
-            pool = pool.view((n * t,) + tuple(pool.shape[2:]))
-            f, h, w, p = pool.shape
-            c = p - c0 if c is None else c
-            assert pool.dtype == torch.uint8 and 0 <= c0 and 0 < c and c0 + c <= p
-            assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
-            assert out.is_contiguous() and tuple(out.shape) == (n, t, c, h, w), (tuple(out.shape), (n, t, c, h, w))
-            d = new_pool_warp_desc()
-            d.out_dtype, d.pool, d.index, d.lut, d.out = _DT[out.dtype], pool.data_ptr(), None, lut.data_ptr(), out.data_ptr()
-            d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
-            d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
-        else:
-            d = self._fill_pool_desc(new_pool_warp_desc(), pool, index, lut, fill, out, c0, c)
+            nt = int(pool.shape[0]), int(pool.shape[1])
+            pool = pool.view((nt[0] * nt[1],) + tuple(pool.shape[2:]))
+        d = self._fill_pool_desc(new_pool_warp_desc(), pool, index, lut, fill, out, c0, c, nt)
         assert warp.dtype == torch.float32 and tuple(warp.shape) == (d.n, WARP_ROW_FLOATS) and warp.is_contiguous()
         assert warp.device == out.device
         d.warp = warp.data_ptr()
@@ -1592,22 +1637,8 @@ class HipBackend:
         (F,H,W,P) uint8 with unit channel stride, channels c0 .. c0+c-1 -- or the constant image of byte fill when the index
         is outside [0, F); index (N,T) int32, box (N,4) int32 and crop (N,2) int32 | None on the device, read when the launch
         runs; out (N,T,C',S,S') f32|bf16 with unit W stride, channels c_off .. c_off+c-1 written."""
-        f, h, w, p = pool.shape
-        c = p - c0 if c is None else c
-        assert pool.dtype == torch.uint8 and pool.stride(3) == 1 and 0 <= c0 and 0 < c and c0 + c <= p
-        assert index.dtype == torch.int32 and index.dim() == 2 and index.is_contiguous()
-        n, t = index.shape
-        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
-        assert box.dtype == torch.int32 and box.is_contiguous() and tuple(box.shape) == (n, 4)
-        assert out.dim() == 5 and out.stride(4) == 1 and out.shape[0] == n and out.shape[1] == t and c_off + c <= out.shape[2]
-        assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (n, 2))
         d = new_roi_pool_desc()
-        d.antialias, d.pool, d.index, d.lut, d.box, d.crop = 1 if antialias else 0, pool.data_ptr(), index.data_ptr(), lut.data_ptr(), box.data_ptr(), _ptr(crop)
-        d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
-        d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.pad, d.fill = f, h, w, c0, c, n, t, int(pad), int(fill)
-        d.out_h, d.out_w = out.shape[3], out.shape[4]
-        d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
-        d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
+        d = self._roi_dst(d, *self._roi_pool_src(d, pool, index, fill, c0, c), lut, box, out, antialias, c_off, crop, pad)
         return self._plain("sfk_roi_resize_pool", C.byref(d), keep=(d, pool, index, lut, box, out, crop))
 
     def roi_resize_ragged(self, arena, offset, hw, lut, fill: int, box, out, antialias: bool, crop=None, pad: int = 0,
@@ -1618,83 +1649,34 @@ class HipBackend:
         (N,2) int32, box (N,4) int32 in the rectangle's coordinates and crop (N,2) int32 | None on the device, read when the
         launch runs; max_hw = (max_h, max_w) bounds every hw row and sizes the tile (None: read from hw, which
         synchronises); out (N,T,C',S,S') f32|bf16 with unit W stride, channels c_off .. c_off+c-1 written."""
-        c = pitch - c0 if c is None else c
-        assert arena.dtype == torch.uint8 and arena.dim() == 1 and arena.is_contiguous() and 0 <= c0 and 0 < c and c0 + c <= pitch
-        assert offset.dtype == torch.int64 and offset.dim() == 2 and offset.is_contiguous()
-        n, t = offset.shape
-        assert hw.dtype == torch.int32 and hw.is_contiguous() and tuple(hw.shape) == (n, 2)
-        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
-        assert box.dtype == torch.int32 and box.is_contiguous() and tuple(box.shape) == (n, 4)
-        assert out.dim() == 5 and out.stride(4) == 1 and out.shape[0] == n and out.shape[1] == t and c_off + c <= out.shape[2]
-        assert crop is None or (crop.dtype == torch.int32 and crop.is_contiguous() and tuple(crop.shape) == (n, 2))
-        if max_hw is None:
-            max_hw = tuple(max(int(v), 1) for v in hw.max(0).values.tolist())
         d = new_roi_ragged_desc()
-        d.antialias, d.arena, d.arena_bytes, d.offset, d.hw = 1 if antialias else 0, arena.data_ptr(), arena.numel(), offset.data_ptr(), hw.data_ptr()
-        d.lut, d.box, d.crop = lut.data_ptr(), box.data_ptr(), _ptr(crop)
-        d.pixel_pitch, d.c0, d.c, d.n, d.t, d.pad, d.fill = int(pitch), c0, c, n, t, int(pad), int(fill)
-        d.max_h, d.max_w = int(max_hw[0]), int(max_hw[1])
-        d.out_h, d.out_w = out.shape[3], out.shape[4]
-        d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
-        d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
+        ntc = self._roi_ragged_src(d, arena, offset, hw, fill, pitch, c0, c, max_hw)
+        d = self._roi_dst(d, *ntc, lut, box, out, antialias, c_off, crop, pad)
         return self._plain("sfk_roi_resize_ragged", C.byref(d), keep=(d, arena, offset, hw, lut, box, out, crop))
-
-    @staticmethod
-    def _roi_warp_common(d, n, t, c, lut, box, warp, out, antialias, c_off):
-        """what the three sfk_roi_warp descriptors share: the assertions on lut, box, warp and out, and those fields of d"""
-        assert lut.dtype == torch.float32 and lut.numel() == 256 and lut.is_contiguous()
-        assert box.dtype == torch.int32 and box.is_contiguous() and tuple(box.shape) == (n, 4)
-        assert warp.dtype == torch.float32 and warp.is_contiguous() and tuple(warp.shape) == (n, WARP_ROW_FLOATS)
-        assert warp.device == out.device
-        assert out.dim() == 5 and out.stride(4) == 1 and out.shape[0] == n and out.shape[1] == t and 0 <= c_off and c_off + c <= out.shape[2]
-        d.antialias, d.lut, d.box, d.warp = 1 if antialias else 0, lut.data_ptr(), box.data_ptr(), warp.data_ptr()
-        d.out_h, d.out_w = out.shape[3], out.shape[4]
-        d.dst_dtype, d.dst, d.c_off = _DT[out.dtype], out.data_ptr(), c_off
-        d.dn, d.dt, d.dc, d.dh = out.stride()[:4]
-        return d
 
     def roi_resize_warp(self, src, lut, box, warp, out, antialias: bool, c_off: int = 0):
         """sfk_roi_resize_warp (include/sfk_roi_warp.h): ``roi_resize`` sampled through a matrix per clip -- warp (N,6) float32
         (a, b, c, d, e, f) on the device, read when the launch runs: out[n,t,ch,y,x] is the resize's own interpolant at the
         position (a x + b y + c, d x + e y + f) of the resized image, zero outside it."""
-        n, t, h, w, c = src.shape
-        assert src.dtype == torch.uint8
-        d = self._roi_warp_common(new_roi_warp_desc(), n, t, c, lut, box, warp, out, antialias, c_off)
-        d.src = src.data_ptr()
-        d.sn, d.st, d.sh, d.sw, d.sc = src.stride()
-        d.n, d.t, d.h, d.w, d.c = n, t, h, w, c
+        d = new_roi_warp_desc()
+        d = self._roi_dst(d, *self._roi_strided_src(d, src), lut, box, out, antialias, c_off, warp=warp)
         return self._plain("sfk_roi_resize_warp", C.byref(d), keep=(d, src, lut, box, warp, out))
 
     def roi_resize_pool_warp(self, pool, index, lut, fill: int, box, warp, out, antialias: bool, c0: int = 0,
                              c: Optional[int] = None, c_off: int = 0):
         """sfk_roi_resize_pool_warp (include/sfk_roi_warp.h): ``roi_resize_pool`` sampled through warp (N,6) float32 as
         ``roi_resize_warp`` samples; a frame whose index is outside [0, F) is the constant image of byte fill."""
-        f, h, w, p = pool.shape
-        c = p - c0 if c is None else c
-        assert pool.dtype == torch.uint8 and pool.stride(3) == 1 and 0 <= c0 and 0 < c and c0 + c <= p
-        assert index.dtype == torch.int32 and index.dim() == 2 and index.is_contiguous()
-        n, t = index.shape
-        d = self._roi_warp_common(new_roi_pool_warp_desc(), n, t, c, lut, box, warp, out, antialias, c_off)
-        d.pool, d.index = pool.data_ptr(), index.data_ptr()
-        d.frame_stride, d.row_stride, d.pixel_pitch = pool.stride(0), pool.stride(1), pool.stride(2)
-        d.frames, d.h, d.w, d.c0, d.c, d.n, d.t, d.fill = f, h, w, c0, c, n, t, int(fill)
+        d = new_roi_pool_warp_desc()
+        d = self._roi_dst(d, *self._roi_pool_src(d, pool, index, fill, c0, c), lut, box, out, antialias, c_off, warp=warp)
         return self._plain("sfk_roi_resize_pool_warp", C.byref(d), keep=(d, pool, index, lut, box, warp, out))
 
     def roi_resize_ragged_warp(self, arena, offset, hw, lut, fill: int, box, warp, out, antialias: bool, pitch: int = 7,
                                c0: int = 0, c: Optional[int] = None, c_off: int = 0, max_hw=None):
         """sfk_roi_resize_ragged_warp (include/sfk_roi_warp.h): ``roi_resize_ragged`` sampled through warp (N,6) float32 as
         ``roi_resize_warp`` samples; a frame that does not lie in the arena whole is the constant image of byte fill."""
-        c = pitch - c0 if c is None else c
-        assert arena.dtype == torch.uint8 and arena.dim() == 1 and arena.is_contiguous() and 0 <= c0 and 0 < c and c0 + c <= pitch
-        assert offset.dtype == torch.int64 and offset.dim() == 2 and offset.is_contiguous()
-        n, t = offset.shape
-        assert hw.dtype == torch.int32 and hw.is_contiguous() and tuple(hw.shape) == (n, 2)
-        if max_hw is None:
-            max_hw = tuple(max(int(v), 1) for v in hw.max(0).values.tolist())
-        d = self._roi_warp_common(new_roi_ragged_warp_desc(), n, t, c, lut, box, warp, out, antialias, c_off)
-        d.arena, d.arena_bytes, d.offset, d.hw = arena.data_ptr(), arena.numel(), offset.data_ptr(), hw.data_ptr()
-        d.pixel_pitch, d.c0, d.c, d.n, d.t, d.fill = int(pitch), c0, c, n, t, int(fill)
-        d.max_h, d.max_w = int(max_hw[0]), int(max_hw[1])
+        d = new_roi_ragged_warp_desc()
+        ntc = self._roi_ragged_src(d, arena, offset, hw, fill, pitch, c0, c, max_hw)
+        d = self._roi_dst(d, *ntc, lut, box, out, antialias, c_off, warp=warp)
         return self._plain("sfk_roi_resize_ragged_warp", C.byref(d), keep=(d, arena, offset, hw, lut, box, warp, out))
 
     def u8_pad_resize_cubic(self, src, offset, hw, out, size: int, max_side: int, fill: int):

@@ -78,28 +78,9 @@ __global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, Ro
   const int Bv = min(g.B, d.out_h - Y0), TWv = min(g.TW, d.out_w - X0);
   const int C = d.c, KH = g.KH, KW = g.KW;
 
-  // the frame extent and row stride: the descriptor's, or the clip's own rectangle; its table rows are read once per
-  // workgroup and are block-uniform.  A frame is missing unless it lies in the arena whole: no product here can overflow
-  // (h_n * w_n < 2^62, and the bytes left after o are divided, not the rectangle multiplied)
-  int H = d.h, W = d.w;
-  int64_t rstride = d.sh;
-  int64_t foff = 0;                                       // the frame's byte offset in the arena
-  bool miss = false;
-  if (SRC == kRagged) {
-    const int hn = p.hw[2 * (int64_t)n], wn = p.hw[2 * (int64_t)n + 1];
-    const int64_t o = p.offset[(int64_t)n * d.t + t];
-    H = min(max(hn, 1), d.h);
-    W = min(max(wn, 1), d.w);
-    miss = o < 0 || hn != H || wn != W || o > p.arena_bytes || (int64_t)hn * wn > (p.arena_bytes - o) / d.sw;
-    rstride = (int64_t)W * d.sw;
-    foff = miss ? 0 : o;                                  // 64-bit: an arena may exceed 2^31 bytes
-  }
-
-  // the box, clamped the way a Python slice clamps it
-  const int32_t* bx = d.box + 4 * (int64_t)n;
-  const int x1 = min(max(bx[0], 0), W - 1), y1 = min(max(bx[1], 0), H - 1);
-  const int x2 = min(max(bx[2], x1 + 1), W), y2 = min(max(bx[3], y1 + 1), H);
-  const int bw = x2 - x1, bh = y2 - y1;
+  const RoiFrame f = roi_frame<SRC>(d, p, n, t);
+  const RoiBox b = roi_box(d, n, f.H, f.W);
+  const int bw = b.bw, bh = b.bh;
   int dy = 0, dx = 0;
   if (d.crop) {
     dy = d.crop[2 * (int64_t)n] - d.pad;
@@ -130,17 +111,8 @@ __global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, Ro
   const int ncol = min(xhi - xlo + 1, g.SP), nrow = min(yhi - ylo + 1, g.R);
 
   // 2. stage the window's bytes: sb[(row * SP + col) * C + ch]
-  const uint8_t* base = d.src + (int64_t)(y1 + ylo) * rstride + (int64_t)(x1 + xlo) * d.sw;
-  if (SRC == kPool) {
-    const int f = p.index[(int64_t)n * d.t + t];          // read once per workgroup; block-uniform
-    miss = f < 0 || f >= p.frames;
-    base += (int64_t)(miss ? 0 : f) * d.st;               // 64-bit: a pool may exceed 2^31 bytes
-  } else if (SRC == kRagged) {
-    base += foff;
-  } else {
-    base += n * d.sn + t * d.st;
-  }
-  roi_stage<SRC>(sb, g.SP, C, base, rstride, d, miss, p.fill, nrow, ncol, tid, kThreads);
+  const uint8_t* base = f.first + (int64_t)(b.y1 + ylo) * f.rstride + (int64_t)(b.x1 + xlo) * d.sw;
+  roi_stage<SRC>(sb, g.SP, C, base, f.rstride, d, f.miss, p.fill, nrow, ncol, tid, kThreads);
   __syncthreads();
 
   // 3. horizontal pass: tmp[(row * C + ch) * TW + j]
@@ -181,21 +153,13 @@ __global__ __launch_bounds__(kThreads) void roi_resize_kernel(sfk_roi_desc d, Ro
   }
 }
 
-// every host-side check the three entry points share (each checks its own struct_size and its own source first), then the
-// launch: p == nullptr is sfk_roi_resize's strided source, otherwise the pool's or the arena's
+// the host-side checks the three entry points share (roi_check, and pad; each checks its own struct_size and its own source
+// first), then the launch: p == nullptr is sfk_roi_resize's strided source, otherwise the pool's or the arena's
 int roi_resize(const sfk_roi_desc* d, int src, const RoiSrc* p, sfk_stream_t stream) {
-  if (!d->src || !d->lut || !d->box || !d->dst) return SFK_ERR_INVALID;
-  if (d->n <= 0 || d->t <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->out_h <= 0 || d->out_w <= 0) return SFK_ERR_INVALID;
-  if (d->sn < 0 || d->st < 0 || d->sh < 0 || d->sw < 0 || d->sc < 0 || d->dn < 0 || d->dt < 0 || d->dc < 0 || d->dh < 0)
-    return SFK_ERR_INVALID;
-  if ((d->antialias != 0 && d->antialias != 1) || d->pad < 0 || d->c_off < 0) return SFK_ERR_INVALID;
-  if (d->dst_dtype != SFK_F32 && d->dst_dtype != SFK_BF16) return SFK_ERR_INVALID;
-  if (d->c > SFK_ROI_MAX_C || (d->sc == 1 && d->sw > 4096)) return SFK_ERR_UNSUPPORTED;
+  if (d->pad < 0) return SFK_ERR_INVALID;
+  if (const int st = roi_check(d)) return st;
   const double sh = (double)d->h / d->out_h, sw = (double)d->w / d->out_w;
-  if (sh > SFK_ROI_MAX_RATIO || sw > SFK_ROI_MAX_RATIO) return SFK_ERR_UNSUPPORTED;
-  // worst-case taps: the box never exceeds its frame, so its ratio never exceeds sh / sw
-  const int KH = d->antialias ? (int)ceil(sh > 1.0 ? sh : 1.0) * 2 + 1 : 2;
-  const int KW = d->antialias ? (int)ceil(sw > 1.0 ? sw : 1.0) * 2 + 1 : 2;
+  const int KH = roi_max_taps(d->h, d->out_h, d->antialias), KW = roi_max_taps(d->w, d->out_w, d->antialias);
   const double spans_h = sh > 1.0 ? sh : 1.0, spans_w = sw > 1.0 ? sw : 1.0;
   RoiGeo g{};
   bool ok = false;
@@ -211,14 +175,10 @@ int roi_resize(const sfk_roi_desc* d, int src, const RoiSrc* p, sfk_stream_t str
   }
   if (!ok) return SFK_ERR_UNSUPPORTED;
   const int64_t tiles = (int64_t)g.row_tiles * g.col_tiles;
-  if (tiles > 0x7fffffff || d->t > 65535 || d->n > 65535) return SFK_ERR_UNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!roi_grid_fits(tiles, d)) return SFK_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)tiles, (unsigned)d->t, (unsigned)d->n);
-  const bool bf = d->dst_dtype == SFK_BF16;
-  const auto kernel = src == kRagged ? (bf ? roi_resize_kernel<bf16_t, kRagged> : roi_resize_kernel<float, kRagged>)
-                      : src == kPool ? (bf ? roi_resize_kernel<bf16_t, kPool> : roi_resize_kernel<float, kPool>)
-                                     : (bf ? roi_resize_kernel<bf16_t, kStacked> : roi_resize_kernel<float, kStacked>);
-  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), g.lds, s, *d, g, p ? *p : RoiSrc{});
+  hipLaunchKernelGGL(SFK_ROI_KERNEL(roi_resize_kernel, d->dst_dtype, src), grid, dim3(kThreads), g.lds,
+                     static_cast<hipStream_t>(stream), *d, g, p ? *p : RoiSrc{});
   SFK_CHECK_LAUNCH();
   return SFK_OK;
 }
@@ -232,41 +192,19 @@ extern "C" int sfk_roi_resize(const sfk_roi_desc* d, sfk_stream_t stream) {
 
 extern "C" int sfk_roi_resize_pool(const sfk_roi_pool_desc* d, sfk_stream_t stream) {
   if (!d || d->struct_size != sizeof(sfk_roi_pool_desc)) return SFK_ERR_INVALID;
-  if (!d->pool || !d->index || d->frames <= 0) return SFK_ERR_INVALID;
-  if (d->frame_stride < 0 || d->row_stride < 0 || d->c0 < 0) return SFK_ERR_INVALID;
-  if ((int64_t)d->pixel_pitch < (int64_t)d->c0 + d->c) return SFK_ERR_INVALID;
-  if (d->fill < 0 || d->fill > 255) return SFK_ERR_INVALID;
-  sfk_roi_desc r{};
-  r.struct_size = sizeof(sfk_roi_desc);
-  r.antialias = d->antialias;
-  r.src = d->pool + d->c0;
-  r.sn = 0, r.st = d->frame_stride, r.sh = d->row_stride, r.sw = d->pixel_pitch, r.sc = 1;
-  r.n = d->n, r.t = d->t, r.h = d->h, r.w = d->w, r.c = d->c;
-  r.out_h = d->out_h, r.out_w = d->out_w;
-  r.lut = d->lut, r.box = d->box, r.crop = d->crop, r.pad = d->pad;
-  r.dst_dtype = d->dst_dtype, r.dst = d->dst;
-  r.dn = d->dn, r.dt = d->dt, r.dc = d->dc, r.dh = d->dh, r.c_off = d->c_off;
-  const RoiSrc p{d->index, d->frames, d->fill, nullptr, nullptr, 0};
+  sfk_roi_desc r;
+  RoiSrc p;
+  if (const int st = roi_from_pool(*d, &r, &p)) return st;
+  r.crop = d->crop, r.pad = d->pad;
   return roi_resize(&r, kPool, &p, stream);
 }
 
 extern "C" int sfk_roi_resize_ragged(const sfk_roi_ragged_desc* d, sfk_stream_t stream) {
   if (!d || d->struct_size != sizeof(sfk_roi_ragged_desc)) return SFK_ERR_INVALID;
-  if (!d->arena || !d->offset || !d->hw || d->max_h <= 0 || d->max_w <= 0) return SFK_ERR_INVALID;
-  if (d->arena_bytes <= 0 || (d->arena_bytes & 3) || ((uintptr_t)d->arena & 3) || d->c0 < 0) return SFK_ERR_INVALID;
-  if ((int64_t)d->pixel_pitch < (int64_t)d->c0 + d->c) return SFK_ERR_INVALID;
-  if (d->fill < 0 || d->fill > 255) return SFK_ERR_INVALID;
-  sfk_roi_desc r{};
-  r.struct_size = sizeof(sfk_roi_desc);
-  r.antialias = d->antialias;
-  r.src = d->arena + d->c0;
-  r.sn = 0, r.st = 0, r.sh = 0, r.sw = d->pixel_pitch, r.sc = 1;
-  r.n = d->n, r.t = d->t, r.h = d->max_h, r.w = d->max_w, r.c = d->c;
-  r.out_h = d->out_h, r.out_w = d->out_w;
-  r.lut = d->lut, r.box = d->box, r.crop = d->crop, r.pad = d->pad;
-  r.dst_dtype = d->dst_dtype, r.dst = d->dst;
-  r.dn = d->dn, r.dt = d->dt, r.dc = d->dc, r.dh = d->dh, r.c_off = d->c_off;
-  const RoiSrc p{nullptr, 0, d->fill, d->offset, d->hw, d->arena_bytes};
+  sfk_roi_desc r;
+  RoiSrc p;
+  if (const int st = roi_from_ragged(*d, &r, &p)) return st;
+  r.crop = d->crop, r.pad = d->pad;
   return roi_resize(&r, kRagged, &p, stream);
 }
 

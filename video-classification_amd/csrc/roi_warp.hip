@@ -5,7 +5,7 @@
 // compiled under the headers' own contraction mode and fuse after inlining); the fused operations the contract does name --
 // the source index, and every tap after the first of a weighted sum, which is how roi_resize_kernel's passes are compiled --
 // are explicit __fmaf_rn.  The three entry points share one kernel and one launcher; the source addressing is a compile-time
-// switch, as in roi_resize.hip, whose RoiSrc, box clamp and byte staging (roi_common.h) are used here.
+// switch, as in roi_resize.hip; where a frame lies, the box clamp and the byte staging are roi_common.h's, shared with it.
 //
 // One workgroup owns a tile of TILE_H x TILE_W destination pixels of one (clip, frame), all channels:
 //   1. it reads the clip's box and matrix, evaluates the contract's (u, v) at the tile's four corners -- each is monotone in
@@ -95,32 +95,9 @@ __global__ __launch_bounds__(kThreads) void roi_warp_kernel(sfk_roi_desc d, cons
   const int Bv = min(kTH, d.out_h - Y0), TWv = min(kTW, d.out_w - X0);
   const int C = d.c, aa = d.antialias;
 
-  // the frame extent, row stride and first byte, and whether the frame is missing: roi_resize_kernel's, word for word
-  int H = d.h, W = d.w;
-  int64_t rstride = d.sh;
-  const uint8_t* frame = d.src;
-  bool miss = false;
-  if (SRC == kRagged) {
-    const int hn = p.hw[2 * (int64_t)n], wn = p.hw[2 * (int64_t)n + 1];
-    const int64_t o = p.offset[(int64_t)n * d.t + t];
-    H = min(max(hn, 1), d.h);
-    W = min(max(wn, 1), d.w);
-    miss = o < 0 || hn != H || wn != W || o > p.arena_bytes || (int64_t)hn * wn > (p.arena_bytes - o) / d.sw;
-    rstride = (int64_t)W * d.sw;
-    frame += miss ? 0 : o;
-  } else if (SRC == kPool) {
-    const int f = p.index[(int64_t)n * d.t + t];
-    miss = f < 0 || f >= p.frames;
-    frame += (int64_t)(miss ? 0 : f) * d.st;
-  } else {
-    frame += n * d.sn + t * d.st;
-  }
-
-  // the box, clamped the way a Python slice clamps it
-  const int32_t* bx = d.box + 4 * (int64_t)n;
-  const int x1 = min(max(bx[0], 0), W - 1), y1 = min(max(bx[1], 0), H - 1);
-  const int x2 = min(max(bx[2], x1 + 1), W), y2 = min(max(bx[3], y1 + 1), H);
-  const int bw = x2 - x1, bh = y2 - y1;
+  const RoiFrame f = roi_frame<SRC>(d, p, n, t);
+  const RoiBox b = roi_box(d, n, f.H, f.W);
+  const int bw = b.bw, bh = b.bh;
   const float* m = warp + 6 * (int64_t)n;
   const float ma = m[0], mb = m[1], mc = m[2], md = m[3], me = m[4], mf = m[5];
   const float umax_ok = (float)d.out_w - 0.5f, vmax_ok = (float)d.out_h - 0.5f;
@@ -146,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void roi_warp_kernel(sfk_roi_desc d, cons
   const unsigned char* base = sb;
   int64_t rs = 0, cs = 0, chs = 0;
   int oy = 0, ox = 0, rmax = 0, cmax = 0;
-  if (SRC != kStacked && miss) {
+  if (SRC != kStacked && f.miss) {
     if (tid == 0) sb[0] = (unsigned char)p.fill;
   } else if (!outside) {
     bool staged = false;
@@ -160,16 +137,16 @@ __global__ __launch_bounds__(kThreads) void roi_warp_kernel(sfk_roi_desc d, cons
       const int yhi = min(f2 + max(c2, 1) - 1, bh - 1);
       const int ncol = max(xhi - xlo + 1, 1), nrow = max(yhi - ylo + 1, 1);
       if ((int64_t)nrow * ncol * C <= kStage) {
-        const uint8_t* wbase = frame + (int64_t)(y1 + ylo) * rstride + (int64_t)(x1 + xlo) * d.sw;
-        roi_stage<SRC>(sb, ncol, C, wbase, rstride, d, false, 0, nrow, ncol, tid, kThreads);
+        const uint8_t* wbase = f.first + (int64_t)(b.y1 + ylo) * f.rstride + (int64_t)(b.x1 + xlo) * d.sw;
+        roi_stage<SRC>(sb, ncol, C, wbase, f.rstride, d, false, 0, nrow, ncol, tid, kThreads);
         staged = true;
         rs = (int64_t)ncol * C, cs = C, chs = 1;
         oy = ylo, ox = xlo, rmax = nrow - 1, cmax = ncol - 1;
       }
     }
     if (!staged) {
-      base = frame + (int64_t)y1 * rstride + (int64_t)x1 * d.sw;
-      rs = rstride, cs = d.sw, chs = d.sc;
+      base = f.first + (int64_t)b.y1 * f.rstride + (int64_t)b.x1 * d.sw;
+      rs = f.rstride, cs = d.sw, chs = d.sc;
       rmax = bh - 1, cmax = bw - 1;
     }
   }
@@ -221,22 +198,14 @@ __global__ __launch_bounds__(kThreads) void roi_warp_kernel(sfk_roi_desc d, cons
   }
 }
 
-// every host-side check the three entry points share (each checks its own struct_size and its own source first), then the
-// launch: roi_resize's, with warp in place of crop and pad
+// the host-side checks the three entry points share (roi_check, and warp; each checks its own struct_size and its own source
+// first), then the launch: roi_resize's, with warp in place of crop and pad
 int roi_warp(const sfk_roi_desc* d, const float* warp, int src, const RoiSrc* p, sfk_stream_t stream) {
-  if (!d->src || !d->lut || !d->box || !d->dst || !warp) return SFK_ERR_INVALID;
-  if (d->n <= 0 || d->t <= 0 || d->h <= 0 || d->w <= 0 || d->c <= 0 || d->out_h <= 0 || d->out_w <= 0) return SFK_ERR_INVALID;
-  if (d->sn < 0 || d->st < 0 || d->sh < 0 || d->sw < 0 || d->sc < 0 || d->dn < 0 || d->dt < 0 || d->dc < 0 || d->dh < 0)
-    return SFK_ERR_INVALID;
-  if ((d->antialias != 0 && d->antialias != 1) || d->c_off < 0) return SFK_ERR_INVALID;
-  if (d->dst_dtype != SFK_F32 && d->dst_dtype != SFK_BF16) return SFK_ERR_INVALID;
-  if (d->c > SFK_ROI_MAX_C || (d->sc == 1 && d->sw > 4096)) return SFK_ERR_UNSUPPORTED;
-  const double sh = (double)d->h / d->out_h, sw = (double)d->w / d->out_w;
-  if (sh > SFK_ROI_MAX_RATIO || sw > SFK_ROI_MAX_RATIO) return SFK_ERR_UNSUPPORTED;
-  // worst-case taps: the box never exceeds its frame, so its ratio never exceeds sh / sw
+  if (!warp) return SFK_ERR_INVALID;
+  if (const int st = roi_check(d)) return st;
   RoiWarpGeo g{};
-  g.KH = d->antialias ? (int)ceil(sh > 1.0 ? sh : 1.0) * 2 + 1 : 2;
-  g.KW = d->antialias ? (int)ceil(sw > 1.0 ? sw : 1.0) * 2 + 1 : 2;
+  g.KH = roi_max_taps(d->h, d->out_h, d->antialias);
+  g.KW = roi_max_taps(d->w, d->out_w, d->antialias);
   const int row_tiles = (d->out_h + kTH - 1) / kTH;
   g.col_tiles = (d->out_w + kTW - 1) / kTW;
   g.off_xw = 256 * 4;
@@ -244,14 +213,10 @@ int roi_warp(const sfk_roi_desc* d, const float* warp, int src, const RoiSrc* p,
   g.off_sb = g.off_yw + g.KH * kThreads * 4;
   const int lds = g.off_sb + kStage;                      // at most 1 + 34 + 24 KiB
   const int64_t tiles = (int64_t)row_tiles * g.col_tiles;
-  if (tiles > 0x7fffffff || d->t > 65535 || d->n > 65535) return SFK_ERR_UNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!roi_grid_fits(tiles, d)) return SFK_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)tiles, (unsigned)d->t, (unsigned)d->n);
-  const bool bf = d->dst_dtype == SFK_BF16;
-  const auto kernel = src == kRagged ? (bf ? roi_warp_kernel<bf16_t, kRagged> : roi_warp_kernel<float, kRagged>)
-                      : src == kPool ? (bf ? roi_warp_kernel<bf16_t, kPool> : roi_warp_kernel<float, kPool>)
-                                     : (bf ? roi_warp_kernel<bf16_t, kStacked> : roi_warp_kernel<float, kStacked>);
-  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), lds, s, *d, warp, g, p ? *p : RoiSrc{});
+  hipLaunchKernelGGL(SFK_ROI_KERNEL(roi_warp_kernel, d->dst_dtype, src), grid, dim3(kThreads), lds,
+                     static_cast<hipStream_t>(stream), *d, warp, g, p ? *p : RoiSrc{});
   SFK_CHECK_LAUNCH();
   return SFK_OK;
 }
@@ -260,56 +225,23 @@ int roi_warp(const sfk_roi_desc* d, const float* warp, int src, const RoiSrc* p,
 
 extern "C" int sfk_roi_resize_warp(const sfk_roi_warp_desc* d, sfk_stream_t stream) {
   if (!d || d->struct_size != sizeof(sfk_roi_warp_desc)) return SFK_ERR_INVALID;
-  sfk_roi_desc r{};
-  r.struct_size = sizeof(sfk_roi_desc);
-  r.antialias = d->antialias;
-  r.src = d->src;
-  r.sn = d->sn, r.st = d->st, r.sh = d->sh, r.sw = d->sw, r.sc = d->sc;
-  r.n = d->n, r.t = d->t, r.h = d->h, r.w = d->w, r.c = d->c;
-  r.out_h = d->out_h, r.out_w = d->out_w;
-  r.lut = d->lut, r.box = d->box;
-  r.dst_dtype = d->dst_dtype, r.dst = d->dst;
-  r.dn = d->dn, r.dt = d->dt, r.dc = d->dc, r.dh = d->dh, r.c_off = d->c_off;
+  const sfk_roi_desc r = roi_from_strided(*d);
   return roi_warp(&r, d->warp, kStacked, nullptr, stream);
 }
 
 extern "C" int sfk_roi_resize_pool_warp(const sfk_roi_pool_warp_desc* d, sfk_stream_t stream) {
   if (!d || d->struct_size != sizeof(sfk_roi_pool_warp_desc)) return SFK_ERR_INVALID;
-  if (!d->pool || !d->index || d->frames <= 0) return SFK_ERR_INVALID;
-  if (d->frame_stride < 0 || d->row_stride < 0 || d->c0 < 0) return SFK_ERR_INVALID;
-  if ((int64_t)d->pixel_pitch < (int64_t)d->c0 + d->c) return SFK_ERR_INVALID;
-  if (d->fill < 0 || d->fill > 255) return SFK_ERR_INVALID;
-  sfk_roi_desc r{};
-  r.struct_size = sizeof(sfk_roi_desc);
-  r.antialias = d->antialias;
-  r.src = d->pool + d->c0;
-  r.sn = 0, r.st = d->frame_stride, r.sh = d->row_stride, r.sw = d->pixel_pitch, r.sc = 1;
-  r.n = d->n, r.t = d->t, r.h = d->h, r.w = d->w, r.c = d->c;
-  r.out_h = d->out_h, r.out_w = d->out_w;
-  r.lut = d->lut, r.box = d->box;
-  r.dst_dtype = d->dst_dtype, r.dst = d->dst;
-  r.dn = d->dn, r.dt = d->dt, r.dc = d->dc, r.dh = d->dh, r.c_off = d->c_off;
-  const RoiSrc p{d->index, d->frames, d->fill, nullptr, nullptr, 0};
+  sfk_roi_desc r;
+  RoiSrc p;
+  if (const int st = roi_from_pool(*d, &r, &p)) return st;
   return roi_warp(&r, d->warp, kPool, &p, stream);
 }
 
 extern "C" int sfk_roi_resize_ragged_warp(const sfk_roi_ragged_warp_desc* d, sfk_stream_t stream) {
   if (!d || d->struct_size != sizeof(sfk_roi_ragged_warp_desc)) return SFK_ERR_INVALID;
-  if (!d->arena || !d->offset || !d->hw || d->max_h <= 0 || d->max_w <= 0) return SFK_ERR_INVALID;
-  if (d->arena_bytes <= 0 || (d->arena_bytes & 3) || ((uintptr_t)d->arena & 3) || d->c0 < 0) return SFK_ERR_INVALID;
-  if ((int64_t)d->pixel_pitch < (int64_t)d->c0 + d->c) return SFK_ERR_INVALID;
-  if (d->fill < 0 || d->fill > 255) return SFK_ERR_INVALID;
-  sfk_roi_desc r{};
-  r.struct_size = sizeof(sfk_roi_desc);
-  r.antialias = d->antialias;
-  r.src = d->arena + d->c0;
-  r.sn = 0, r.st = 0, r.sh = 0, r.sw = d->pixel_pitch, r.sc = 1;
-  r.n = d->n, r.t = d->t, r.h = d->max_h, r.w = d->max_w, r.c = d->c;
-  r.out_h = d->out_h, r.out_w = d->out_w;
-  r.lut = d->lut, r.box = d->box;
-  r.dst_dtype = d->dst_dtype, r.dst = d->dst;
-  r.dn = d->dn, r.dt = d->dt, r.dc = d->dc, r.dh = d->dh, r.c_off = d->c_off;
-  const RoiSrc p{nullptr, 0, d->fill, d->offset, d->hw, d->arena_bytes};
+  sfk_roi_desc r;
+  RoiSrc p;
+  if (const int st = roi_from_ragged(*d, &r, &p)) return st;
   return roi_warp(&r, d->warp, kRagged, &p, stream);
 }
 

@@ -409,6 +409,40 @@ def unpool_item(item: dict) -> list:
     return [{pk[:-len("_pool")] + "_u8": ext[row], "label": item["label"]} for row in idx]
 
 
+def _persistent_table(tables: dict, name: str, host: torch.Tensor, device) -> torch.Tensor:
+    """host table -> its view of the persistent device buffer tables[name], written on the current stream.  The buffer is
+    sized at first use and grows to the largest table seen, so equal-shaped batches get the SAME address (a smaller one the
+    same base); the copy is ordered behind every launch already enqueued that reads the old contents."""
+    buf = tables.get(name)
+    if buf is None or buf.numel() < host.numel():
+        buf = tables[name] = torch.empty(host.numel(), dtype=host.dtype, device=device)
+    view = buf[:host.numel()].view(host.shape)
+    src = host
+    if src.device.type == "cpu" and device.type == "cuda" and not src.is_pinned():
+        src = src.pin_memory()
+    view.copy_(src, non_blocking=True)
+    return view
+
+
+def _roi_tables(who: str, n: int, size: int, box, crop, padding, warp) -> tuple:
+    """what ``RoiResize`` and the two ``roi_gather``s (who: the caller a ValueError names) take per batch of n clips, as host
+    tensors: (box (n, 4) int32, crop (n, 2) int32 | None, pad, warp (n, 6) float32 validated | None); pad is RandomCrop's
+    padding, size // 10 unless given, and 0 without a crop.  Where each is uploaded is the caller's."""
+    if crop is not None and warp is not None:
+        raise ValueError(f"{who}: crop and warp together (a warp row carries RandomCrop's translation itself)")
+    box = torch.as_tensor(box).to(torch.int32).contiguous()
+    assert tuple(box.shape) == (n, 4), tuple(box.shape)
+    pad = 0
+    if crop is not None:
+        crop = torch.as_tensor(crop).to(torch.int32).contiguous()
+        assert tuple(crop.shape) == (n, 2), tuple(crop.shape)
+        pad = size // 10 if padding is None else int(padding)
+    if warp is not None:
+        warp = validate_warp_rows(warp)
+        assert tuple(warp.shape) == (n, 6), tuple(warp.shape)
+    return box, crop, pad, warp
+
+
 class FramePool:
     """The device side of the pooled items: an arena of uint8 HWC frames (capacity, S, S, P) on the device, grown on demand.
 
@@ -550,18 +584,8 @@ class FramePool:
         return idx
 
     def _table(self, name: str, host: torch.Tensor) -> torch.Tensor:
-        """host table (int32; float32 for 'warp') -> its view of the pool's persistent device buffer `name`, written on the current stream.  The
-        buffer is sized at first use and grows to the largest table seen, so equal-shaped batches get the SAME address (a
-        smaller one the same base); the copy is ordered behind every launch already enqueued that reads the old contents."""
-        buf = self._tables.get(name)
-        if buf is None or buf.numel() < host.numel():
-            buf = self._tables[name] = torch.empty(host.numel(), dtype=host.dtype, device=self.device)
-        view = buf[:host.numel()].view(host.shape)
-        src = host
-        if src.device.type == "cpu" and self.device.type == "cuda" and not src.is_pinned():
-            src = src.pin_memory()
-        view.copy_(src, non_blocking=True)
-        return view
+        """host table (int32; float32 for 'warp' and 'roi_warp') -> its view of the pool's persistent device buffer `name`"""
+        return _persistent_table(self._tables, name, host, self.device)
 
     def clip(self, index_rows: torch.Tensor, channels, crop: Optional[torch.Tensor] = None,
              padding: Optional[int] = None) -> list:
@@ -620,38 +644,20 @@ class FramePool:
         current stream; the H2D of the index, box and crop tables only.  warp (N, 6) float32 (``draw_affine``) instead of
         crop: ONE ``sfk_roi_resize_pool_warp`` launch (include/sfk_roi_warp.h) instead, the validated rows written into the
         pool's persistent 'roi_warp' table; crop and warp together is a ValueError."""
-        if crop is not None and warp is not None:
-            raise ValueError("roi_gather: crop and warp together (a warp row carries RandomCrop's translation itself)")
-        idx = torch.as_tensor(index_rows, dtype=torch.int32).contiguous()
-        assert idx.dim() == 2 and idx.numel() > 0 and self.arena is not None
-        ok = torch.zeros(self.arena.shape[0] + 1, dtype=torch.bool)      # the last entry stands for -1
-        ok[-1] = True
-        for b, n in self.live.items():
-            ok[b:b + n] = True
-        if int(idx.min()) < -1 or int(idx.max()) >= self.arena.shape[0] or not bool(ok[idx.long()].all()):
-            raise ValueError("roi_gather: an index is neither -1 nor a slot of a video that is in the pool")
-        n, size = idx.shape[0], int(size)
-        box = torch.as_tensor(box).to(torch.int32).contiguous()
-        assert tuple(box.shape) == (n, 4), tuple(box.shape)
-        pad = 0
-        if crop is not None:
-            crop = torch.as_tensor(crop).to(torch.int32).contiguous()
-            assert tuple(crop.shape) == (n, 2), tuple(crop.shape)
-            pad = size // 10 if padding is None else int(padding)
-            crop = h2d(crop, self.device)
+        size = int(size)
+        box, crop, pad, warp = _roi_tables("roi_gather", len(index_rows), size, box, crop, padding, warp)
+        idx = self._checked_rows(index_rows, "roi_gather")
         if self._byte_lut is None:
             self._byte_lut = byte_lut().to(self.device)
         if out is None:
-            out = torch.empty(n, idx.shape[1], self.arena.shape[3], size, size, dtype=out_dtype, device=self.device)
+            out = torch.empty(idx.shape[0], idx.shape[1], self.arena.shape[3], size, size, dtype=out_dtype, device=self.device)
         stream = stream_of(self.device)
         if warp is not None:
-            rows = validate_warp_rows(warp)
-            assert tuple(rows.shape) == (n, 6), tuple(rows.shape)
             self.be.roi_resize_pool_warp(self.arena, h2d(idx, self.device), self._byte_lut, self.fill, h2d(box, self.device),
-                                         self._table("roi_warp", rows), out, bool(antialias))(stream)
+                                         self._table("roi_warp", warp), out, bool(antialias))(stream)
             return out
         self.be.roi_resize_pool(self.arena, h2d(idx, self.device), self._byte_lut, self.fill, h2d(box, self.device), out,
-                                bool(antialias), crop, pad)(stream)
+                                bool(antialias), None if crop is None else h2d(crop, self.device), pad)(stream)
         return out
 
 
@@ -678,7 +684,7 @@ class BoxArena:
         self.pitch: Optional[int] = None        # P: that of the first block, and of every block after it
         self.bytes_uploaded = 0
         self._byte_lut = None                   # roi_gather's table, made at its first call
-        self._warp_table = None                 # roi_gather's persistent device table of warp rows, grown to the largest seen
+        self._tables = {}                       # persistent device tables: roi_gather's 'roi_warp' (float32) -> flat buffer
 
     @classmethod
     def _span(cls, shape) -> int:
@@ -762,42 +768,27 @@ class BoxArena:
         (``draw_affine``) instead of crop: ONE ``sfk_roi_resize_ragged_warp`` launch (include/sfk_roi_warp.h) instead, the
         validated rows written into the arena's persistent warp table; crop and warp together is a ValueError.  The matrix
         lives in the coordinates of the RESIZED image, so the rectangle's origin, which translates the box, does not touch it."""
-        if crop is not None and warp is not None:
-            raise ValueError("roi_gather: crop and warp together (a warp row carries RandomCrop's translation itself)")
+        size = int(size)
+        box, crop, pad, warp = _roi_tables("roi_gather", len(offset_rows), size, box, crop, padding, warp)
         off = torch.as_tensor(offset_rows, dtype=torch.int64).contiguous()
         assert off.dim() == 2 and off.numel() > 0 and self.arena is not None
-        n, size = off.shape[0], int(size)
+        n, pitch = off.shape[0], self.pitch
         hw = torch.as_tensor(hw).to(torch.int32).contiguous()
-        box = torch.as_tensor(box).to(torch.int32).contiguous()
-        assert tuple(hw.shape) == (n, 2) and tuple(box.shape) == (n, 4), (tuple(hw.shape), tuple(box.shape))
+        assert tuple(hw.shape) == (n, 2), tuple(hw.shape)
         self._check_table(off, hw, box)
-        pitch, pad = self.pitch, 0
-        if crop is not None:
-            crop = torch.as_tensor(crop).to(torch.int32).contiguous()
-            assert tuple(crop.shape) == (n, 2), tuple(crop.shape)
-            pad = size // 10 if padding is None else int(padding)
-            crop = h2d(crop, self.device)
         if self._byte_lut is None:
             self._byte_lut = byte_lut().to(self.device)
         if out is None:
             out = torch.empty(n, off.shape[1], pitch, size, size, dtype=out_dtype, device=self.device)
-        stream = stream_of(self.device)
+        stream, max_hw = stream_of(self.device), (int(hw[:, 0].max()), int(hw[:, 1].max()))
         if warp is not None:
-            rows = validate_warp_rows(warp)
-            assert tuple(rows.shape) == (n, 6), tuple(rows.shape)
-            if self._warp_table is None or self._warp_table.numel() < rows.numel():
-                self._warp_table = torch.empty(rows.numel(), dtype=torch.float32, device=self.device)
-            table = self._warp_table[:rows.numel()].view(rows.shape)
-            if self.device.type == "cuda" and not rows.is_pinned():
-                rows = rows.pin_memory()
-            table.copy_(rows, non_blocking=True)
             self.be.roi_resize_ragged_warp(self.arena, h2d(off, self.device), h2d(hw, self.device), self._byte_lut, self.fill,
-                                           h2d(box, self.device), table, out, bool(antialias), pitch=pitch,
-                                           max_hw=(int(hw[:, 0].max()), int(hw[:, 1].max())))(stream)
+                                           h2d(box, self.device), _persistent_table(self._tables, "roi_warp", warp, self.device),
+                                           out, bool(antialias), pitch=pitch, max_hw=max_hw)(stream)
             return out
         self.be.roi_resize_ragged(self.arena, h2d(off, self.device), h2d(hw, self.device), self._byte_lut, self.fill,
-                                  h2d(box, self.device), out, bool(antialias), crop, pad, pitch=pitch,
-                                  max_hw=(int(hw[:, 0].max()), int(hw[:, 1].max())))(stream)
+                                  h2d(box, self.device), out, bool(antialias), None if crop is None else h2d(crop, self.device),
+                                  pad, pitch=pitch, max_hw=max_hw)(stream)
         return out
 
 
@@ -1101,25 +1092,16 @@ class RoiResize:
                  padding: Optional[int] = None, out: Optional[torch.Tensor] = None,
                  warp: Optional[torch.Tensor] = None) -> torch.Tensor:
         assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 5
-        if crop is not None and warp is not None:
-            raise ValueError("RoiResize: crop and warp together (a warp row carries RandomCrop's translation itself)")
         n, t, h, w, c = frames_u8.shape
-        x = h2d(frames_u8, self.device)
-        box = h2d(box.to(torch.int32), self.device).contiguous()
-        assert tuple(box.shape) == (n, 4)
-        pad = 0
-        if crop is not None:
-            pad = self.size // 10 if padding is None else int(padding)
-            crop = h2d(crop.to(torch.int32), self.device).contiguous()
+        box, crop, pad, warp = _roi_tables("RoiResize", n, self.size, box, crop, padding, warp)
+        x, box = h2d(frames_u8, self.device), h2d(box, self.device)
         if out is None:
             out = torch.empty(n, t, c, self.size, self.size, dtype=self.out_dtype, device=self.device)
         stream = stream_of(self.device)
         if warp is not None:
-            rows = validate_warp_rows(warp)
-            assert tuple(rows.shape) == (n, 6), tuple(rows.shape)
-            self.be.roi_resize_warp(x, self.lut, box, h2d(rows, self.device), out, self.antialias)(stream)
+            self.be.roi_resize_warp(x, self.lut, box, h2d(warp, self.device), out, self.antialias)(stream)
             return out
-        self.be.roi_resize(x, self.lut, box, out, self.antialias, crop, pad)(stream)
+        self.be.roi_resize(x, self.lut, box, out, self.antialias, None if crop is None else h2d(crop, self.device), pad)(stream)
         return out
 
 
